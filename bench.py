@@ -10,9 +10,15 @@ Workload (config.workload): BASELINE configs[1] — `s2t_transformer_w2v2` with 
 front end (7-layer CNN over raw 16 kHz samples + 12 x 768 Transformer), label-smoothed CE, Adam — one full update
 (fwd + bwd + gradient all-reduce + optimizer) per step on a synthetic batch of 32 utterances x <= 30 s per GPU
 (weak scaling), inputs resident in HBM when the clock starts.  Random-init weights, seeded synthetic data.
-Prints ONE JSON line on rank 0."""
+Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the line.  Everything else it can measure runs only with --full:
+the roofline (one more update under per-launch hipEvents, the dominant GEMM launch alone), the H2D figures, the CPU baseline
+and, on one GPU, the extra legs (all-30 s batch, Chimera, beam-search decode).  --dump-outputs DIR writes what the last timed
+step computed as .npy files (dump_outputs); the same arguments give the same inputs in every run."""
 import argparse
 import importlib
+import itertools
 import json
 import os
 import sys
@@ -235,9 +241,43 @@ def cpu_baseline(trainer, task, tasks, ns, args):
             "thread_probe_seconds_4s_utterance": probe}
 
 
+DUMP_SAMPLE = 1 << 22  # elements per sampled array (16 MiB in float32): parameters + gradients stay well under 64 MB
+
+
+def dump_outputs(trainer, out, path):
+    """--dump-outputs: what a caller of Trainer.train_step holds after the last timed step, as .npy files in `path`:
+      * log_<key>.npy — the step's logging output (loss, nll_loss, gnorm, lr, ...), float64, one value each;
+      * params.npy / grads.npy — the updated trainable parameters and the gradient of the step, float32, in named_parameters order,
+        flattened and concatenated.  Above DUMP_SAMPLE elements they are the same fixed sample of that concatenation: DUMP_SAMPLE
+        positions drawn with seed 0, sorted (the sample depends only on the parameter names' order and shapes)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for k, v in sorted((out or {}).items()):
+        np.save(os.path.join(path, "log_%s.npy" % k), np.asarray([v], dtype=np.float64))
+    grads = {id(p): g for p, g in zip(trainer.buffers.params, trainer.buffers.grad_views)}
+    named = [p for _, p in trainer.get_model().named_parameters() if p.requires_grad]
+    sizes = [p.numel() for p in named]
+    total = sum(sizes)
+    if total > DUMP_SAMPLE:
+        idx = torch.randint(0, total, (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort()[0]
+    else:
+        idx = torch.arange(total)
+    starts = [0] + list(itertools.accumulate(sizes))
+    cuts = torch.searchsorted(idx, torch.tensor(starts)).tolist()
+
+    def gather(tensors):
+        parts = [t.detach().reshape(-1)[(idx[lo:hi] - s).to(t.device)].float().cpu()
+                 for t, s, lo, hi in zip(tensors, starts, cuts, cuts[1:]) if hi > lo]
+        return torch.cat(parts).numpy()
+
+    np.save(os.path.join(path, "params.npy"), gather(named))
+    np.save(os.path.join(path, "grads.npy"), gather([grads[id(p)] for p in named]))
+
+
 def measure_train(args, device, rank, lib, traffic=True):
     """Build the model of `args`, run warm-up + timed updates on one resident batch (barrier + synchronize on both sides, MAX over
-    ranks) and — unless --no-roofline — one more update with every C-ABI launch bracketed by hipEvents on its launch stream."""
+    ranks), write the last timed update's outputs if --dump-outputs asks for them and — with --full, unless --no-roofline — run
+    one more update with every C-ABI launch bracketed by hipEvents on its launch stream."""
     import torch.distributed as dist
     trainer, task, tasks, ns = build(args, device)
     sample = make_batch(tasks, task, args, rank, device)  # resident in HBM before the clock starts
@@ -259,16 +299,19 @@ def measure_train(args, device, rank, lib, traffic=True):
     if dist.is_initialized():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(trainer, out, args.dump_outputs)  # (before the roofline update below moves the parameters on)
 
     roof = None
-    if not args.no_roofline:
+    roofline = args.full and not args.no_roofline
+    if roofline:
         # one extra (untimed) update on EVERY rank (its gradient all-reduce is a collective); rank 0 wraps each of its launches
         # in a hipEvent pair on the launch stream
         if rank == 0:
             lib.prof_enable(True)
         trainer.train_step([sample])
         barrier()
-    if not args.no_roofline and rank == 0:
+    if roofline and rank == 0:
         table = lib.prof_query()
         lib.prof_enable(False)
         dom = max(table.items(), key=lambda kv: kv[1]["ms"])
@@ -499,7 +542,15 @@ def main():
     ap.add_argument("--mode", default="train", choices=["train", "decode"], help="decode = BASELINE configs[4] (s2t_transformer_l beam search)")
     ap.add_argument("--beam", type=int, default=5)
     ap.add_argument("--max-len", type=int, default=200)
+    ap.add_argument("--full", action="store_true", help="also the roofline, H2D, CPU-baseline and extra legs (the --no-* switches apply "
+                                                        "to them); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed training step computed to DIR/<name>.npy (dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.mode != "train":
+        ap.error("--dump-outputs writes the outputs of the training step (--mode train)")
 
     dist_mod = importlib.import_module("chimera-st_amd.distributed")
     if dist_mod.needs_self_launch(args.gpus):
@@ -524,10 +575,10 @@ def main():
 
     import torch.distributed as dist
     trainer, task, tasks, ns, sample, dt, out, roof = measure_train(args, device, rank, lib)
-    h2d = h2d_ms(sample, device) if rank == 0 else (None, None)
-    h2d_rate = h2d_overlapped(trainer, sample, device) if (world == 1 and not args.no_extra) else None
+    h2d = h2d_ms(sample, device) if (args.full and rank == 0) else (None, None)
+    h2d_rate = h2d_overlapped(trainer, sample, device) if (args.full and world == 1 and not args.no_extra) else None
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(trainer, task, tasks, ns, args)
         # the oracle restates the reference with plain ATen calls and is slower than the reference itself on the same cores; the
         # ratio was measured in the build container, where /root/reference can be imported (profiles/r01d_cpu_reference_vs_oracle.txt)
@@ -537,7 +588,7 @@ def main():
                                                  "(profiles/r01d_cpu_reference_vs_oracle.txt: 30 s utterance, fp32, reference 4.65 s, oracle 8.43 s per "
                                                  "update, identical loss) and is applied here to whatever thread count this box's probe picked"}
     extra = None
-    if rank == 0 and world == 1 and not args.no_extra and args.model == "s2t_w2v2" and args.mode == "train":
+    if args.full and rank == 0 and world == 1 and not args.no_extra and args.model == "s2t_w2v2" and args.mode == "train":
         # BASELINE configs[3] (Chimera M = 64, joint MT + ST batches) and configs[4] (s2t_transformer_l beam-5 decode) on the same box,
         # so that the driver's record carries them too (short runs: ~15 s together)
         CF = importlib.import_module("chimera-st_amd.functional")
@@ -571,7 +622,7 @@ def main():
         CF.WEIGHT_TRANSPOSES.invalidate()  # the next model must not refresh (or keep alive) this one's W^T copies
         torch.cuda.empty_cache()
         ca = argparse.Namespace(**vars(args))
-        ca.model, ca.steps, ca.warmup = "chimera", 4, 2
+        ca.model, ca.steps, ca.warmup, ca.dump_outputs = "chimera", 4, 2, None
         c_tr, _, _, _, c_sample, c_dt, c_out, c_roof = measure_train(ca, device, rank, lib, traffic=False)
         extra.update({"chimera": {"metric": "train utterances/sec, Chimera s2t_transformer_w2v2_interlingua_base M=64 (triplet_st_mt_contrastive), 1 MI355X",
                              "value": args.batch * ca.steps / c_dt, "unit": "utterances/s", "ms_per_step": c_dt / ca.steps * 1e3, "steps": ca.steps,

@@ -25,7 +25,7 @@ def _run(extra, env=None):
 
 
 def test_bench_line_contract():
-    d = _run([])
+    d = _run(["--full"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
               "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
@@ -52,6 +52,33 @@ def test_bench_line_contract():
     assert x["maxlen"]["value"] > 0 and x["maxlen"]["steps"] == 4 and 0 < x["maxlen"]["mfu"] < 1 and x["maxlen"]["per_class_ms"]["gemm"] > 0
     assert x["chimera"]["value"] > 0 and x["chimera"]["unit"] == "utterances/s" and x["chimera"]["roofline"]["frac"] > 0
     assert x["decode"]["value"] > 0 and x["decode"]["ms_per_decode_step"] > 0 and x["decode"]["roofline"]["bound"] == "hbm"
+
+
+def test_plain_bench_times_the_steps_only_and_dumps_the_last_step(tmp_path):
+    """A plain run (no --full) carries the headline figures and nothing that needs runs of its own; --dump-outputs writes the last
+    timed step's logging output, parameters and gradients, and two runs with the same arguments write the same arrays."""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        out = tmp_path / ("run%d" % i)
+        d = _run(["--dump-outputs", str(out)])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in d, k
+        assert d["steps"] == 2 and d["warmup"] == 1 and d["unit"] == "utterances/s" and d["dtype"] == "bf16"
+        assert abs(d["value"] - 4 * 2 / (d["ms_per_step"] * 2e-3)) / d["value"] < 1e-6
+        assert d["roofline"] is None and d["cpu_baseline"] is None and "extra" not in d
+        assert d["config"]["h2d"]["ms_per_batch"] is None and d["config"]["h2d"]["value_with_h2d"] is None
+        files = sorted(os.listdir(out))
+        assert "params.npy" in files and "grads.npy" in files and "log_loss.npy" in files, files
+        assert sum(os.path.getsize(out / f) for f in files) <= 64 << 20
+        arrs = {f: np.load(out / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        assert float(arrs["log_loss.npy"][0]) == d["config"]["loss"]
+        assert np.isfinite(arrs["params.npy"]).all() and np.isfinite(arrs["grads.npy"]).all() and np.abs(arrs["grads.npy"]).max() > 0
+        dumps.append(arrs)
+    assert sorted(dumps[0]) == sorted(dumps[1])
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f], equal_nan=True), f
 
 
 def test_bench_under_a_process_group():

@@ -115,3 +115,47 @@ def test_bench_algorithmic_flops_of_the_headline_batch():
     nc = Namespace(encoder_embed_dim=512, encoder_ffn_embed_dim=2048, encoder_layers=6, decoder_layers=6, interlingua_length=64, interlingua_layers=3)
     ac = bench.algorithmic_tflop(one, nc, True, conv)
     assert abs(ac["total"] * 1e12 / 6 / 1e9 - 267.1) < 0.8
+
+
+def test_bench_dump_outputs_writes_parameters_and_gradients_in_named_order(tmp_path):
+    """bench.dump_outputs on a small CPU model behind the trainer's flat buffers: the logging output one float64 file per key, the
+    parameters and gradients in named_parameters order (whole, or the same seeded sample of both above DUMP_SAMPLE elements)."""
+    import sys
+
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    optim = importlib.import_module("chimera-st_amd.optim")
+    torch.manual_seed(0)
+    model = torch.nn.Sequential(torch.nn.Linear(7, 5), torch.nn.LayerNorm(5), torch.nn.Linear(5, 3))
+    buffers = optim.FlatParamBuffers(model.parameters())
+    for g in buffers.grad_views:
+        g.copy_(torch.randn_like(g))
+
+    class T:
+        def get_model(self):
+            return model
+
+    trainer = T()
+    trainer.buffers = buffers
+    grads = {id(p): g for p, g in zip(buffers.params, buffers.grad_views)}
+    named = [p for _, p in model.named_parameters()]
+    flat_p = torch.cat([p.detach().reshape(-1) for p in named]).numpy()
+    flat_g = torch.cat([grads[id(p)].reshape(-1) for p in named]).numpy()
+    bench.dump_outputs(trainer, {"loss": 2.5, "gnorm": 0.125}, str(tmp_path / "all"))
+    assert sorted(os.listdir(tmp_path / "all")) == ["grads.npy", "log_gnorm.npy", "log_loss.npy", "params.npy"]
+    loss = np.load(tmp_path / "all" / "log_loss.npy")
+    assert loss.dtype == np.float64 and loss.tolist() == [2.5]
+    p, g = np.load(tmp_path / "all" / "params.npy"), np.load(tmp_path / "all" / "grads.npy")
+    assert p.dtype == np.float32 and g.dtype == np.float32
+    assert np.array_equal(p, flat_p) and np.array_equal(g, flat_g)
+    bench.DUMP_SAMPLE = 16
+    for d in ("s0", "s1"):
+        bench.dump_outputs(trainer, None, str(tmp_path / d))
+    idx = torch.randint(0, flat_p.size, (16,), generator=torch.Generator().manual_seed(0)).sort()[0].numpy()
+    for f, ref in (("params.npy", flat_p), ("grads.npy", flat_g)):
+        a, b = np.load(tmp_path / "s0" / f), np.load(tmp_path / "s1" / f)
+        assert a.shape == (16,) and np.array_equal(a, b) and np.array_equal(a, ref[idx])

@@ -38,11 +38,11 @@ python tools/pmc_gemm_one.py $O/pmc_g8_ea $O/pmc_g8_hm 47968 3072 768 "$BUILD gr
 rm -rf $O/trace $O/pmc_mfma $O/pmc_hbm $O/dec_trace $O/pmc_one_ea $O/pmc_one_hm $O/pmc_g8_ea $O/pmc_g8_hm
 # the bench lines below quote the counter files of THIS build
 cp $O/${TAG}_pmc_gemm_class.json $O/${TAG}_pmc_gemm.json $R/profiles/
-python bench.py > $O/${TAG}_bench_s2t.json 2> $O/bench_s2t.err
-python bench.py --model chimera --no-cpu-baseline --no-extra > $O/${TAG}_bench_chimera.json 2> $O/bench_chimera.err
-python bench.py --dropout 0 --no-cpu-baseline --no-extra > $O/${TAG}_bench_dropout0.json 2> $O/bench_dropout0.err
+python bench.py --full > $O/${TAG}_bench_s2t.json 2> $O/bench_s2t.err
+python bench.py --full --model chimera --no-cpu-baseline --no-extra > $O/${TAG}_bench_chimera.json 2> $O/bench_chimera.err
+python bench.py --full --dropout 0 --no-cpu-baseline --no-extra > $O/${TAG}_bench_dropout0.json 2> $O/bench_dropout0.err
 python bench.py --mode decode > $O/${TAG}_bench_decode.json 2> $O/bench_decode.err
-python bench.py --lengths max --no-cpu-baseline --no-extra > $O/${TAG}_bench_maxlen.json 2> $O/bench_maxlen.err
+python bench.py --full --lengths max --no-cpu-baseline --no-extra > $O/${TAG}_bench_maxlen.json 2> $O/bench_maxlen.err
 python tools/probes/hipblaslt_names.py 2>/dev/null | grep ratio > $O/${TAG}_hipblaslt_vs_this_library.txt
 python tools/gemm_shapes_in_step.py > $O/${TAG}_gemm_shapes_in_step.txt 2>/dev/null
 python tools/vendor_in_step.py > $O/${TAG}_vendor_in_step.txt 2>/dev/null

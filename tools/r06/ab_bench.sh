@@ -4,8 +4,8 @@
 O=$1; N=${2:-2}
 for i in $(seq $N); do
   for which in new old; do
-    if [ $which = new ]; then python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-extra > /tmp/ab.json 2>/dev/null
-    else CST_AB_LIB=$O python tools/ab_lib.py bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-extra > /tmp/ab.json 2>/dev/null; fi
+    if [ $which = new ]; then python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --no-extra > /tmp/ab.json 2>/dev/null
+    else CST_AB_LIB=$O python tools/ab_lib.py bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --no-extra > /tmp/ab.json 2>/dev/null; fi
     python - $which <<'PY'
 import json, sys
 d = json.loads(open("/tmp/ab.json").read().strip().splitlines()[-1])

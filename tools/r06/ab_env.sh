@@ -3,8 +3,8 @@
 V=$1; N=${2:-2}
 for i in $(seq $N); do
   for which in base alt; do
-    if [ $which = base ]; then python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-extra > /tmp/ab.json 2>/tmp/ab.err
-    else env $V python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-extra > /tmp/ab.json 2>/tmp/ab.err; fi
+    if [ $which = base ]; then python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --no-extra > /tmp/ab.json 2>/tmp/ab.err
+    else env $V python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --no-extra > /tmp/ab.json 2>/tmp/ab.err; fi
     python - $which <<'PY'
 import json, sys
 try:
