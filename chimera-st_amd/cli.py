@@ -16,7 +16,7 @@ import time
 
 import torch
 
-from . import checkpoint_utils, criterions, registry, s2t_transformer, tasks, w2v2_transformer, w2v2_transformer_interlingua  # noqa: F401
+from . import checkpoint_utils, criterions, fbank, registry, s2t_transformer, tasks, w2v2_transformer, w2v2_transformer_interlingua  # noqa: F401
 from .distributed import distributed_init, launch_ranks, needs_self_launch
 from .hostcfg import limit_host_threads
 from .trainer import Trainer
@@ -269,11 +269,15 @@ def generate_main(argv=None):
     for sample in itr.next_epoch_itr(shuffle=False):
         if not sample:
             continue
-        src = sample["net_input"]["src_tokens"]
+        ni = sample["net_input"]
+        if "src_audio" in ni:  # fbank route (data.py): filter banks of the audio batch, computed on the device
+            ni = fbank.materialize({k: (v.cuda() if torch.is_tensor(v) else v) for k, v in ni.items()},
+                                   max_frames=int(ni["src_lengths"].max()))
+        src = ni["src_tokens"]
         # raw waveforms [B, S] stay fp32 as in training (Trainer._prepare_sample: conv0 reads fp32 samples); only feature
         # inputs [B, T, F] take the model's storage dtype
         src = src.to("cuda", dtype) if (src.dim() == 3 and src.is_floating_point()) else src.cuda()
-        s = {"net_input": {"src_tokens": src, "src_lengths": sample["net_input"]["src_lengths"].cuda()}}
+        s = {"net_input": {"src_tokens": src, "src_lengths": ni["src_lengths"].cuda()}}
         results = task.inference_step(gen, [model], s)
         for i, sid in enumerate(sample["id"].tolist()):
             ref = tgt_dict.string(sample["target"][i]) if sample.get("target") is not None else None

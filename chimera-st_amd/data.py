@@ -2,18 +2,21 @@
   fairseq/data/audio/speech_to_text_dataset.py  S2TDataConfig :30-115, get_features_or_waveform :165-204, _collate_frames :207-225,
                                                 SpeechToTextDataset :228-420, SpeechToTextDatasetCreator :423-557
   fairseq/data/audio/triplet_dataset.py         TripletDataConfig :34-48, TripletDataset :51-244, TripletDatasetCreator :247-370
-  fairseq/data/audio/audio_utils.py             get_waveform / get_waveform_chi :7-55 (soundfile -> cst_wav_read_f32)
+  fairseq/data/audio/audio_utils.py             get_waveform / get_waveform_chi :7-55 (soundfile -> cst_wav_read_f32),
+                                                get_fbank :80-93 (-> the device feature stage, fbank.py / csrc/fbank.hip)
+  fairseq/data/audio/feature_transforms/        utterance_cmvn / global_cmvn / specaugment (fbank.py)
   fairseq/data/data_utils.py                    collate_tokens :34-64, numpy_seed :115-128, _filter_by_size_dynamic :148-184,
                                                 batch_by_size :276-337 (Cython batch_by_size_fast -> cst_batch_by_size)
   fairseq/data/iterators.py                     EpochBatchIterator._get_iterator_for_epoch :384-435, ShardedIterator :470-500
   fairseq/data/encoders/sentencepiece_bpe.py    SentencepieceBPE :20-47
 Wire formats kept: the MuST-C TSV manifest (id, audio, n_frames, tgt_text, src_text, speaker[, src_lang, tgt_lang]) with
-`audio` = "<wav path>[:<offset>:<length>]", the data config YAML of chimera/tools/hand-make-config.py, the fairseq dictionary
+`audio` = "<wav path>[:<offset>:<length>]" | "<.npy path>" | "<zip path>:<byte offset>:<byte length>", the data config YAML of chimera/tools/hand-make-config.py, the fairseq dictionary
 file, and the collater's `sample` dict.  Host-only code: decoded batches are handed to the trainer as CPU tensors (pinned when
 asked) and moved to the GPU by it."""
 import contextlib
 import csv
 import ctypes
+import io
 import math
 import os.path as op
 import re
@@ -23,6 +26,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from . import fbank as FB
 from . import lib as L
 from .tasks import collate_tokens
 
@@ -55,6 +59,13 @@ class S2TDataConfig:
         t = cur.get("_train") if t is None and is_train else t
         t = cur.get("_eval") if t is None and not is_train else t
         return cur.get("*") if t is None else t
+
+    def get_feature_transforms_config(self, split, is_train):
+        """speech_to_text_dataset.py:100-123: the config with "transforms" = the split's list (per-transform settings under
+        their names)."""
+        cfg = dict(self.config)
+        cfg["transforms"] = self.get_feature_transforms(split, is_train)
+        return cfg
 
 
 class TripletDataConfig(S2TDataConfig):
@@ -113,8 +124,59 @@ def get_waveform(path, offset=0, length=-1):
     return (out if ch.value == 1 else out.reshape(-1, ch.value)), sr.value
 
 
+def read_from_uncompressed_zip(file_path, offset, file_size) -> bytes:
+    """speech_to_text_dataset.py:138-142."""
+    with open(file_path, "rb") as f:
+        f.seek(offset)
+        return f.read(file_size)
+
+
+def _features_from_zip(path, byte_offset, byte_size):
+    """speech_to_text_dataset.py:151-162 for .npy members (the reference prep's fbank80.zip); audio members are rejected."""
+    data = read_from_uncompressed_zip(path, byte_offset, byte_size)
+    if len(data) >= 2 and data[0] == 147 and data[1] == 78:  # is_npy_data
+        return np.load(io.BytesIO(data))
+    if len(data) >= 2 and ((data[0] == 102 and data[1] == 76) or (data[0] == 82 and data[1] == 73)):  # is_flac_or_wav_data
+        raise ValueError("%s:%d:%d: WAV/FLAC bytes inside a zip are not supported; store .npy features in the zip, or list the "
+                         ".wav file itself" % (path, byte_offset, byte_size))
+    raise ValueError('Unknown file format for "%s"' % path)
+
+
+def fbank_audio_entry(path: str):
+    """The (wav path, sample offset, sample count) of a manifest entry that takes the device fbank route when use_audio_input is
+    false ("x.wav" or "x.wav:<offset>:<count>"), or None for a feature entry (.npy, stored zip)."""
+    _path, *extra = path.split(":")
+    ext = op.splitext(_path)[1].lower()
+    if ext == ".flac":
+        raise ValueError("%s: FLAC decoding is not supported; convert the audio to 16-bit PCM WAV" % path)
+    if ext != ".wav":
+        return None
+    if len(extra) == 0:
+        return _path, 0, -1
+    if len(extra) == 2:
+        return _path, int(extra[0]), int(extra[1])
+    raise ValueError("Invalid path: %s" % path)
+
+
+def get_fbank_audio(path: str, sample_rate=16000):
+    """The mono 16 kHz waveform (float32 in [-1, 1)) of an fbank-route entry, checked for what the device stage computes."""
+    _path, offset, length = fbank_audio_entry(path)
+    if not op.exists(_path):
+        raise FileNotFoundError("File not found: %s" % _path)
+    wave, sr = get_waveform(_path, offset, length)
+    if wave.ndim != 1:
+        raise ValueError("%s: multi-channel audio (%d channels) is not supported on the fbank route" % (path, wave.shape[1]))
+    if sr != FB.SAMPLE_RATE or sample_rate != FB.SAMPLE_RATE:
+        raise ValueError("%s: sample rate %d Hz; the fbank route computes 16000 Hz filter banks only" % (path, sr))
+    if len(wave) < FB.WIN:
+        raise ValueError("%s: %d samples is shorter than one %d-sample frame (0 filter-bank frames)" % (path, len(wave), FB.WIN))
+    return wave
+
+
 def get_features_or_waveform(path: str, need_waveform=False, sample_rate=16000):
-    """speech_to_text_dataset.py:165-204: "<.npy/.wav path>" or "<wav path>:<sample offset>:<sample count>"."""
+    """speech_to_text_dataset.py:165-204: "<.npy/.wav path>", "<wav path>:<sample offset>:<sample count>" or
+    "<zip path>:<byte offset>:<byte length>".  Filter banks of audio (need_waveform false) are not computed here: those entries
+    take the device route (fbank_audio_entry / get_fbank_audio, fbank.py)."""
     _path, *extra = path.split(":")
     if not op.exists(_path):
         raise FileNotFoundError("File not found: %s" % _path)
@@ -122,13 +184,17 @@ def get_features_or_waveform(path: str, need_waveform=False, sample_rate=16000):
         if need_waveform:
             wave, sr = get_waveform(_path)
             return wave[::(sr // sample_rate)] if sr != sample_rate else wave
-        if op.splitext(_path)[1] == ".npy":
+        ext = op.splitext(_path)[1]
+        if ext == ".npy":
             return np.load(_path)
-        raise NotImplementedError("filter-bank extraction from audio (torchaudio/kaldi) is not on the Chimera wave path; "
-                                  "precomputed .npy features or use_audio_input: true")
+        if ext in (".wav", ".flac"):
+            raise NotImplementedError("filter banks of %s are computed on the device: SpeechToTextDataset's fbank route" % _path)
+        raise ValueError('Unsupported file format for "%s"' % _path)
     if len(extra) == 2:
         if _path.endswith(".zip"):
-            raise NotImplementedError("zip-packed feature archives are not on the Chimera wave path")
+            if need_waveform:
+                raise NotImplementedError("audio inside zip archives is not on the Chimera wave path")
+            return _features_from_zip(_path, int(extra[0]), int(extra[1]))
         assert need_waveform, "path %s and not need_waveform conflict" % _path
         wave, sr = get_waveform(_path, int(extra[0]), int(extra[1]))
         return wave[::(sr // sample_rate)] if sr != sample_rate else wave
@@ -175,6 +241,15 @@ def batch_by_size(indices, num_tokens_fn, max_tokens=None, max_sentences=None, r
     return [indices[e - n:e].tolist() for n, e in zip(out[:nb], ends)]
 
 
+class FbankAudio:
+    """An item of the fbank route: the utterance's waveform [S] (float32 in [-1, 1)), its frame count and SpecAugment's
+    intervals ([(f0, f)], [(t0, t)])."""
+    __slots__ = ("wave", "n_frames", "fmask", "tmask")
+
+    def __init__(self, wave, n_frames, fmask, tmask):
+        self.wave, self.n_frames, self.fmask, self.tmask = wave, n_frames, fmask, tmask
+
+
 # --------------------------------------------------------------------------------------------------------------------
 class SpeechToTextDataset(torch.utils.data.Dataset):
     """speech_to_text_dataset.py:228-420."""
@@ -197,10 +272,20 @@ class SpeechToTextDataset(torch.utils.data.Dataset):
         self.check_tgt_lang_tag()
         self.ids = ids
         self.shuffle = data_cfg.shuffle if is_train_split else False
+        self.feature_transforms = None
         if data_cfg.get_feature_transforms(split, is_train_split):
-            raise NotImplementedError("feature transforms (specaugment / cmvn on filter banks) are not on the wave-input path")
+            if data_cfg.use_audio_input:
+                raise NotImplementedError("feature transforms (specaugment / cmvn on filter banks) are not on the wave-input path")
+            self.feature_transforms = FB.build_transforms(data_cfg.get_feature_transforms_config(split, is_train_split))
+        self._device_transforms = None
         self.pre_tokenizer, self.bpe_tokenizer = pre_tokenizer, bpe_tokenizer
         self.normalize, self.mask, self.sample_rate = normalize, mask, sample_rate
+
+    def device_transforms(self):
+        """The transforms in the form the device feature stage applies them (raises on an order it does not fuse)."""
+        if self._device_transforms is None:
+            self._device_transforms = FB.DeviceTransforms(self.feature_transforms)
+        return self._device_transforms
 
     @classmethod
     def is_lang_tag(cls, token):
@@ -221,13 +306,28 @@ class SpeechToTextDataset(torch.utils.data.Dataset):
         return text
 
     def _source(self, index):
-        source = get_features_or_waveform(self.audio_paths[index], need_waveform=self.data_cfg.use_audio_input,
-                                          sample_rate=self.sample_rate)
+        path = self.audio_paths[index]
+        if not self.data_cfg.use_audio_input and fbank_audio_entry(path) is not None:
+            return self._fbank_audio(path)
+        source = get_features_or_waveform(path, need_waveform=self.data_cfg.use_audio_input, sample_rate=self.sample_rate)
+        if self.feature_transforms is not None:
+            source = self.feature_transforms(source)  # speech_to_text_dataset.py:310-312
         source = torch.from_numpy(np.ascontiguousarray(source)).float()
         if self.normalize:
             with torch.no_grad():
                 source = F.layer_norm(source, source.shape)
         return source
+
+    def _fbank_audio(self, path):
+        """The fbank route: the waveform and, where the reference would run its transforms, SpecAugment's draws (the values are
+        computed on the device when the trainer / generator materialises the batch: fbank.materialize)."""
+        if self.normalize:
+            raise ValueError("--normalize is not supported on the fbank route (%s): the filter banks are computed on the device" % path)
+        tr = self.device_transforms()
+        wave = get_fbank_audio(path, self.sample_rate)
+        n = FB.num_frames(len(wave))
+        fmask, tmask = tr.draw(n)
+        return FbankAudio(torch.from_numpy(np.ascontiguousarray(wave, dtype=np.float32)), n, fmask, tmask)
 
     def _target(self, index):
         if self.tgt_texts is None:
@@ -247,8 +347,19 @@ class SpeechToTextDataset(torch.utils.data.Dataset):
 
     def _collate_common(self, samples):
         indices = torch.tensor([s[0] for s in samples], dtype=torch.long)
-        frames = _collate_frames([s[1] for s in samples], self.data_cfg.use_audio_input)
-        n_frames = torch.tensor([s[1].size(0) for s in samples], dtype=torch.long)
+        audio_route = isinstance(samples[0][1], FbankAudio)
+        if any(isinstance(s[1], FbankAudio) != audio_route for s in samples):
+            raise ValueError("a batch mixes .wav entries (device filter banks) with feature entries (.npy / zip)")
+        if audio_route:
+            # padded waveform; the row length is rounded up to a multiple of 4 samples (16-byte rows for the device stage)
+            smax = max(s[1].wave.size(0) for s in samples)
+            frames = torch.zeros(len(samples), (smax + 3) // 4 * 4)
+            for i, s in enumerate(samples):
+                frames[i, :s[1].wave.size(0)] = s[1].wave
+            n_frames = torch.tensor([s[1].n_frames for s in samples], dtype=torch.long)
+        else:
+            frames = _collate_frames([s[1] for s in samples], self.data_cfg.use_audio_input)
+            n_frames = torch.tensor([s[1].size(0) for s in samples], dtype=torch.long)
         n_frames, order = n_frames.sort(descending=True)  # sort samples by descending number of frames
         indices, frames = indices.index_select(0, order), frames.index_select(0, order)
         target = target_lengths = prev_output_tokens = ntokens = None
@@ -259,8 +370,18 @@ class SpeechToTextDataset(torch.utils.data.Dataset):
             prev_output_tokens = collate_tokens(tg, self.tgt_dict.pad(), self.tgt_dict.eos(),
                                                 move_eos_to_beginning=True).index_select(0, order)
             ntokens = sum(t.size(0) for t in tg)
+        if audio_route:
+            srcs = [samples[i][1] for i in order.tolist()]
+            tr = self.device_transforms()
+            net_input = {"src_audio": frames, "src_audio_lengths": torch.tensor([a.wave.size(0) for a in srcs], dtype=torch.long),
+                         "src_lengths": n_frames, "src_audio_transforms": tr,
+                         "src_audio_fmask": FB.intervals_tensor([a.fmask for a in srcs], tr.n_fmask),
+                         "src_audio_tmask": FB.intervals_tensor([a.tmask for a in srcs], tr.n_tmask),
+                         "prev_output_tokens": prev_output_tokens, "mask": self.mask}
+        else:
+            net_input = {"src_tokens": frames, "src_lengths": n_frames, "prev_output_tokens": prev_output_tokens, "mask": self.mask}
         out = {"id": indices,
-               "net_input": {"src_tokens": frames, "src_lengths": n_frames, "prev_output_tokens": prev_output_tokens, "mask": self.mask},
+               "net_input": net_input,
                "target": target, "target_lengths": target_lengths, "ntokens": ntokens, "nsentences": len(samples)}
         return out, order
 

@@ -9,7 +9,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libcst_hip.so")
-ABI_VERSION = 6  # include/cst.h: CST_ABI_VERSION
+ABI_VERSION = 7  # include/cst.h: CST_ABI_VERSION
 
 F32, BF16 = 0, 1
 ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
@@ -94,6 +94,21 @@ class BeamDesc(ctypes.Structure):
     ]
 
 
+class FbankDesc(ctypes.Structure):
+    _fields_ = [
+        ("B", c_i64), ("S", c_i64), ("T", c_i64),
+        ("wave", c_p), ("n_samples", c_p), ("out", c_p), ("n_frames", c_p),
+        ("utterance_cmvn", c_int), ("norm_means", c_int), ("norm_vars", c_int),
+        ("global_mean", c_p), ("global_std", c_p),
+        ("global_first", c_int),
+        ("specaugment", c_int),
+        ("n_fmask", c_int), ("n_tmask", c_int),
+        ("fmask", c_p), ("tmask", c_p),
+        ("mask_mean", c_int), ("mask_value", c_f),
+        ("workspace", c_p), ("workspace_bytes", c_i64),
+    ]
+
+
 # every symbol include/cst.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("cst_last_error", ctypes.c_char_p, []),
@@ -160,6 +175,8 @@ SYMBOLS = [
     ("cst_wav_info", c_int, [ctypes.c_char_p, c_p, c_p, c_p, c_p]),
     ("cst_wav_read_f32", c_i64, [ctypes.c_char_p, c_i64, c_i64, c_p, c_i64]),
     ("cst_dec_cross_attn", c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_f, c_int, c_p]),
+    ("cst_fbank_workspace_bytes", c_i64, [c_i64, c_i64]),
+    ("cst_fbank", c_int, [ctypes.POINTER(FbankDesc), c_p]),
     ("cst_dec_ln_q_cross_attn", c_int, [c_p, c_i64, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_f, c_int, c_p]),
 ]
 

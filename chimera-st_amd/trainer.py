@@ -12,7 +12,7 @@ import torch
 import torch.distributed as dist
 
 from .distributed import DistributedFairseqModel, all_reduce_stats
-from . import rng
+from . import fbank, rng
 from .profiling import scope
 from .hostcfg import limit_host_threads
 from .optim import ALIGN, FlatParamBuffers, FusedAdam, qkv_groups
@@ -123,7 +123,8 @@ class Trainer:
         rng.reseed(seed)  # dropout sites of the HIP path: keys = f(seed, site ordinal)
 
     def _prepare_sample(self, sample):
-        """trainer.py:896-932: H2D; the waveform stays fp32 (conv0 reads it directly), token tensors stay int64."""
+        """trainer.py:896-932: H2D; the waveform stays fp32 (conv0 reads it directly), token tensors stay int64.  A batch of the
+        fbank route (net_input["src_audio"], data.py) gets its filter banks computed on the device here (fbank.materialize)."""
         def mv(x):
             if torch.is_tensor(x):
                 return x.to(self.device, non_blocking=True)
@@ -131,7 +132,11 @@ class Trainer:
                 return {k: mv(v) for k, v in x.items()}
             return x
 
-        return mv(sample)
+        out = mv(sample)
+        ni = sample.get("net_input") if isinstance(sample, dict) else None
+        if ni and "src_audio" in ni:
+            out["net_input"] = fbank.materialize(out["net_input"], max_frames=int(ni["src_lengths"].max()))
+        return out
 
     def train_step(self, samples, raise_oom=False):
         """`_train_step` inside the "train_step-N" range of the reference (fairseq_cli/train.py:225-227; N = updates done so far).

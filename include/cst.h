@@ -30,9 +30,9 @@ extern "C" {
 
 /* Bumps on any change of a signature or a descriptor layout (3: cst_gemm_desc.m_len, cst_attn_desc.seq_offsets, workspaces of the
  * fixed-order reductions; 4: cst_attn_desc.kpm_bits / bwd_ws, the separable attention-dropout mask; 5: cst_gemm_desc.colsum;
- * 6: cst_dec_ln_q_cross_attn).
+ * 6: cst_dec_ln_q_cross_attn; 7: cst_fbank_desc, cst_fbank, cst_fbank_workspace_bytes).
  * cst_version() returns the value the library was built with; chimera-st_amd/lib.py refuses a mismatch. */
-#define CST_ABI_VERSION 6
+#define CST_ABI_VERSION 7
 
 typedef enum { CST_F32 = 0, CST_BF16 = 1 } cst_dtype;
 
@@ -543,6 +543,47 @@ int cst_dec_cross_attn(const void* q, const void* kx, const void* vx, const uint
 int cst_dec_ln_q_cross_attn(const void* x, int64_t ldx, const void* Wg, const float* sg, const float* sb, float eps, const void* kx, const void* vx,
                             const uint8_t* key_padding_mask, void* out, const int32_t* step, int64_t max_len, int64_t bsz, int64_t beam, int64_t H,
                             int64_t D, int64_t S, float scale, int dtype, cst_stream stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Filter banks of collated 16 kHz audio — replaces the per-utterance host feature extraction of the fbank-input route:
+ *   get_features_or_waveform -> get_features_from_npy_or_audio -> get_fbank
+ *                                             fairseq/data/audio/speech_to_text_dataset.py:143-147
+ *   torchaudio.compliance.kaldi.fbank(wave, num_mel_bins=80, sample_frequency=16000)
+ *                                             fairseq/data/audio/audio_utils.py:80-93 (input x 2^15, no dither)
+ * and the transforms __getitem__ applies to its result (speech_to_text_dataset.py:310-312, CompositeAudioFeatureTransform):
+ *   utterance_cmvn  feature_transforms/utterance_cmvn.py:26-37   global_cmvn  feature_transforms/global_cmvn.py:20-23
+ *   specaugment     feature_transforms/specaugment.py:79-133 (masks only: the intervals are drawn on the host; no time warp)
+ * wave: fp32 [B, S] (row stride S), samples in [-1, 1); n_samples: int64 [B] on the device (clamped to S).  T_i = 1 + (n_i - 400)
+ * / 160 frames (0 below 400 samples).  out: fp32 [B, T, 80], 16-byte aligned; rows t >= T_i are 0 (T should be max T_i; frames
+ * beyond T are not computed).  n_frames: int64 [B] (optional) receives T_i.
+ * Transforms, applied in this order: CMVN — utterance_cmvn (norm_means / norm_vars) and global_cmvn (global_mean / global_std fp32
+ * [80], NULL = absent), global first when global_first — then SpecAugment when `specaugment`: cells of the frequency intervals
+ * fmask int32 [B][n_fmask][2] = (f0, width) and the time intervals tmask int32 [B][n_tmask][2] = (t0, width) (width 0 = no mask,
+ * at most 8 of each) take mask_value, or the mean of the spectrogram entering SpecAugment when mask_mean.  Utterance statistics
+ * are per-tile partial sums (fp64) reduced by a second launch in a fixed order: bit-reproducible.  workspace (8-byte aligned,
+ * cst_fbank_workspace_bytes(B, T) bytes) is needed when any transform is configured; without one, one launch writes `out`.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+  int64_t B, S, T;
+  const float* wave;
+  const int64_t* n_samples;
+  float* out;
+  int64_t* n_frames;
+  int utterance_cmvn, norm_means, norm_vars;
+  const float* global_mean;
+  const float* global_std;
+  int global_first;
+  int specaugment;
+  int n_fmask, n_tmask;
+  const int32_t* fmask;
+  const int32_t* tmask;
+  int mask_mean;
+  float mask_value;
+  void* workspace;
+  int64_t workspace_bytes;
+} cst_fbank_desc;
+int64_t cst_fbank_workspace_bytes(int64_t B, int64_t T);
+int cst_fbank(const cst_fbank_desc* d, cst_stream stream);
 
 /* ------------------------------------------------------------------------------------------
  * Host-side (CPU) natives of the input pipeline — no device work, no stream.
