@@ -808,6 +808,67 @@ def conv0_gn_gelu(wav, weight, gn_weight, gn_bias, stride, eps=1e-5, write_limit
 
 
 # ------------------------------------------------------------------------------------------------
+# the feature extractor in extractor_mode="layer_norm": conv (+ bias) -> LayerNorm over channels -> GELU in every layer
+# ------------------------------------------------------------------------------------------------
+class _Conv0LnFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, wav, w, bias, gamma, beta, stride, eps, write_limit, grad_limit):
+        C, _, k = w.shape
+        w2 = w.reshape(C, k).contiguous()
+        wav = wav.float().contiguous()
+        if _os.environ.get("CST_NO_MLEN") or _os.environ.get("CST_GEMM_NO_KLIVE"):
+            write_limit = grad_limit = None  # (with the GEMM-side skipping off, every frame of this layer is read)
+        y, mean, rstd = K.conv0_ln_fwd(wav, w2, bias, gamma, beta, k, stride, eps, frame_limit=write_limit)
+        ctx.save_for_backward(wav, w2, bias, gamma, beta, mean, rstd)
+        ctx.k, ctx.stride, ctx.grad_limit = k, stride, grad_limit
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        wav, w2, bias, gamma, beta, mean, rstd = ctx.saved_tensors
+        dw, dbi, dg, db = K.conv0_ln_bwd(dy.contiguous(), wav, w2, bias, gamma, beta, mean, rstd, ctx.k, ctx.stride, frame_limit=ctx.grad_limit)
+        return (None, dw.view(w2.shape[0], 1, ctx.k).to(w2.dtype), dbi.to(bias.dtype), dg.to(gamma.dtype), db.to(gamma.dtype),
+                None, None, None, None)
+
+
+def conv0_ln_gelu(wav, weight, bias, ln_weight, ln_bias, stride, eps=1e-5, write_limit=None, grad_limit=None):
+    """wav [B,S] -> channels-last [B, L, C] = GELU(LayerNorm_C(conv1d(wav, weight[C,1,k], stride) + bias)), one pass
+    (cst_conv0_ln_gelu_fwd / _bwd).  write_limit / grad_limit as in conv0_gn_gelu."""
+    return _Conv0LnFn.apply(wav, weight, bias, ln_weight, ln_bias, stride, eps, write_limit, grad_limit)
+
+
+class _LnGeluFn(torch.autograd.Function):
+    """y = GELU(LayerNorm_C(u)) over channels-last rows [B, L, C].  `conv_bias` (optional) is the bias the conv GEMM in front added to
+    u: its gradient is the column sum of du, which the backward kernel accumulates on its way (the conv is then called with a
+    detached bias and needs no column-sum pass of its own)."""
+
+    @staticmethod
+    def forward(ctx, u, gamma, beta, conv_bias, eps, row_limit):
+        if _os.environ.get("CST_NO_MLEN"):
+            row_limit = None
+        u = u if u.is_contiguous() else u.contiguous()
+        y, mean, rstd = K.ln_gelu_fwd(u, gamma, beta, eps, row_limit)
+        ctx.save_for_backward(u, gamma, beta, mean, rstd)
+        ctx.row_limit = row_limit
+        ctx.bias_dtype = conv_bias.dtype if conv_bias is not None else None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        u, gamma, beta, mean, rstd = ctx.saved_tensors
+        want_bias = ctx.bias_dtype is not None and ctx.needs_input_grad[3]
+        du, dg, db, dc = K.ln_gelu_bwd(dy if dy.is_contiguous() else dy.contiguous(), u, gamma, beta, mean, rstd, ctx.row_limit,
+                                       want_colsum=want_bias, padded=True)
+        return du, dg.to(gamma.dtype), db.to(gamma.dtype), (dc.to(ctx.bias_dtype) if want_bias else None), None, None
+
+
+def ln_gelu(u, ln_weight, ln_bias, conv_bias=None, eps=1e-5, row_limit=None):
+    """GELU(LayerNorm over the last axis) of u [B, L, C] (cst_ln_gelu_fwd / _bwd).  row_limit (int32 [B]): rows t >= row_limit[b] are
+    read by nobody and carry exactly zero gradient (cst_conv_row_limits): they are skipped and come back as zeros."""
+    return _LnGeluFn.apply(u, ln_weight, ln_bias, conv_bias, eps, row_limit)
+
+
+# ------------------------------------------------------------------------------------------------
 # channels-last conv1d as implicit GEMM (wav2vec2 conv layers 1.., subsampler)
 # ------------------------------------------------------------------------------------------------
 def _padded_base(t, L, C):

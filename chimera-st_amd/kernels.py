@@ -501,6 +501,77 @@ def conv0_bwd(dy, wav, w, gamma, beta, mean, rstd, gram, k, stride, frame_limit=
     return dw, dg, db
 
 
+def conv0_ln_fwd(wav, w, bias, gamma, beta, k, stride, eps=1e-5, frame_limit=None):
+    """Layer 0 of the layer-norm feature extractor.  wav [B,S] fp32; w [C,k]; bias, gamma, beta [C] -> y [B,L,C] channels-last and the
+    per-frame (mean, rstd) [B,L].  frame_limit (int32 [B]): frames from there on are unread and left unwritten (include/cst.h)."""
+    assert wav.dtype == torch.float32 and wav.is_contiguous()
+    B, S = wav.shape
+    C = w.shape[0]
+    Lo = (S - k) // stride + 1
+    y = torch.empty(B, Lo, C, dtype=w.dtype, device=wav.device)
+    mean = torch.empty(B, Lo, dtype=torch.float32, device=wav.device)
+    rstd = torch.empty(B, Lo, dtype=torch.float32, device=wav.device)
+    L.check(L.load().cst_conv0_ln_gelu_fwd(L.ptr(wav), L.ptr(w), L.ptr(bias), L.ptr(gamma), L.ptr(beta), L.ptr(y), L.ptr(mean),
+                                           L.ptr(rstd), _lim(frame_limit, B), B, S, C, k, stride, eps, L.dtype_code(w.dtype),
+                                           L.stream_ptr()), "cst_conv0_ln_gelu_fwd")
+    return y, mean, rstd
+
+
+def conv0_ln_bwd(dy, wav, w, bias, gamma, beta, mean, rstd, k, stride, frame_limit=None):
+    """-> (dw [C,k], dbias, dgamma, dbeta [C]) fp32."""
+    B, S = wav.shape
+    C = w.shape[0]
+    lib = L.load()
+    dw = torch.empty(C, k, dtype=torch.float32, device=wav.device)
+    dbi, dg, db = (torch.empty(C, dtype=torch.float32, device=wav.device) for _ in range(3))
+    ws = workspace(lib.cst_conv0_ln_bwd_workspace(B, S, C, k, stride), wav.device)
+    L.check(lib.cst_conv0_ln_gelu_bwd(L.ptr(dy), L.ptr(wav), L.ptr(w), L.ptr(bias), L.ptr(gamma), L.ptr(beta), L.ptr(mean),
+                                      L.ptr(rstd), L.ptr(dw), L.ptr(dbi), L.ptr(dg), L.ptr(db), L.ptr(ws), _lim(frame_limit, B), B, S,
+                                      C, k, stride, L.dtype_code(w.dtype), L.stream_ptr()), "cst_conv0_ln_gelu_bwd")
+    return dw, dbi, dg, db
+
+
+def _row_lim(row_limit, B):
+    if row_limit is None:
+        return None
+    assert row_limit.dtype == torch.int32 and row_limit.numel() == B and row_limit.is_contiguous()
+    return L.ptr(row_limit)
+
+
+def ln_gelu_fwd(u, gamma, beta, eps=1e-5, row_limit=None):
+    """u [B,L,C] contiguous -> y = GELU(LayerNorm_C(u)), (mean, rstd) [B,L].  Rows t >= row_limit[b] are not read; y is zero there."""
+    assert u.dim() == 3 and u.is_contiguous()
+    B, Lr, C = u.shape
+    y = torch.empty_like(u)
+    mean = torch.empty(B, Lr, dtype=torch.float32, device=u.device)
+    rstd = torch.empty(B, Lr, dtype=torch.float32, device=u.device)
+    L.check(L.load().cst_ln_gelu_fwd(L.ptr(u), L.ptr(gamma), L.ptr(beta), L.ptr(y), L.ptr(mean), L.ptr(rstd), _row_lim(row_limit, B),
+                                     B, Lr, C, eps, L.dtype_code(u.dtype), L.stream_ptr()), "cst_ln_gelu_fwd")
+    return y, mean, rstd
+
+
+def ln_gelu_bwd(dy, u, gamma, beta, mean, rstd, row_limit=None, want_colsum=False, padded=False):
+    """-> (du, dgamma, dbeta, colsum(du) or None); the three vectors fp32.  padded: du is the interior view of a [B, L+2, C] allocation
+    whose first and last row per utterance are zero (what the windowed dX GEMMs of functional.conv1d_cl read without a copy)."""
+    assert dy.is_contiguous() and u.is_contiguous()
+    B, Lr, C = u.shape
+    lib = L.load()
+    if padded:
+        full = torch.empty(B, Lr + 2, C, dtype=u.dtype, device=u.device)
+        full[:, 0].zero_()
+        full[:, Lr + 1].zero_()
+        du = full[:, 1:1 + Lr]
+    else:
+        du = torch.empty_like(u)
+    dg, db = (torch.empty(C, dtype=torch.float32, device=u.device) for _ in range(2))
+    dc = torch.empty(C, dtype=torch.float32, device=u.device) if want_colsum else None
+    ws = workspace(lib.cst_ln_gelu_bwd_workspace(B * Lr, C), u.device)
+    L.check(lib.cst_ln_gelu_bwd(L.ptr(dy), L.ptr(u), L.ptr(gamma), L.ptr(beta), L.ptr(mean), L.ptr(rstd), L.ptr(du), du.stride(0),
+                                L.ptr(dg), L.ptr(db), L.ptr(dc), L.ptr(ws), _row_lim(row_limit, B), B, Lr, C, L.dtype_code(u.dtype),
+                                L.stream_ptr()), "cst_ln_gelu_bwd")
+    return du, dg, db, dc
+
+
 def glu_fwd(z):
     z = _2d(z)
     rows, C2 = z.shape

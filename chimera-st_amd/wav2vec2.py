@@ -28,12 +28,21 @@ class _Slot(nn.Module):
 
 
 class ConvFeatureExtractionModel(nn.Module):
-    """wav2vec2.py:685-763, mode "default": layer 0 = Conv1d(no bias)+GroupNorm(C,C)+GELU, layers 1.. = Conv1d+GELU."""
+    """wav2vec2.py:685-763.  mode "default": layer 0 = Conv1d+GroupNorm(C,C)+GELU, layers 1.. = Conv1d+GELU;
+    mode "layer_norm" (the published large models): every layer = Conv1d+LayerNorm over channels (fp32 statistics)+GELU.
+    conv_bias adds a bias to every conv.  State-dict keys are the reference's: conv_layers.N.0.{weight,bias} for the conv,
+    conv_layers.N.2.{weight,bias} for layer 0's GroupNorm, conv_layers.N.2.1.{weight,bias} for a layer's LayerNorm."""
 
     def __init__(self, conv_layers, dropout=0.0, mode="default", conv_bias=False):
         super().__init__()
-        assert mode == "default", "extractor_mode=layer_norm is not on the Chimera path (wav2vec_small uses default)"
-        assert not conv_bias and dropout == 0.0
+        assert mode in {"default", "layer_norm"}, "extractor_mode must be default or layer_norm, not %r" % (mode,)
+        assert dropout == 0.0
+        if mode == "default" and conv_bias:
+            # layer 0's GroupNorm kernel derives its statistics from lag moments of the audio (csrc/conv0.hip), which a bias would
+            # have to enter as extra terms; no published checkpoint uses this combination (DESIGN §7)
+            raise NotImplementedError("extractor_mode=default with conv_bias=True is not built (no published wav2vec2 model uses it); "
+                                      "extractor_mode=layer_norm takes conv_bias")
+        self.mode, self.conv_bias = mode, bool(conv_bias)
         self.conv_spec = [tuple(c) for c in conv_layers]
         self.conv_layers = nn.ModuleList()
         in_d = 1
@@ -42,8 +51,18 @@ class ConvFeatureExtractionModel(nn.Module):
             conv = nn.Module()
             conv.weight = nn.Parameter(torch.empty(dim, in_d, k))
             nn.init.kaiming_normal_(conv.weight)
+            if conv_bias:  # nn.Conv1d's default bias init: U(-1/sqrt(fan_in), 1/sqrt(fan_in))
+                bound = 1.0 / math.sqrt(in_d * k)
+                conv.bias = nn.Parameter(torch.empty(dim).uniform_(-bound, bound))
             blk.add_module("0", conv)
-            if i == 0:
+            if mode == "layer_norm":  # nn.Sequential(TransposeLast(), Fp32LayerNorm(dim), TransposeLast()) at index 2
+                seq = nn.Module()
+                ln = nn.Module()
+                ln.weight = nn.Parameter(torch.ones(dim))
+                ln.bias = nn.Parameter(torch.zeros(dim))
+                seq.add_module("1", ln)
+                blk.add_module("2", seq)
+            elif i == 0:
                 gn = nn.Module()
                 gn.weight = nn.Parameter(torch.ones(dim))
                 gn.bias = nn.Parameter(torch.zeros(dim))
@@ -66,6 +85,8 @@ class ConvFeatureExtractionModel(nn.Module):
             for i, (_, _, st_) in enumerate(self.conv_spec):
                 nz[i] = lim[i, 0]
                 res[i] = lim[i, 1:1 + st_]
+        if self.mode == "layer_norm":
+            return self._forward_layer_norm(x, lim, nz, res)
         l0 = self.conv_layers[0]
         dim, k, stride = self.conv_spec[0]
         # layer 0 writes only the frames layer 1's live tiles read, its backward reads only the frames that carry gradient
@@ -83,6 +104,35 @@ class ConvFeatureExtractionModel(nn.Module):
             y, z = CF.conv1d_cl(y, w, None, stride, pad=0, act="gelu", prev_z=z, grad_is_dz=(i < n - 1), nz_out=nz[i], nz_in=res[i])
         return y
 
+    def _forward_layer_norm(self, x, lim, nz, res):
+        """Conv (+ bias) -> LayerNorm over channels -> GELU in every layer.  Layer 0 is one fused pass from the samples
+        (cst_conv0_ln_gelu); layers 1.. are the implicit-GEMM conv with the bias in its epilogue followed by cst_ln_gelu.  The trick
+        of the default mode — GELU' of layer i-1 folded into layer i's dX epilogue — does not apply: a LayerNorm sits between them.
+        The frame limits carry over unchanged: no statistic crosses frames, a frame's gradient is zero where its dy is zero."""
+        n = len(self.conv_spec)
+        zero_bias = None
+
+        def params(i):
+            nonlocal zero_bias
+            conv, ln = getattr(self.conv_layers[i], "0"), getattr(getattr(self.conv_layers[i], "2"), "1")
+            bias = getattr(conv, "bias", None)
+            if bias is None:
+                if zero_bias is None or zero_bias.numel() != conv.weight.shape[0]:
+                    zero_bias = torch.zeros(conv.weight.shape[0], dtype=conv.weight.dtype, device=conv.weight.device)
+                bias = zero_bias
+            return conv.weight, bias, ln.weight, ln.bias
+
+        w, b, g, be = params(0)
+        y = CF.conv0_ln_gelu(x, w, b, g, be, self.conv_spec[0][2],
+                             write_limit=lim[0, 1] if lim is not None and n > 1 else None, grad_limit=nz[0])
+        for i in range(1, n):
+            w, b, g, be = params(i)
+            # the conv bias takes its gradient from cst_ln_gelu_bwd (the column sums of du): the GEMM sees a detached copy.
+            # unread_ok: rows of skipped tiles hold the bias instead of a conv output — behind nz[i] nobody reads them (ln_gelu skips them too)
+            u, _ = CF.conv1d_cl(y, w, b.detach(), self.conv_spec[i][2], pad=0, act=None, nz_out=nz[i], nz_in=res[i], unread_ok=True)
+            y = CF.ln_gelu(u, g, be, conv_bias=b if b.requires_grad else None, row_limit=nz[i])
+        return y
+
     def output_length(self, s):
         for (_, k, st) in self.conv_spec:
             s = (s - k) // st + 1
@@ -90,12 +140,11 @@ class ConvFeatureExtractionModel(nn.Module):
 
 
 class TransformerSentenceEncoderLayer(nn.Module):
-    """wav2vec2.py:864-959, post-norm branch (layer_norm_first=False)."""
+    """wav2vec2.py:864-959: the post-norm branch (layer_norm_first=False, :936-957) and the pre-norm one (True, :917-934)."""
 
     def __init__(self, embedding_dim=768, ffn_embedding_dim=3072, num_attention_heads=8, dropout=0.1,
                  attention_dropout=0.1, activation_dropout=0.1, activation_fn="relu", layer_norm_first=False):
         super().__init__()
-        assert not layer_norm_first, "layer_norm_first=True (wav2vec2 large) is not built yet"
         self.embedding_dim = embedding_dim
         self.dropout, self.activation_dropout = dropout, activation_dropout
         self.activation_fn = activation_fn
@@ -109,6 +158,18 @@ class TransformerSentenceEncoderLayer(nn.Module):
     def forward(self, x, self_attn_mask=None, self_attn_padding_mask=None, need_weights=False, att_args=None, seq=None):
         p_drop = float(self.dropout) if self.training else 0.0             # dropout1 / dropout3 (wav2vec2.py:940-955)
         p_act = float(self.activation_dropout) if self.training else 0.0   # dropout2
+        if self.layer_norm_first:
+            # x = x + dropout1(attn(LN(x)));  x = x + dropout3(fc2(dropout2(act(fc1(LN(x))))))  — the residual adds and dropouts ride in
+            # the out_proj / fc2 epilogues as in the post-norm branch; the LayerNorm hands its input back as the residual so both
+            # gradient branches meet inside cst_layernorm_bwd (LayerNorm.forward_residual)
+            h, residual = self.self_attn_layer_norm.forward_residual(x)
+            x, _ = self.self_attn(query=h, key=h, value=h, key_padding_mask=self_attn_padding_mask, need_weights=False,
+                                  resid=residual, out_dropout_p=p_drop, seq=seq)
+            h, residual = self.final_layer_norm.forward_residual(x)
+            x = to_time_major_view(CF.ffn(to_batch_major(h), self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias,
+                                          self.activation_fn, resid=to_batch_major(residual), activation_dropout_p=p_act,
+                                          dropout_p=p_drop))
+            return x, None
         residual = x
         x, _ = self.self_attn(query=x, key=x, value=x, key_padding_mask=self_attn_padding_mask, need_weights=False,
                               resid=residual, out_dropout_p=p_drop, seq=seq)  # x = residual + dropout1(attn) (out_proj epilogue)
@@ -133,7 +194,8 @@ def init_bert_params(module):
 
 
 class TransformerEncoder(nn.Module):
-    """wav2vec2.py:766-861: weight-normed grouped pos_conv + SamePad + GELU, LayerNorm, N post-norm layers, layerdrop."""
+    """wav2vec2.py:766-861: weight-normed grouped pos_conv + SamePad + GELU, LayerNorm, N layers, layerdrop.  Post-norm stacks
+    normalise in front of the layers, pre-norm ones (layer_norm_first, the large models) behind the last layer."""
 
     def __init__(self, args):
         super().__init__()
@@ -229,7 +291,8 @@ class TransformerEncoder(nn.Module):
         x = CF.pos_conv_gelu_residual(x, self.pos_conv_weight(), pc.bias, self.conv_pos_groups, lens, grad_rows, grad_rows_host)  # x += GELU(SamePad(conv(x)))
         if plan is not None:
             x = CF.pack_rows(x, plan)  # [1, rows, C]
-        x = self.layer_norm(x)
+        if not self.layer_norm_first:
+            x = self.layer_norm(x)  # (:827-828; a pre-norm stack normalises behind its last layer instead)
         if self.training and self.dropout > 0:
             x = CF.dropout(x, self.dropout)  # F.dropout(x, p=self.dropout) (:830)
         x = to_time_major_view(x)
@@ -240,6 +303,8 @@ class TransformerEncoder(nn.Module):
             else:
                 notify_unused_parameters(layer.parameters())  # keeps the overlapped bucket order moving (distributed.py)
         x = to_batch_major(x)
+        if self.layer_norm_first:
+            x = self.layer_norm(x)  # (:813-814, applied by forward() behind extract_features: a row-wise op, so before the unpacking)
         if plan is not None:
             # [B, T, C]; frames behind the kept rows repeat the last kept row — unless the consumer declared how far past an utterance's
             # end it reads and the plan keeps exactly those frames (packing_margin): then nobody reads the frames behind them, they come

@@ -30,9 +30,10 @@ extern "C" {
 
 /* Bumps on any change of a signature or a descriptor layout (3: cst_gemm_desc.m_len, cst_attn_desc.seq_offsets, workspaces of the
  * fixed-order reductions; 4: cst_attn_desc.kpm_bits / bwd_ws, the separable attention-dropout mask; 5: cst_gemm_desc.colsum;
- * 6: cst_dec_ln_q_cross_attn; 7: cst_fbank_desc, cst_fbank, cst_fbank_workspace_bytes).
+ * 6: cst_dec_ln_q_cross_attn; 7: cst_fbank_desc, cst_fbank, cst_fbank_workspace_bytes; 8: cst_conv0_ln_gelu_fwd / _bwd,
+ * cst_ln_gelu_fwd / _bwd and their workspaces).
  * cst_version() returns the value the library was built with; chimera-st_amd/lib.py refuses a mismatch. */
-#define CST_ABI_VERSION 7
+#define CST_ABI_VERSION 8
 
 typedef enum { CST_F32 = 0, CST_BF16 = 1 } cst_dtype;
 
@@ -292,6 +293,41 @@ int cst_conv0_gn_gelu_bwd(const void* dy, const float* wav, const void* w, const
                           float* dw, float* dgamma, float* dbeta, float* workspace, const int32_t* frame_limit,
                           int64_t B, int64_t S, int64_t C, int k, int stride, int dtype,
                           cst_stream stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The feature extractor in extractor_mode="layer_norm" (ABI 8; wav2vec2.py:714-724, the published large models): every conv layer
+ * is followed by a LayerNorm over the C channels of a FRAME (fp32 statistics, Fp32LayerNorm) and GELU.  No statistic crosses
+ * frames, so every frame limit below is exact without caveat.  All sums over frames go through per-block partials in the caller's
+ * workspace, added in a fixed order (no atomics: bit-reproducible forward and backward).
+ *
+ * Layer 0: y = GELU(LayerNorm_C(conv1d(wav, w, stride) + bias)), one pass (the pre-norm conv output is never written; the backward
+ * recomputes it from the samples).
+ *   wav [B,S] fp32 (never down-cast);  w [C,k], bias, gamma, beta [C] in `dtype`;  y [B,L,C] channels-last in `dtype`;
+ *   mean, rstd fp32 [B,L] (per frame);  L = (S-k)/stride + 1;  k <= 16;  stride <= 7;  C % 8 == 0, C <= 512 (one wave64 holds a frame).
+ *   frame_limit (optional, int32 [B]): forward — frames t >= frame_limit[b] are neither computed nor written (y, mean, rstd keep
+ *   whatever the buffers held); backward — dy is exactly zero from there on and is not read.  NULL = every frame.
+ *   dw [C,k], dbias, dgamma, dbeta [C] are fp32 and overwritten (there is no input gradient: the input is audio). */
+int cst_conv0_ln_gelu_fwd(const float* wav, const void* w, const void* bias, const void* gamma, const void* beta, void* y,
+                          float* mean, float* rstd, const int32_t* frame_limit, int64_t B, int64_t S, int64_t C, int k,
+                          int stride, float eps, int dtype, cst_stream stream);
+int64_t cst_conv0_ln_bwd_workspace(int64_t B, int64_t S, int64_t C, int k, int stride);
+int cst_conv0_ln_gelu_bwd(const void* dy, const float* wav, const void* w, const void* bias, const void* gamma, const void* beta,
+                          const float* mean, const float* rstd, float* dw, float* dbias, float* dgamma, float* dbeta,
+                          float* workspace, const int32_t* frame_limit, int64_t B, int64_t S, int64_t C, int k, int stride,
+                          int dtype, cst_stream stream);
+/* Layers 1..: y = GELU(LayerNorm_C(u)) over channels-last rows u [B,L,C] (the conv GEMM's output with bias), C % 8 == 0, C <= 2048.
+ *   mean, rstd fp32 [B,L].  row_limit (optional, int32 [B]; cst_conv_row_limits out[i][0], the limits the conv GEMMs take): rows
+ *   t >= row_limit[b] are read by nobody — they are not read or computed, and y (forward) / du (backward, where dy is exactly zero)
+ *   are written as zeros there, so that tiles of the neighbouring GEMMs that straddle a limit meet numbers.
+ *   Backward: du in `dtype` with `du_batch_stride` elements between utterances (>= L*C: the windowed dX GEMMs of the conv in front
+ *   want a spare row before and after every utterance); dgamma, dbeta fp32 [C]; dcolsum (optional) fp32 [C] = column sums of du,
+ *   i.e. the gradient of the conv bias in front.  workspace: cst_ln_gelu_bwd_workspace(B*L, C) bytes. */
+int cst_ln_gelu_fwd(const void* u, const void* gamma, const void* beta, void* y, float* mean, float* rstd,
+                    const int32_t* row_limit, int64_t B, int64_t L, int64_t C, float eps, int dtype, cst_stream stream);
+int64_t cst_ln_gelu_bwd_workspace(int64_t rows, int64_t C);
+int cst_ln_gelu_bwd(const void* dy, const void* u, const void* gamma, const void* beta, const float* mean, const float* rstd,
+                    void* du, int64_t du_batch_stride, float* dgamma, float* dbeta, float* dcolsum, float* workspace,
+                    const int32_t* row_limit, int64_t B, int64_t L, int64_t C, int dtype, cst_stream stream);
 
 /* ------------------------------------------------------------------------------------------
  * Elementwise / reduction helpers (HBM-bound)
