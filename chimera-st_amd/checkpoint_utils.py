@@ -124,6 +124,7 @@ def load_model_ensemble_and_task(filenames, arg_overrides=None, task=None, stric
     """checkpoint_utils.py:269-309: [(model built from the checkpoint's args, state loaded)], args, task."""
     from . import criterions, s2t_transformer, tasks, w2v2_transformer, w2v2_transformer_interlingua, wav2vec2  # noqa: F401 (registries)
     ensemble, args = [], None
+    filenames = list(filenames)
     for filename in filenames:
         state = load_checkpoint_to_cpu(filename, arg_overrides)
         args = state.get("args")
@@ -138,6 +139,8 @@ def load_model_ensemble_and_task(filenames, arg_overrides=None, task=None, stric
             args.data, args.synthetic_vocab_size = None, int(state["model"]["decoder.embed_tokens.weight"].shape[0])
         if task is None:
             task = registry.setup_task(args)
+        elif ensemble:  # a further ensemble member: its distribution is averaged with the first's token by token
+            _require_same_dictionary(task.target_dictionary, registry.setup_task(args).target_dictionary, state["model"], filenames[0], filename)
         registry.ARCH_CONFIG_REGISTRY[args.arch](args)
         model = task.build_model(args)
         sd = state["model"]
@@ -145,6 +148,18 @@ def load_model_ensemble_and_task(filenames, arg_overrides=None, task=None, stric
         model.load_state_dict(sd, strict=strict)
         ensemble.append(model)
     return ensemble, args, task
+
+
+def _require_same_dictionary(first, other, model_state, first_file, other_file):
+    """Ensemble members must share the target dictionary: same length, same symbols, and the member's output vocabulary is it."""
+    rows = model_state["decoder.embed_tokens.weight"].shape[0] if "decoder.embed_tokens.weight" in model_state else len(other)
+    if len(first) != len(other) or rows != len(first):
+        raise ValueError("ensemble members must share the target dictionary: %s has %d symbols, %s has %d"
+                         % (first_file, len(first), other_file, rows if rows != len(first) else len(other)))
+    for i, (a, b) in enumerate(zip(first.symbols, other.symbols)):
+        if a != b:
+            raise ValueError("ensemble members must share the target dictionary: symbol %d is %r in %s and %r in %s"
+                             % (i, a, first_file, b, other_file))
 
 
 def save_state(filename, args, model_state_dict, criterion, optimizer, num_updates, optim_history=None, extra_state=None):

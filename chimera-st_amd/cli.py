@@ -219,7 +219,8 @@ def generate_main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     p = argparse.ArgumentParser(allow_abbrev=False)
     p.add_argument("data")
-    p.add_argument("--path", required=True, help="checkpoint(s), colon separated (the first is decoded: single-model search)")
+    p.add_argument("--path", required=True, help="checkpoint(s), colon separated: several files are decoded as an ensemble "
+                   "(the members' next-token distributions are averaged at every step)")
     p.add_argument("--task", default="triplet")
     p.add_argument("--config-yaml", default="config.yaml")
     p.add_argument("--gen-subset", default="test")
@@ -246,13 +247,13 @@ def generate_main(argv=None):
     limit_host_threads()
     overrides = {"data": args.data, "config_yaml": args.config_yaml, "max_source_positions": args.max_source_positions,
                  "max_target_positions": args.max_target_positions}
-    models, margs, task = checkpoint_utils.load_model_ensemble_and_task(args.path.split(":")[:1], arg_overrides=overrides)
+    models, margs, task = checkpoint_utils.load_model_ensemble_and_task(args.path.split(":"), arg_overrides=overrides)
     dtype = torch.bfloat16 if (args.fp16 or args.bf16) else torch.float32
-    model = models[0].to("cuda", dtype).eval()
+    models = [m.to("cuda", dtype).eval() for m in models]
     ds = task.load_dataset(args.gen_subset)
     itr = task.get_batch_iterator(ds, max_tokens=args.max_tokens, max_sentences=args.batch_size,
                                   max_positions=(args.max_source_positions, args.max_target_positions), ignore_invalid_inputs=True)
-    gen = task.build_generator([model], args)
+    gen = task.build_generator(models, args)
     tgt_dict = task.target_dictionary
     if args.results_path:
         os.makedirs(args.results_path, exist_ok=True)
@@ -278,7 +279,7 @@ def generate_main(argv=None):
         # inputs [B, T, F] take the model's storage dtype
         src = src.to("cuda", dtype) if (src.dim() == 3 and src.is_floating_point()) else src.cuda()
         s = {"net_input": {"src_tokens": src, "src_lengths": ni["src_lengths"].cuda()}}
-        results = task.inference_step(gen, [model], s)
+        results = task.inference_step(gen, models, s)
         for i, sid in enumerate(sample["id"].tolist()):
             ref = tgt_dict.string(sample["target"][i]) if sample.get("target") is not None else None
             h = results[i][0]
@@ -296,7 +297,7 @@ def generate_main(argv=None):
     torch.cuda.synchronize()
     dt = time.time() - t0
     summary = {"event": "generate", "subset": args.gen_subset, "sentences": nsent, "tokens": ntok, "seconds": dt,
-               "sentences_per_s": nsent / max(dt, 1e-9), "tokens_per_s": ntok / max(dt, 1e-9), "beam": args.beam,
+               "sentences_per_s": nsent / max(dt, 1e-9), "tokens_per_s": ntok / max(dt, 1e-9), "beam": args.beam, "models": len(models),
                "bleu4_whitespace": corpus_bleu(hyps, refs) if any(refs) else None, "ignored_flags": ignored}
     print(json.dumps(summary), file=out, flush=True)
     if out is not sys.stdout:

@@ -54,6 +54,13 @@ __global__ void beam_init_kernel(BeamP p, int32_t* ticket) {
   }
 }
 
+// 16-byte vector of T -> floats
+template <typename T>
+__device__ __forceinline__ void ld_vec(const T* p, float (&v)[DT<T>::VEC]) {
+  if constexpr (DT<T>::VEC == 8) { float v8[8]; load8(p, v8); for (int e = 0; e < 8; ++e) v[e] = v8[e]; }
+  else { const f32x4 a = *reinterpret_cast<const f32x4*>(p); for (int e = 0; e < 4; ++e) v[e] = a[e]; }
+}
+
 __device__ __forceinline__ bool cand_better(float x, int i, float y, int j) { return x > y || (x == y && i < j); }
 constexpr int BEAM_MAX = 20, KMAX_ALL = 2 * BEAM_MAX;
 
@@ -64,8 +71,30 @@ constexpr int BEAM_MAX = 20, KMAX_ALL = 2 * BEAM_MAX;
 // The row's logits stay in registers (NV 16-byte vectors per thread) between the statistics pass and the selection; the
 // selection is 2*beam block-wide arg-max rounds in which only the winning thread rescans its registers (an earlier version kept
 // a sorted top-K list per thread for a whole sentence per workgroup: the divergent insertion chains made it 105 us per step).
-template <typename T, int NV>
-__global__ __launch_bounds__(512) void beam_row_topk_kernel(BeamP p, float* cand_val, int32_t* cand_tok) {
+//
+// ENS (checkpoint ensembles, sequence_generator.py EnsembleModel.forward_decoder :806-868): (a) becomes, over the e.n members' rows,
+//   lse_n = logsumexp_v(l_n[v] / T),   lp[v] = log(sum_n exp(l_n[v] / T - lse_n)) - log N          (all fp32, never stored in bf16)
+// in two sweeps over the members: the first gathers every member's (max, sum) — wave shuffles, ONE barrier for all members — the
+// second re-reads the rows (L2 hits) and folds a_n = l_n / T - lse_n into a per-element running (max, sum) over the members, so the
+// exp never sees more than a_n - max_n a_n <= 0 and an element that is -inf in every member stays -inf.  A member whose row has no
+// finite lse (NaN logits, an all -inf row) makes the whole row NaN like the reference's stack + logsumexp; (b) and (c) are shared.
+constexpr int ENS_MAX = 8;
+struct EnsP {
+  int n;
+  float temperature, log_n;
+  const void* logits[ENS_MAX];
+  float* lprobs_out;  // optional [rows][ld_logits] fp32: lp before the masks of (b)
+};
+
+// (max, sum exp(x - max)) of two partial softmax statistics
+__device__ __forceinline__ void lse_merge(float& mx, float& sum, float m2, float s2) {
+  const float M = fmaxf(mx, m2);
+  sum = (mx == -INFINITY ? 0.0f : sum * expf(mx - M)) + (m2 == -INFINITY ? 0.0f : s2 * expf(m2 - M));
+  mx = M;
+}
+
+template <typename T, int NV, bool ENS>
+__device__ __forceinline__ void beam_row_topk_body(const BeamP& p, const EnsP* ep, float* cand_val, int32_t* cand_tok) {
   constexpr int VEC = DT<T>::VEC, NTH = 512, NW = NTH / 64;
   const int s = *p.step;
   if (s > p.max_len) return;
@@ -83,6 +112,75 @@ __global__ __launch_bounds__(512) void beam_row_topk_kernel(BeamP p, float* cand
   static_assert(KMAX_ALL <= 64 && NW <= 64, "the merge keeps one output candidate / one list head per lane of wave 0");
 
   float x[NV][VEC];
+  float lse;
+  if constexpr (ENS) {
+    const EnsP& e = *ep;
+    __shared__ float ens_m[ENS_MAX][NW], ens_s[ENS_MAX][NW], ens_lse[ENS_MAX];
+    float t[NV][VEC];
+    auto load_member = [&](int n) {  // member n's row / T; -inf behind the vocabulary
+      const T* ln = reinterpret_cast<const T*>(e.logits[n]) + (int64_t)h * p.ld_logits;
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        const int vi = tid + i * NTH;
+        if (vi < nvec) ld_vec<T>(ln + (int64_t)vi * VEC, t[i]);
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) t[i][k] = (vi < nvec && vi * VEC + k < V) ? t[i][k] / e.temperature : NEG;
+      }
+    };
+    for (int n = 0; n < e.n; ++n) {
+      load_member(n);
+      float mx = NEG, sum = 0.0f;
+      bool nan = false;
+#pragma unroll
+      for (int i = 0; i < NV; ++i)
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) { nan = nan || t[i][k] != t[i][k]; mx = fmaxf(mx, t[i][k]); }
+      if (mx != NEG) {
+#pragma unroll
+        for (int i = 0; i < NV; ++i)
+#pragma unroll
+          for (int k = 0; k < VEC; ++k) sum += expf(t[i][k] - mx);
+      }
+      if (nan) sum = NAN;
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) lse_merge(mx, sum, __shfl_xor(mx, o, 64), __shfl_xor(sum, o, 64));
+      if (lane == 0) { ens_m[n][wave] = mx; ens_s[n][wave] = sum; }
+    }
+    __syncthreads();
+    if (tid < e.n) {
+      float mm = NEG, ss = 0.0f;
+      for (int w = 0; w < NW; ++w) lse_merge(mm, ss, ens_m[tid][w], ens_s[tid][w]);
+      ens_lse[tid] = mm + logf(ss);
+    }
+    __syncthreads();
+    bool bad = false;
+    for (int n = 0; n < e.n; ++n) bad = bad || !(ens_lse[n] - ens_lse[n] == 0.0f);  // NaN or +-inf: the member's log-softmax is NaN
+    float acc[NV][VEC];
+#pragma unroll
+    for (int i = 0; i < NV; ++i)
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) { x[i][k] = NEG; acc[i][k] = 0.0f; }
+    for (int n = 0; n < e.n; ++n) {
+      load_member(n);
+      const float ln = ens_lse[n];
+#pragma unroll
+      for (int i = 0; i < NV; ++i)
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) lse_merge(x[i][k], acc[i][k], t[i][k] - ln, 1.0f);
+    }
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) x[i][k] = bad ? NAN : (x[i][k] == NEG ? NEG : x[i][k] + (logf(acc[i][k]) - e.log_n));  // (the small term first: one rounding at the magnitude of lp)
+      const int vi = tid + i * NTH;
+      if (e.lprobs_out && vi < nvec) {
+        float* o = e.lprobs_out + (int64_t)h * p.ld_logits + (int64_t)vi * VEC;
+#pragma unroll
+        for (int k = 0; k < VEC; k += 4) { f32x4 o4 = {x[i][k], x[i][k + 1], x[i][k + 2], x[i][k + 3]}; *reinterpret_cast<f32x4*>(o + k) = o4; }
+      }
+    }
+    lse = 0.0f;  // x holds log-probabilities already
+  } else {
   float mx = NEG;
   bool nan = false;
 #pragma unroll
@@ -127,7 +225,8 @@ __global__ __launch_bounds__(512) void beam_row_topk_kernel(BeamP p, float* cand
     sh_lse = mm + logf(ss);
   }
   __syncthreads();
-  const float lse = sh_lse;
+  lse = sh_lse;
+  }
   const float prev = s > 0 ? (p.scores + (int64_t)(s & 1) * p.bsz * p.beam * L1)[(int64_t)h * L1 + s - 1] : 0.0f;
   // candidate values replace the logits in the registers
 #pragma unroll
@@ -245,9 +344,19 @@ __global__ __launch_bounds__(512) void beam_row_topk_kernel(BeamP p, float* cand
   }
 }
 
+template <typename T, int NV>
+__global__ __launch_bounds__(512) void beam_row_topk_kernel(BeamP p, float* cand_val, int32_t* cand_tok) {
+  beam_row_topk_body<T, NV, false>(p, nullptr, cand_val, cand_tok);
+}
+template <typename T, int NV>
+__global__ __launch_bounds__(512) void beam_row_topk_ens_kernel(BeamP p, EnsP e, float* cand_val, int32_t* cand_tok) {
+  beam_row_topk_body<T, NV, true>(p, &e, cand_val, cand_tok);
+}
+
 // generic-width variant: rows too long for registers are re-read from memory (L2-resident) on every scan
-template <typename T>
-__global__ __launch_bounds__(512) void beam_row_topk_wide_kernel(BeamP p, float* cand_val, int32_t* cand_tok) {
+// (ENS: the members' statistics as in the register kernel; every scan recombines the N rows element by element)
+template <typename T, bool ENS>
+__device__ __forceinline__ void beam_row_topk_wide_body(const BeamP& p, const EnsP* ep, float* cand_val, int32_t* cand_tok) {
   constexpr int NTH = 512, NW = NTH / 64;
   const int s = *p.step;
   if (s > p.max_len) return;
@@ -262,6 +371,33 @@ __global__ __launch_bounds__(512) void beam_row_topk_wide_kernel(BeamP p, float*
   __shared__ float sh_lse;
   __shared__ float o_val[KMAX_ALL];
   __shared__ int o_tok[KMAX_ALL];
+  __shared__ float ens_m[ENS ? ENS_MAX : 1][NW], ens_s[ENS ? ENS_MAX : 1][NW], ens_lse[ENS ? ENS_MAX : 1];
+  float lse = 0.0f;
+  bool bad = false;
+  if constexpr (ENS) {
+    for (int n = 0; n < ep->n; ++n) {
+      const T* ln = reinterpret_cast<const T*>(ep->logits[n]) + (int64_t)h * p.ld_logits;
+      float mx = NEG, sum = 0.0f;
+      bool nan = false;
+      for (int v = tid; v < V; v += NTH) {
+        const float xv = DT<T>::ld(ln + v) / ep->temperature;
+        nan = nan || xv != xv;
+        lse_merge(mx, sum, xv, 1.0f);
+      }
+      if (nan) sum = NAN;
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) lse_merge(mx, sum, __shfl_xor(mx, o, 64), __shfl_xor(sum, o, 64));
+      if (lane == 0) { ens_m[n][wave] = mx; ens_s[n][wave] = sum; }
+    }
+    __syncthreads();
+    if (tid < ep->n) {
+      float mm = NEG, ss = 0.0f;
+      for (int w = 0; w < NW; ++w) lse_merge(mm, ss, ens_m[tid][w], ens_s[tid][w]);
+      ens_lse[tid] = mm + logf(ss);
+    }
+    __syncthreads();
+    for (int n = 0; n < ep->n; ++n) bad = bad || !(ens_lse[n] - ens_lse[n] == 0.0f);
+  } else {
   float mx = NEG, sum = 0.0f;
   for (int v = tid; v < V; v += NTH) {
     const float xv = DT<T>::ld(lg + v) * p.inv_temperature;
@@ -288,14 +424,30 @@ __global__ __launch_bounds__(512) void beam_row_topk_wide_kernel(BeamP p, float*
     sh_lse = mm + logf(ss);
   }
   __syncthreads();
-  const float lse = sh_lse;
+  lse = sh_lse;
+  }
+  // log-probability of token v before the masks
+  auto lprob = [&](int v) -> float {
+    if constexpr (ENS) {
+      float m = NEG, a = 0.0f;
+      for (int n = 0; n < ep->n; ++n)
+        lse_merge(m, a, DT<T>::ld(reinterpret_cast<const T*>(ep->logits[n]) + (int64_t)h * p.ld_logits + v) / ep->temperature - ens_lse[n], 1.0f);
+      return bad ? NAN : (m == NEG ? NEG : m + (logf(a) - ep->log_n));
+    } else {
+      return DT<T>::ld(lg + v) * p.inv_temperature - lse;
+    }
+  };
+  if constexpr (ENS) {
+    if (ep->lprobs_out)
+      for (int v = tid; v < V; v += NTH) ep->lprobs_out[(int64_t)h * p.ld_logits + v] = lprob(v);
+  }
   const float prev = s > 0 ? (p.scores + (int64_t)(s & 1) * p.bsz * p.beam * L1)[(int64_t)h * L1 + s - 1] : 0.0f;
   float tv = INFINITY, bv;
   int ti = -1, bi;
   auto rescan = [&]() {
     bv = NEG; bi = INT_MAX;
     for (int v = tid; v < V; v += NTH) {
-      float val = DT<T>::ld(lg + v) * p.inv_temperature - lse;
+      float val = lprob(v);
       if (val != val) val = NEG;
       if (v == p.pad) val = NEG;
       if (v == p.unk) val -= p.unk_penalty;
@@ -329,6 +481,15 @@ __global__ __launch_bounds__(512) void beam_row_topk_wide_kernel(BeamP p, float*
     cand_val[(int64_t)h * K + tid] = o_val[tid];
     cand_tok[(int64_t)h * K + tid] = o_tok[tid];
   }
+}
+
+template <typename T>
+__global__ __launch_bounds__(512) void beam_row_topk_wide_kernel(BeamP p, float* cand_val, int32_t* cand_tok) {
+  beam_row_topk_wide_body<T, false>(p, nullptr, cand_val, cand_tok);
+}
+template <typename T>
+__global__ __launch_bounds__(512) void beam_row_topk_wide_ens_kernel(BeamP p, EnsP e, float* cand_val, int32_t* cand_tok) {
+  beam_row_topk_wide_body<T, true>(p, &e, cand_val, cand_tok);
 }
 
 // ---- beam search step, kernel 2 of 2: one workgroup per SENTENCE -------------------------------------------------------------
@@ -478,12 +639,6 @@ __global__ void dec_embed_kernel(const int64_t* tokens, const int32_t* stepp, co
   }
 }
 
-// 16-byte vector of T -> floats
-template <typename T>
-__device__ __forceinline__ void ld_vec(const T* p, float (&v)[DT<T>::VEC]) {
-  if constexpr (DT<T>::VEC == 8) { float v8[8]; load8(p, v8); for (int e = 0; e < 8; ++e) v[e] = v8[e]; }
-  else { const f32x4 a = *reinterpret_cast<const f32x4*>(p); for (int e = 0; e < 4; ++e) v[e] = a[e]; }
-}
 // packed 16-byte vector -> floats (keeps in-flight loads at 4 VGPRs each instead of 8 for bf16)
 template <typename T>
 __device__ __forceinline__ void cvt_vec(const u32x4& r, float (&v)[DT<T>::VEC]) {
@@ -1006,18 +1161,39 @@ int cst_beam_step(const cst_beam_desc* d, cst_stream stream) {
   CST_REQUIRE(d->ld_logits % vec == 0 && d->ld_logits >= cst_ceil_div(d->vocab, vec) * vec && ((uintptr_t)d->logits % 16) == 0,
               "cst_beam_step: logits rows must be 16-byte aligned and padded to a multiple of %lld elements", (long long)vec);
   CST_REQUIRE(d->workspace != nullptr && ((uintptr_t)d->workspace % 16) == 0, "cst_beam_step: workspace of cst_beam_workspace() bytes required");
+  // checkpoint ensembles: members >= 2 (0 and 1 both mean the single matrix `logits`, today's kernels with today's arguments)
+  CST_REQUIRE(d->members >= 0 && d->members <= ENS_MAX, "cst_beam_step: %lld ensemble members (at most %d)", (long long)d->members, ENS_MAX);
+  EnsP e;
+  e.n = (int)d->members;
+  e.temperature = d->temperature;
+  e.log_n = logf((float)(d->members > 0 ? d->members : 1));
+  e.lprobs_out = d->lprobs_out;
+  const bool ens = d->members >= 2;
+  CST_REQUIRE(ens || d->lprobs_out == nullptr, "cst_beam_step: lprobs_out is written by the ensemble kernel (members >= 2)");
+  CST_REQUIRE(d->lprobs_out == nullptr || ((uintptr_t)d->lprobs_out % 16) == 0, "cst_beam_step: lprobs_out must be 16-byte aligned");
+  for (int n = 0; n < ENS_MAX; ++n) {
+    e.logits[n] = n == 0 ? d->logits : (n < e.n ? d->logits_n[n - 1] : nullptr);
+    CST_REQUIRE(n >= e.n || (e.logits[n] != nullptr && ((uintptr_t)e.logits[n] % 16) == 0),
+                "cst_beam_step: logits of ensemble member %d null or not 16-byte aligned", n);
+  }
   hipStream_t s = (hipStream_t)stream;
   const int64_t rows = (int64_t)p.bsz * p.beam, K = 2 * p.beam;
   int32_t* ticket = reinterpret_cast<int32_t*>(d->workspace);
   float* cand_val = reinterpret_cast<float*>(reinterpret_cast<char*>(d->workspace) + 64);
   int32_t* cand_tok = reinterpret_cast<int32_t*>(cand_val + rows * K);
   {
-    CstProfScope prof(CST_K_ELEMENTWISE, s, 0.0, (double)rows * p.vocab * cst_dtype_size(d->dtype));
+    CstProfScope prof(CST_K_ELEMENTWISE, s, 0.0, (double)rows * p.vocab * cst_dtype_size(d->dtype) * (ens ? 2 * e.n : 1));
     const int64_t nvec = cst_ceil_div(d->vocab, vec), per_thread = cst_ceil_div(nvec, 512);
 #define CST_TOPK(T, NV) hipLaunchKernelGGL((beam_row_topk_kernel<T, NV>), dim3((unsigned)rows), dim3(512), 0, s, p, cand_val, cand_tok)
 #define CST_TOPK_T(T) do { if (per_thread <= 1) CST_TOPK(T, 1); else if (per_thread <= 3) CST_TOPK(T, 3); else if (per_thread <= 5) CST_TOPK(T, 5); \
                             else hipLaunchKernelGGL((beam_row_topk_wide_kernel<T>), dim3((unsigned)rows), dim3(512), 0, s, p, cand_val, cand_tok); } while (0)
-    if (d->dtype == CST_BF16) CST_TOPK_T(bf16_t); else CST_TOPK_T(float);
+#define CST_TOPK_E(T, NV) hipLaunchKernelGGL((beam_row_topk_ens_kernel<T, NV>), dim3((unsigned)rows), dim3(512), 0, s, p, e, cand_val, cand_tok)
+#define CST_TOPK_ET(T) do { if (per_thread <= 1) CST_TOPK_E(T, 1); else if (per_thread <= 3) CST_TOPK_E(T, 3); else if (per_thread <= 5) CST_TOPK_E(T, 5); \
+                            else hipLaunchKernelGGL((beam_row_topk_wide_ens_kernel<T>), dim3((unsigned)rows), dim3(512), 0, s, p, e, cand_val, cand_tok); } while (0)
+    if (ens) { if (d->dtype == CST_BF16) CST_TOPK_ET(bf16_t); else CST_TOPK_ET(float); }
+    else if (d->dtype == CST_BF16) CST_TOPK_T(bf16_t); else CST_TOPK_T(float);
+#undef CST_TOPK_ET
+#undef CST_TOPK_E
 #undef CST_TOPK_T
 #undef CST_TOPK
     hipLaunchKernelGGL(beam_merge_kernel, dim3(p.bsz), dim3(256), 0, s, p, (const float*)cand_val, (const int32_t*)cand_tok, ticket);

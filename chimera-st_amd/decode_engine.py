@@ -30,7 +30,12 @@ from .optim import PARAM_EPOCH
 class BeamDecodeEngine:
     def __init__(self, decoder, tgt_dict, beam_size, max_len, min_len=1, normalize_scores=True, len_penalty=1.0,
                  unk_penalty=0.0, temperature=1.0, use_graph=True, poll=8, cross_kernel=None, lanes=None):
-        self.dec = decoder
+        # a checkpoint ensemble (--path a.pt:b.pt:c.pt) is a LIST of decoders: every member keeps its own packed weights, K/V caches,
+        # encoder K/V and logits buffer; the beam state (tokens / scores / ancestry, step counter, finalized hypotheses) is shared —
+        # all members follow the same hypotheses, so one ancestry table serves every member's append-only caches
+        self.decs = list(decoder) if isinstance(decoder, (list, tuple)) else [decoder]
+        assert 1 <= len(self.decs) <= 8, "cst_beam_step combines at most 8 ensemble members"
+        self.dec = self.decs[0]
         self.pad, self.unk, self.eos = tgt_dict.pad(), tgt_dict.unk(), tgt_dict.eos()
         self.vocab = len(tgt_dict)
         self.beam, self.max_len, self.min_len = int(beam_size), int(max_len), int(min_len)
@@ -79,16 +84,29 @@ class BeamDecodeEngine:
         self._state.clear()
 
     def _pack(self, dtype, device):
-        """Per-layer packed [3C, C] self-attention projection (weights are constants in eval mode)."""
+        """Per member and layer the packed [3C, C] self-attention projection (weights are constants in eval mode).  Returns member
+        0's dict; the other members' dicts are its "others" entry (no reference back to itself: a cycle would leave dropped weight
+        copies and graphs to the cyclic collector, which may then run inside a later graph capture)."""
         # weights may have been updated since the last call (training between validations): re-pack and drop the graphs
         # (autograd versions catch load_state_dict / copy_; optim.PARAM_EPOCH catches the fused optimizer's raw-pointer updates)
-        key = (dtype, device, PARAM_EPOCH[0], tuple((p.data_ptr(), p._version) for p in self.dec.parameters()))
+        key = (dtype, device, PARAM_EPOCH[0], tuple((p.data_ptr(), p._version) for dec in self.decs for p in dec.parameters()))
         if self._packed is not None and self._packed[0] == key:
             return self._packed[1]
         self._state.clear()
+        members = [self._pack_member(dec, dtype, device) for dec in self.decs]
+        members[0]["others"] = members[1:]
+        self._packed = (key, members[0])
+        return self._packed[1]
+
+    @staticmethod
+    def members(d):
+        """[member 0's dict, member 1's, ...] of a state or packed-weights dict."""
+        return [d] + d.get("others", [])
+
+    def _pack_member(self, dec, dtype, device):
         layers = []
-        fuse = self._fuse_ln(dtype)
-        for l in self.dec.layers:
+        fuse = self._fuse_ln(dtype, dec)
+        for l in dec.layers:
             sa = l.self_attn
             d = dict(
                 wqkv=torch.cat((sa.q_proj.weight, sa.k_proj.weight, sa.v_proj.weight), 0).detach().contiguous(),
@@ -99,31 +117,34 @@ class BeamDecodeEngine:
                 d["ln_q_frag"] = self.fragment_major(d["ln_q"][0], l.encoder_attn.num_heads)  # cst_dec_ln_q_cross_attn's weight layout
                 d["ln_fc1"] = self._fold_ln(l.final_layer_norm, l.fc1.weight, l.fc1.bias)
             layers.append(d)
-        pos = self.dec.embed_positions
-        need = self.dec.padding_idx + 2 + self.max_len + 1
+        pos = dec.embed_positions
+        need = dec.padding_idx + 2 + self.max_len + 1
         table = pos.get_embedding(need, pos.embedding_dim, pos.padding_idx).to(device=device, dtype=torch.float32).contiguous()
         # the module path adds positions converted to the storage dtype (models/transformer.py:756 on a .half()/bf16 model)
         if dtype != torch.float32:
             table = table.to(dtype).float()
-        self._packed = (key, dict(layers=layers, pos=table))
-        return self._packed[1]
+        return dict(layers=layers, pos=table)
 
     def nodes_per_step(self, dtype, rows=None):
         """Kernel launches (graph nodes) of one decode step: embed + per layer (LayerNorm, qkv, self-attention, out, LayerNorm, q,
         cross-attention, out, LayerNorm, fc1, fc2 — the three LayerNorms folded into their projections on the bf16 path) + final
         LayerNorm + vocabulary projection + the two beam-search kernels; + the split-K reduce of fc2 where it is split (bf16, <= 256
-        hypothesis rows, ffn >= 4096)."""
-        per_layer = 8 if self._fuse_ln(dtype) else 11
-        D = self.dec.layers[0].self_attn.head_dim
-        if self._fuse_ln(dtype) and self._fuse_q_cross(dtype, D, self.dec.embed_dim, self._cross_mode(dtype, D)):
+        hypothesis rows, ffn >= 4096).  An ensemble runs every member's sequence up to its vocabulary projection, then ONE pair of
+        beam-search kernels over the members' logits."""
+        return sum(self._member_nodes(dec, dtype, rows) for dec in self.decs) + 2
+
+    def _member_nodes(self, dec, dtype, rows):
+        per_layer = 8 if self._fuse_ln(dtype, dec) else 11
+        D = dec.layers[0].self_attn.head_dim
+        if self._fuse_ln(dtype, dec) and self._fuse_q_cross(dtype, D, dec.embed_dim, self._cross_mode(dtype, D)):
             per_layer -= 1  # the query projection runs inside the cross-attention launch
-        F = self.dec.layers[0].fc1.out_features
+        F = dec.layers[0].fc1.out_features
         if rows is not None and rows <= 256 and F >= 4096 and dtype == torch.bfloat16 and not os.environ.get("CST_DEC_NO_SPLITK"):
             per_layer += 1
-        return 1 + per_layer * len(self.dec.layers) + (1 if self.dec.layer_norm is not None else 0) + 1 + 2
+        return 1 + per_layer * len(dec.layers) + (1 if dec.layer_norm is not None else 0) + 1
 
-    def _fuse_ln(self, dtype):
-        C = self.dec.embed_dim
+    def _fuse_ln(self, dtype, dec=None):
+        C = (self.dec if dec is None else dec).embed_dim
         return dtype == torch.bfloat16 and C % 512 == 0 and not os.environ.get("CST_DEC_NO_LINEAR") and not os.environ.get("CST_DEC_NO_LN_FUSE")
 
     @staticmethod
@@ -153,28 +174,45 @@ class BeamDecodeEngine:
                 "cst_dec_ln_linear")
 
     # ------------------------------------------------------------------------------------------------------------
+    def _alloc_member(self, dec, bsz, S, dtype, device, has_mask):
+        """One member's own buffers: activations, logits, append-only self-attention caches, per-sentence encoder K/V."""
+        beam, L1 = self.beam, self.max_len + 1
+        bbsz, C, nl = bsz * beam, dec.embed_dim, len(dec.layers)
+        F = dec.layers[0].fc1.out_features
+        z = lambda *shape, dt=dtype: torch.zeros(*shape, dtype=dt, device=device)
+        return dict(
+            x=z(bbsz, C), x2=z(bbsz, C), h=z(bbsz, C), qkv=z(bbsz, 3 * C), q=z(bbsz, C), attn=z(bbsz, C), f=z(bbsz, F),
+            logits=z(bbsz, (self.vocab + 7) // 8 * 8),
+            mean=z(bbsz, dt=torch.float32), rstd=z(bbsz, dt=torch.float32), lse=z(bsz * 64 * beam, dt=torch.float32),
+            kc=[z(bbsz, L1, C) for _ in range(nl)], vc=[z(bbsz, L1, C) for _ in range(nl)],
+            kx=[z(bsz, S, C) for _ in range(nl)], vx=[z(bsz, S, C) for _ in range(nl)],
+            proj=z(bsz * S, C), kpm=z(bsz, S, dt=torch.uint8) if has_mask else None,
+            gemm_ws=z(8 * bbsz * C * 4 if bbsz <= 256 else 0, dt=torch.uint8))  # split-K partials of the fc2 projection (own buffer: captured)
+
     def _alloc(self, lane, bsz, S, dtype, device, has_mask):
+        """S / has_mask: one value per member (members may differ in encoder output length)."""
+        S = tuple(S) if isinstance(S, (list, tuple)) else (S,) * len(self.decs)
+        has_mask = tuple(has_mask) if isinstance(has_mask, (list, tuple)) else (has_mask,) * len(self.decs)
         key = (lane, bsz, S, dtype, device, has_mask)
         st = self._state.get(key)
         if st is not None:
             return st
         beam, L1, LT = self.beam, self.max_len + 1, self.max_len + 2
-        bbsz, C, nl = bsz * beam, self.dec.embed_dim, len(self.dec.layers)
-        F = self.dec.layers[0].fc1.out_features
+        bbsz = bsz * beam
         z = lambda *shape, dt=dtype: torch.zeros(*shape, dtype=dt, device=device)
         st = dict(
             step=z(1, dt=torch.int32), num_remaining=z(1, dt=torch.int32),
             tokens=z(2, bbsz, LT, dt=torch.int64), scores=z(2, bbsz, L1, dt=torch.float32), anc=z(2, bbsz, L1, dt=torch.int32),
             ignore=z(bsz, beam, dt=torch.uint8), finished=z(bsz, dt=torch.uint8), nfinal=z(bsz, dt=torch.int32),
             fin_tokens=z(bsz, beam, L1, dt=torch.int64), fin_pos=z(bsz, beam, L1, dt=torch.float32),
-            fin_score=z(bsz, beam, dt=torch.float32), fin_len=z(bsz, beam, dt=torch.int32),
-            x=z(bbsz, C), x2=z(bbsz, C), h=z(bbsz, C), qkv=z(bbsz, 3 * C), q=z(bbsz, C), attn=z(bbsz, C), f=z(bbsz, F),
-            logits=z(bbsz, (self.vocab + 7) // 8 * 8),
-            mean=z(bbsz, dt=torch.float32), rstd=z(bbsz, dt=torch.float32), lse=z(bsz * 64 * beam, dt=torch.float32),
-            kc=[z(bbsz, L1, C) for _ in range(nl)], vc=[z(bbsz, L1, C) for _ in range(nl)],
-            kx=[z(bsz, S, C) for _ in range(nl)], vx=[z(bsz, S, C) for _ in range(nl)],
-            proj=z(bsz * S, C), kpm=z(bsz, S, dt=torch.uint8) if has_mask else None, graph=None,
-            gemm_ws=z(8 * bbsz * C * 4 if bbsz <= 256 else 0, dt=torch.uint8))  # split-K partials of the fc2 projection (own buffer: captured)
+            fin_score=z(bsz, beam, dt=torch.float32), fin_len=z(bsz, beam, dt=torch.int32), graph=None)
+        # st itself carries member 0's buffers (the single-model layout); the other members' dicts share the beam state
+        st.update(self._alloc_member(self.decs[0], bsz, S[0], dtype, device, has_mask[0]))
+        st["others"] = []
+        for i, dec in enumerate(self.decs[1:], 1):
+            m = self._alloc_member(dec, bsz, S[i], dtype, device, has_mask[i])
+            m.update(step=st["step"], tokens=st["tokens"], anc=st["anc"])
+            st["others"].append(m)
         d = L.BeamDesc()
         d.dtype = L.dtype_code(dtype)
         d.bsz, d.beam, d.vocab, d.max_len = bsz, beam, self.vocab, self.max_len
@@ -182,6 +220,9 @@ class BeamDecodeEngine:
         d.unk_penalty, d.len_penalty, d.temperature = self.unk_penalty, self.len_penalty, self.temperature
         d.normalize_scores = int(self.normalize_scores)
         d.logits, d.ld_logits = st["logits"].data_ptr(), st["logits"].stride(0)
+        d.members = len(self.decs) if len(self.decs) > 1 else 0  # 0: the single-matrix kernels
+        for i, m in enumerate(st["others"]):
+            d.logits_n[i] = m["logits"].data_ptr()
         d.step, d.tokens, d.scores, d.anc = (st[k].data_ptr() for k in ("step", "tokens", "scores", "anc"))
         d.cands_to_ignore, d.finished, d.nfinal = st["ignore"].data_ptr(), st["finished"].data_ptr(), st["nfinal"].data_ptr()
         d.num_remaining = st["num_remaining"].data_ptr()
@@ -233,8 +274,16 @@ class BeamDecodeEngine:
                 "cst_layernorm_fwd")
 
     def _step(self, st, pk, bsz):
-        """One decode step: every launch reads the step counter from device memory."""
-        lib, dec = L.load(), self.dec
+        """One decode step: every launch reads the step counter from device memory.  The members' layer sequences follow one another
+        on the one stream (a linear graph; step graphs on several streams do not overlap on this stack — see `lanes`), then ONE
+        beam step reads all their logits."""
+        for dec, m, mpk in zip(self.decs, self.members(st), self.members(pk)):
+            self._step_member(dec, m, mpk, bsz)
+        L.check(L.load().cst_beam_step(ctypes.byref(st["desc"]), L.stream_ptr()), "cst_beam_step")
+
+    def _step_member(self, dec, st, pk, bsz):
+        """One member's decoder up to its vocabulary projection -> st["logits"]."""
+        lib = L.load()
         bbsz, C = st["x"].shape
         dt = L.dtype_code(st["x"].dtype)
         H = dec.layers[0].self_attn.num_heads
@@ -304,21 +353,24 @@ class BeamDecodeEngine:
             feat = x
         w = dec.output_projection.weight
         self._linear(feat, w, None, st["logits"])
-        L.check(lib.cst_beam_step(ctypes.byref(st["desc"]), L.stream_ptr()), "cst_beam_step")
         # an even number of x/x2 swaps per layer (3) x layers may leave the residual stream in x2: the NEXT step's embed always
         # writes st["x"], and every step performs the same swaps, so the captured sequence is step-invariant.
 
     # ------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def generate(self, encoder_out, bsz):
-        """encoder_out: EncoderOut with encoder_out [S, B, C] (T x B x C view) and encoder_padding_mask [B, S] or None.
+        """encoder_out: EncoderOut with encoder_out [S, B, C] (T x B x C view) and encoder_padding_mask [B, S] or None — for an
+        ensemble a list with one EncoderOut per member (each member's own encoder; lengths S and widths may differ).
         Returns the reference's `finalized` structure (list over sentences of hypothesis dicts, best first)."""
-        enc = encoder_out.encoder_out
-        S, B, Ce = enc.shape
-        assert B == bsz
-        dtype, device = enc.dtype, enc.device
-        mask = encoder_out.encoder_padding_mask
-        has_mask = mask is not None and mask.dim() == 2
+        eouts = [encoder_out] if hasattr(encoder_out, "encoder_out") else list(encoder_out)  # (an EncoderOut is itself a tuple)
+        assert len(eouts) == len(self.decs), "one encoder output per ensemble member"
+        encs = [e.encoder_out for e in eouts]
+        assert all(e.shape[1] == bsz for e in encs)
+        dtype, device = encs[0].dtype, encs[0].device
+        assert all(e.dtype == dtype for e in encs), "ensemble members must share the storage dtype"
+        masks = [e.encoder_padding_mask for e in eouts]
+        masks = [m if (m is not None and m.dim() == 2) else None for m in masks]
+        S, has_mask = tuple(e.shape[0] for e in encs), tuple(m is not None for m in masks)
         pk = self._pack(dtype, device)
         lanes = min(self.lanes, bsz)
         bounds = [(bsz * i // lanes, bsz * (i + 1) // lanes) for i in range(lanes)]
@@ -329,8 +381,8 @@ class BeamDecodeEngine:
         main = torch.cuda.current_stream()
         while lanes > 1 and len(self._streams) < lanes:
             self._streams.append(torch.cuda.Stream(device=device))
-        encb = enc.transpose(0, 1)
-        encb = encb if encb.is_contiguous() else encb.contiguous()
+        encb = [e.transpose(0, 1) for e in encs]
+        encb = [e if e.is_contiguous() else e.contiguous() for e in encb]
         total = self.max_len + 1
         runs = []
         for i, (b0, b1) in enumerate(bounds):
@@ -339,7 +391,7 @@ class BeamDecodeEngine:
                 stream.wait_stream(main)
             with torch.cuda.stream(stream):
                 st = self._alloc(i, b1 - b0, S, dtype, device, has_mask)
-                done = self._begin(st, pk, encb[b0:b1], mask[b0:b1] if has_mask else None, b1 - b0)
+                done = self._begin(st, pk, [e[b0:b1] for e in encb], [m[b0:b1] if m is not None else None for m in masks], b1 - b0)
             runs.append(dict(stream=stream, st=st, bsz=b1 - b0, steps=done, remaining=b1 - b0))
         while any(r["steps"] < total and r["remaining"] > 0 for r in runs):
             for r in runs:
@@ -366,13 +418,11 @@ class BeamDecodeEngine:
                 main.wait_stream(r["stream"])
         return finalized
 
-    def _begin(self, st, pk, encb, mask, bsz):
-        """Queues the per-call work of one lane on the current stream: the static cross-attention K/V of its sentences, the beam
-        state, and — first call of a configuration — the eager step 0 and the capture of the step graph.  Returns the number of
-        decode steps already taken (1 after that eager step, else 0)."""
+    def _begin_member(self, dec, st, encb, mask, bsz):
+        """The static cross-attention K/V of one member, projected from ITS encoder's output."""
         S, Ce = encb.shape[1], encb.shape[2]
         flat = encb.reshape(bsz * S, Ce)
-        for li, layer in enumerate(self.dec.layers):  # static cross-attention K/V, once per sentence (not per beam)
+        for li, layer in enumerate(dec.layers):  # static cross-attention K/V, once per sentence (not per beam)
             ca = layer.encoder_attn
             if self._cross_fits(st["x"].dtype, ca.head_dim):  # head-major [bsz, H, S, D] for cst_dec_cross_attn (one transposing copy per call)
                 for name, proj in (("kx", ca.k_proj), ("vx", ca.v_proj)):
@@ -384,6 +434,13 @@ class BeamDecodeEngine:
                 self._linear(flat, ca.v_proj.weight, ca.v_proj.bias, st["vx"][li].view(bsz * S, -1))
         if mask is not None:
             st["kpm"].copy_(mask.to(torch.uint8))
+
+    def _begin(self, st, pk, encb, mask, bsz):
+        """Queues the per-call work of one lane on the current stream: every member's static cross-attention K/V of its sentences, the beam
+        state, and — first call of a configuration — the eager step 0 and the capture of the step graph.  Returns the number of
+        decode steps already taken (1 after that eager step, else 0)."""
+        for dec, m, e, mk in zip(self.decs, self.members(st), encb, mask):
+            self._begin_member(dec, m, e, mk, bsz)
         L.check(L.load().cst_beam_init(ctypes.byref(st["desc"]), L.stream_ptr()), "cst_beam_init")
         if self.use_graph and st["graph"] is None:
             self._step(st, pk, bsz)  # eager warm-up step 0 (loads code objects, sizes the GEMM workspace)

@@ -1,6 +1,7 @@
 """Beam-search decoding — mirror of fairseq/sequence_generator.py (SequenceGenerator._generate :179-541,
 finalize_hypos :575-696, EnsembleModel.forward_encoder/forward_decoder :800-868) and fairseq/search.py BeamSearch.step
-(:109-144), for one model.  Decoder steps run through the incremental-state path of the HIP modules (K/V caches kept
+(:109-144), for one model or a checkpoint ensemble (`--path a.pt:b.pt:c.pt`: the members' next-token distributions are
+averaged at every step).  Decoder steps run through the incremental-state path of the HIP modules (K/V caches kept
 batch-major [B*beam, T, C]; single-query fused attention).
 
 Differences that do not change results: finished sentences are masked out instead of being removed from the batch
@@ -36,8 +37,14 @@ class SequenceGenerator:
     def __init__(self, models, tgt_dict, beam_size=1, max_len_a=0, max_len_b=200, min_len=1, normalize_scores=True,
                  len_penalty=1.0, unk_penalty=0.0, temperature=1.0, match_source_len=False, no_repeat_ngram_size=0,
                  search_strategy=None, eos=None, fused=True, use_graph=True, cross_kernel=None):
-        self.model = models[0] if isinstance(models, (list, tuple)) else models
+        self.models = list(models) if isinstance(models, (list, tuple)) else [models]
+        self.model = self.models[0]
         self.tgt_dict = tgt_dict
+        for i, m in enumerate(self.models):  # the members' distributions are averaged token by token: one target vocabulary
+            n = getattr(getattr(m.decoder, "embed_tokens", None), "num_embeddings", len(tgt_dict))
+            if n != len(tgt_dict):
+                raise ValueError("ensemble member %d has a target vocabulary of %d symbols, the dictionary has %d: the members of an "
+                                 "ensemble must share the target dictionary" % (i, n, len(tgt_dict)))
         self.pad, self.unk = tgt_dict.pad(), tgt_dict.unk()
         self.eos = tgt_dict.eos() if eos is None else eos
         self.vocab_size = len(tgt_dict)
@@ -53,20 +60,27 @@ class SequenceGenerator:
         self.fused = bool(fused) and search_strategy is None and (eos is None or eos == tgt_dict.eos())
         self._engine = None
         self.use_graph, self.cross_kernel = use_graph, cross_kernel
-        self.model.eval()
+        for m in self.models:
+            m.eval()
 
     @torch.no_grad()
     def generate(self, models, sample, prefix_tokens=None, **kwargs):
         assert prefix_tokens is None
         return self._generate(sample)
 
-    def _forward_decoder(self, tokens, encoder_out, incremental_state):
-        """sequence_generator.py:806-868 for a single model: last-step logits -> fp32 log-softmax (temperature applied)."""
-        logits, _ = self.model.decoder.forward(tokens, encoder_out=encoder_out, incremental_state=incremental_state)
-        logits = logits[:, -1:, :]
-        if self.temperature != 1.0:
-            logits = logits / self.temperature
-        return self.model.get_normalized_probs((logits, None), log_probs=True)[:, -1, :]
+    def _forward_decoder(self, tokens, encoder_outs, incremental_states):
+        """sequence_generator.py:806-868: per member the last-step logits / temperature -> fp32 log-softmax; an ensemble averages the
+        members' DISTRIBUTIONS: logsumexp over the members - log N (:862-864)."""
+        log_probs = []
+        for model, encoder_out, incremental_state in zip(self.models, encoder_outs, incremental_states):
+            logits, _ = model.decoder.forward(tokens, encoder_out=encoder_out, incremental_state=incremental_state)
+            logits = logits[:, -1:, :]
+            if self.temperature != 1.0:
+                logits = logits / self.temperature
+            log_probs.append(model.get_normalized_probs((logits, None), log_probs=True)[:, -1, :])
+        if len(log_probs) == 1:
+            return log_probs[0]
+        return torch.logsumexp(torch.stack(log_probs, dim=0), dim=0) - math.log(len(log_probs))
 
     def _generate(self, sample):
         net_input = sample["net_input"]
@@ -74,20 +88,21 @@ class SequenceGenerator:
         bsz, src_len = src_tokens.size()[:2]
         beam_size = self.beam_size
         device = src_tokens.device
-        max_len = min(int(self.max_len_a * src_len + self.max_len_b), self.model.max_decoder_positions() - 1)
+        max_len = min(int(self.max_len_a * src_len + self.max_len_b), min(m.max_decoder_positions() for m in self.models) - 1)  # :796-797
         assert self.min_len <= max_len
-        encoder_out = self.model.encoder.forward_torchscript(net_input)
+        encoder_outs = [m.encoder.forward_torchscript(net_input) for m in self.models]
         if self.fused:
             from .decode_engine import BeamDecodeEngine
-            if BeamDecodeEngine.supported(self.model.decoder):
+            if len(self.models) <= 8 and all(BeamDecodeEngine.supported(m.decoder) for m in self.models):  # else the whole ensemble takes the host loop
                 if self._engine is None or self._engine.max_len != max_len:
-                    self._engine = BeamDecodeEngine(self.model.decoder, self.tgt_dict, beam_size, max_len, self.min_len,
+                    decs = [m.decoder for m in self.models]
+                    self._engine = BeamDecodeEngine(decs if len(decs) > 1 else decs[0], self.tgt_dict, beam_size, max_len, self.min_len,
                                                     self.normalize_scores, self.len_penalty, self.unk_penalty, self.temperature,
                                                     use_graph=self.use_graph, cross_kernel=self.cross_kernel)
-                return self._engine.generate(encoder_out, bsz)
+                return self._engine.generate(encoder_outs if len(encoder_outs) > 1 else encoder_outs[0], bsz)
         new_order = torch.arange(bsz, device=device).view(-1, 1).repeat(1, beam_size).view(-1)
-        encoder_out = self.model.encoder.reorder_encoder_out(encoder_out, new_order)
-        incremental_state: Dict[str, Dict[str, Optional[Tensor]]] = {}
+        encoder_outs = [m.encoder.reorder_encoder_out(e, new_order) for m, e in zip(self.models, encoder_outs)]
+        incremental_states: List[Dict[str, Dict[str, Optional[Tensor]]]] = [{} for _ in self.models]
 
         scores = torch.zeros(bsz * beam_size, max_len + 1, device=device, dtype=torch.float32)
         tokens = torch.full((bsz * beam_size, max_len + 2), self.pad, device=device, dtype=torch.long)
@@ -103,9 +118,10 @@ class SequenceGenerator:
 
         for step in range(max_len + 1):
             if reorder_state is not None:
-                self.model.decoder.reorder_incremental_state_scripting(incremental_state, reorder_state)
-                encoder_out = self.model.encoder.reorder_encoder_out(encoder_out, reorder_state)
-            lprobs = self._forward_decoder(tokens[:, :step + 1], encoder_out, incremental_state)
+                for m, inc in zip(self.models, incremental_states):
+                    m.decoder.reorder_incremental_state_scripting(inc, reorder_state)
+                encoder_outs = [m.encoder.reorder_encoder_out(e, reorder_state) for m, e in zip(self.models, encoder_outs)]
+            lprobs = self._forward_decoder(tokens[:, :step + 1], encoder_outs, incremental_states)
             lprobs[lprobs != lprobs] = -math.inf
             lprobs[:, self.pad] = -math.inf
             lprobs[:, self.unk] -= self.unk_penalty

@@ -31,9 +31,9 @@ extern "C" {
 /* Bumps on any change of a signature or a descriptor layout (3: cst_gemm_desc.m_len, cst_attn_desc.seq_offsets, workspaces of the
  * fixed-order reductions; 4: cst_attn_desc.kpm_bits / bwd_ws, the separable attention-dropout mask; 5: cst_gemm_desc.colsum;
  * 6: cst_dec_ln_q_cross_attn; 7: cst_fbank_desc, cst_fbank, cst_fbank_workspace_bytes; 8: cst_conv0_ln_gelu_fwd / _bwd,
- * cst_ln_gelu_fwd / _bwd and their workspaces).
+ * cst_ln_gelu_fwd / _bwd and their workspaces; 9: cst_beam_desc.members / logits_n / lprobs_out — checkpoint ensembles).
  * cst_version() returns the value the library was built with; chimera-st_amd/lib.py refuses a mismatch. */
-#define CST_ABI_VERSION 8
+#define CST_ABI_VERSION 9
 
 typedef enum { CST_F32 = 0, CST_BF16 = 1 } cst_dtype;
 
@@ -515,6 +515,12 @@ int cst_adam_step(float* master, float* exp_avg, float* exp_avg_sq, const void* 
  * cst_beam_step: fp32 log-softmax of logits [bbsz, vocab] (/temperature), NaN/pad/unk/min-len/max-len masks, + cumulative
  *   score, top-(2*beam) per sentence, eos finalisation, next active hypotheses, then *step += 1.  beam <= 20.
  *   logits: 16-byte aligned, ld_logits a multiple of 16 bytes and >= vocab rounded up to it (rows are read as vectors).
+ *   members = N >= 2 (at most 8, else CST_ERR_BAD_ARG): the step searches the AVERAGE of N models' next-token distributions
+ *   (sequence_generator.py EnsembleModel.forward_decoder :806-868): per member lse_n = logsumexp_v(l_n[v] / temperature), then
+ *   lp[v] = log(sum_n exp(l_n[v] / temperature - lse_n)) - log N, in fp32 inside the same first kernel (no extra launch; the
+ *   per-element maximum over the members is taken out before the exp; -inf in every member stays -inf; a member whose row
+ *   has NaN logits or no finite entry makes the row NaN -> -inf, as the reference's stack + logsumexp does).  The
+ *   temperature divides every member's logits BEFORE its softmax.  Masks, scores, top-2*beam and bookkeeping are unchanged.
  * ------------------------------------------------------------------------------------------ */
 typedef struct {
   int dtype;                         /* storage type of logits */
@@ -528,6 +534,9 @@ typedef struct {
   uint8_t* cands_to_ignore; uint8_t* finished; int32_t* nfinal; int32_t* num_remaining;
   int64_t* fin_tokens; float* fin_pos; float* fin_score; int32_t* fin_len;
   void* workspace;                   /* cst_beam_workspace(bsz, beam) bytes, 16-byte aligned: per-row candidates + step ticket */
+  int64_t members;                   /* checkpoint ensemble (ABI 9): 0 or 1 = the single matrix `logits`; N >= 2 = `logits` and logits_n[0 .. N-2] */
+  const void* logits_n[7];           /* members 1 .. N-1: same rows, vocab, ld_logits, dtype and alignment as `logits` */
+  float* lprobs_out;                 /* optional, members >= 2: fp32 [bbsz][ld_logits], the combined log-probabilities before the masks */
 } cst_beam_desc;
 int64_t cst_beam_workspace(int64_t bsz, int64_t beam);
 int cst_beam_init(const cst_beam_desc* d, cst_stream stream);

@@ -2,12 +2,14 @@
 """Decode throughput of BASELINE config 5 (SURVEY §8d "Decode"): s2t_transformer_l (d 1024, ffn 4096, 16 heads, 12 encoder +
 6 decoder layers, 10 000-way tied vocabulary), filter-bank input, beam 5, incremental-state decode, 1 x MI355X, bf16.
 
-  python tools/bench_decode.py [--batch 32] [--frames 3000] [--beam 5] [--max-len 200] [--reps 3] [--mirror]
+  python tools/bench_decode.py [--batch 32] [--frames 3000] [--beam 5] [--max-len 200] [--reps 3] [--mirror] [--ensemble N]
 
 Prints one JSON line: utterances/s and generated tokens/s of the device-resident loop (decode_engine.py: one captured HIP
 graph per step), the per-step time, the encoder time, and — with --mirror — the same numbers for the host-driven
 module-by-module loop (fused=False).  Random-init weights emit eos only when forced, so every sentence runs the full
-max_len + 1 steps: the reported rate is the worst case for the configured max_len."""
+max_len + 1 steps: the reported rate is the worst case for the configured max_len.
+--ensemble N decodes N independently seeded copies of the model as a checkpoint ensemble (every member's encoder and decoder run;
+one beam step over the N logits matrices) and adds "models" and "nodes_per_step" to the line."""
 import argparse
 import importlib
 import json
@@ -34,6 +36,7 @@ def main():
     ap.add_argument("--mirror", action="store_true", help="also time the host-driven loop (fused=False)")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--cross-kernel", default="flash", choices=["flash", "flash_hm", "shared"])
+    ap.add_argument("--ensemble", type=int, default=1, help="decode N independently seeded copies of the model as an ensemble")
     ap.add_argument("--profile", action="store_true", help="per-class GPU time of one eager decode loop (hipEvent pairs)")
     args = ap.parse_args()
 
@@ -50,6 +53,10 @@ def main():
     ns = Namespace(share_decoder_input_output_embed=True, dropout=0.0)
     reg.ARCH_CONFIG_REGISTRY[args.arch](ns)
     model = s2t.S2TTransformerModel.build_model(ns, task).to("cuda", dt).eval()
+    models = [model]
+    for k in range(1, args.ensemble):
+        torch.manual_seed(1 + k)
+        models.append(s2t.S2TTransformerModel.build_model(ns, task).to("cuda", dt).eval())
 
     g = torch.Generator().manual_seed(1)
     lens = torch.randint(args.frames // 3, args.frames + 1, (args.batch,), generator=g).sort(descending=True)[0]
@@ -58,11 +65,11 @@ def main():
     sample = {"net_input": {"src_tokens": src, "src_lengths": lens.cuda()}}
 
     def timed(gen):
-        hyps = gen.generate([model], sample)  # warm-up (graph capture, code objects)
+        hyps = gen.generate(models, sample)  # warm-up (graph capture, code objects)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(args.reps):
-            hyps = gen.generate([model], sample)
+            hyps = gen.generate(models, sample)
         torch.cuda.synchronize()
         dt_ = (time.perf_counter() - t0) / args.reps
         ntok = sum(len(h[0]["tokens"]) for h in hyps)
@@ -72,11 +79,12 @@ def main():
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(args.reps):
-            model.encoder(src, sample["net_input"]["src_lengths"])
+            for m in models:
+                m.encoder(src, sample["net_input"]["src_lengths"])
         torch.cuda.synchronize()
         enc_s = (time.perf_counter() - t0) / args.reps
 
-    fused = SG([model], task.target_dictionary, beam_size=args.beam, max_len_a=0, max_len_b=args.max_len, use_graph=not args.no_graph,
+    fused = SG(models, task.target_dictionary, beam_size=args.beam, max_len_a=0, max_len_b=args.max_len, use_graph=not args.no_graph,
                cross_kernel=args.cross_kernel)
     t_f, ntok = timed(fused)
     steps = args.max_len + 1
@@ -84,17 +92,20 @@ def main():
            "beam": args.beam, "max_frames": args.frames, "max_len": args.max_len, "dtype": args.dtype, "graph": not args.no_graph},
            "utterances_per_s": args.batch / t_f, "tokens_per_s": ntok / t_f, "best_hyp_tokens": ntok, "s_per_batch": t_f,
            "encoder_s": enc_s, "ms_per_step": (t_f - enc_s) / steps * 1e3, "hyp_rows_per_step": args.batch * args.beam}
+    if args.ensemble > 1:
+        out["models"] = args.ensemble
+        out["nodes_per_step"] = fused._engine.nodes_per_step(dt, args.batch * args.beam)
     if args.mirror:
-        mirror = SG([model], task.target_dictionary, beam_size=args.beam, max_len_a=0, max_len_b=args.max_len, fused=False)
+        mirror = SG(models, task.target_dictionary, beam_size=args.beam, max_len_a=0, max_len_b=args.max_len, fused=False)
         t_m, ntok_m = timed(mirror)
         out["mirror_host_loop"] = {"utterances_per_s": args.batch / t_m, "tokens_per_s": ntok_m / t_m, "s_per_batch": t_m,
                                    "ms_per_step": (t_m - enc_s) / steps * 1e3}
         out["speedup_vs_host_loop"] = t_m / t_f
     if args.profile:
-        eager = SG([model], task.target_dictionary, beam_size=args.beam, max_len_a=0, max_len_b=args.max_len, use_graph=False)
-        eager.generate([model], sample)
+        eager = SG(models, task.target_dictionary, beam_size=args.beam, max_len_a=0, max_len_b=args.max_len, use_graph=False)
+        eager.generate(models, sample)
         lib.prof_enable(True)
-        eager.generate([model], sample)
+        eager.generate(models, sample)
         torch.cuda.synchronize()
         table = lib.prof_query()
         lib.prof_enable(False)
