@@ -14,8 +14,7 @@ _ACT = {None: L.ACT_NONE, "none": L.ACT_NONE, "relu": L.ACT_RELU, "gelu": L.ACT_
 
 
 def _flat2d(x):
-    x2 = x.reshape(-1, x.shape[-1])
-    return x2 if x2.is_contiguous() else x2.contiguous()
+    return x.reshape(-1, x.shape[-1]).contiguous()
 
 
 # ------------------------------------------------------------------------------------------------
@@ -67,7 +66,7 @@ def _wversion(w):
 
 
 class _WeightTransposes:
-    """W^T copies of the Linear weights the dX GEMMs read (see _linear_backward), kept across updates.  A weight changes only in the
+    """W^T copies of the Linear weights the dX GEMMs read (see _dx_gemm), kept across updates.  A weight changes only in the
     optimizer step (optim.PARAM_EPOCH counts every raw-pointer write of the flat parameter buffer) or through an in-place torch op
     (its autograd version): the first request after an optimizer step refreshes EVERY registered copy in one launch
     (cst_transpose2d_multi — one launch per update instead of one small launch per Linear per backward pass: 0.75 -> 0.15 ms per
@@ -188,7 +187,7 @@ class _LinearFn(torch.autograd.Function):
         x2 = _flat2d(x)
         M, Kd = x2.shape
         N = weight.shape[0]
-        w = weight if weight.is_contiguous() else weight.contiguous()
+        w = weight.contiguous()
         ctx.bias_obj = bias  # (the Parameter / stacked view itself: _may_defer looks at its .grad and marks in backward)
         # odd output widths (e.g. a 60-symbol test vocabulary in bf16): zero-pad the rows of W up to the 16-byte vector
         # the dX / dW loaders need; real shapes (512/768/1024/2048/3072/10000) never take this branch.
@@ -220,6 +219,46 @@ class _LinearFn(torch.autograd.Function):
         return _linear_backward(ctx, dy, None)
 
 
+def _dx_gemm(dz, w, M, *, use_wt, like, resid=None, dact=L.ACT_NONE, aux_in=None, drop=(0.0, 0), m_live=None):
+    """dX [M, n_in] = dropout((dz [M, n_out] W [n_out, n_in]) * act'(aux_in)) + resid, allocated like `like`.
+    use_wt (large token counts, _want_wt): W^T [n_in, n_out] as a k-major B operand — both operands are then read the way the
+    forward GEMM reads them (the transpose reads of an mn-major W measured 15-20 % slower on the 31 760-row shapes); the
+    transposed copy of a <= 5 MB weight costs a few microseconds."""
+    n_out, n_in = w.shape
+    dx = torch.empty(M, n_in, dtype=like.dtype, device=like.device)
+    b, b_kmajor, ldb = (WEIGHT_TRANSPOSES.get(w), 1, n_out) if use_wt else (w, 0, n_in)
+    K.gemm(dz, b, dx, M, n_in, n_out, a_kmajor=1, b_kmajor=b_kmajor, lda=n_out, ldb=ldb, ldc=n_in, dact=dact, aux_in=aux_in, ld_aux_in=n_in,
+           resid=resid, ld_resid=n_in, split_k=1, drop_p=drop[0], drop_key=drop[1], m_live=m_live)
+    return dx
+
+
+def _dw_gemm(dz, x2, w, bias_obj, M, *, db_in_dw, live, dz_travels_on, allow_slot=True, allow_defer=True):
+    """(dW [n_out, n_in] = dz^T x2 over M rows, its bias gradient or None): THE weight-gradient launch of a Linear.
+    dW goes into the weight's slot of the flat gradient buffer where there is one (allow_slot).  db_in_dw: the bias gradient rides in
+    this GEMM (cst_gemm_desc.colsum: the caller has asked dw_colsum_is_fused).  The split-K reduce may wait for the deferred flush
+    when _may_defer says so for the weight — and for bias_obj, the bias Parameter / stacked view itself, when its gradient rides along.
+    A small layer's weight gradient runs on the side stream, off the dX chain (kernels.side_gemm); not when dz IS the incoming
+    gradient that also travels on as the residual gradient (dz_travels_on): something upstream might add into it in place."""
+    n_out, n_in = w.shape
+    dw = _grad_out(w) if allow_slot else None
+    if dw is None:
+        dw = torch.empty(n_out, n_in, dtype=w.dtype, device=w.device)
+    db = torch.empty(n_out, dtype=w.dtype, device=w.device) if db_in_dw else None
+    may = allow_defer and _may_defer(w, bias_obj if db_in_dw else None)
+    big = not may or not K.dw_colsum_is_fused(n_out, n_in, M, w.dtype) or dz_travels_on
+    K.side_gemm(big, (dz, x2, live[0] if live is not None else None), dz, x2, dw, n_out, n_in, M, a_kmajor=0, b_kmajor=0, lda=n_out, ldb=n_in,
+                ldc=n_in, split_k=-1, k_live=live, colsum=db, defer=may)
+    return dw, db
+
+
+def _drop_grad(dy2, drop, out_dtype, live, *, with_colsum, defer):
+    """(dy2 * the dropout mask regenerated from drop = (p, key), the bias gradient or None).  with_colsum: the masked gradient is
+    what the bias sees and nothing else produces its gradient: mask + column sums in one pass (second stage deferrable: `defer`)."""
+    if with_colsum and not _os.environ.get("CST_NO_DROP_COLSUM"):
+        return K.dropout_colsum(dy2.contiguous(), drop[0], drop[1], out_dtype, live, defer=defer)
+    return K.dropout(dy2.contiguous(), *drop), None
+
+
 def _linear_backward(ctx, dy, dxp):
     """Shared by _LinearFn / _LinearPassFn.  dxp: gradient that reached the pass-through alias of x (the residual branch of the
     block this projection opens); it is added in the dX GEMM's epilogue instead of by an autograd accumulation kernel."""
@@ -240,39 +279,18 @@ def _linear_backward(ctx, dy, dxp):
     db_in_dw = want_db and ctx.needs_input_grad[1] and Np % 8 == 0 and not _os.environ.get("CST_NO_GEMM_COLSUM") and K.dw_colsum_is_fused(Np, Kd, M, w.dtype)
     may_b = want_db and Np == N and _may_defer(w, ctx.bias_obj)  # the bias gradient's second stage may wait for the flush
     if ctx.drop[0] > 0.0:  # gradient of the dropped branch: the same mask, regenerated
-        dyc = dy2 if dy2.is_contiguous() else dy2.contiguous()
-        if not db_in_dw and ctx.act == L.ACT_NONE and want_db and Np == N and N % 8 == 0 and not _os.environ.get("CST_NO_DROP_COLSUM"):
-            dy2, db_fused = K.dropout_colsum(dyc, ctx.drop[0], ctx.drop[1], w.dtype, live, defer=may_b)  # mask + bias gradient in one pass
-        else:
-            dy2 = K.dropout(dyc, *ctx.drop)
+        dy2, db_fused = _drop_grad(dy2, ctx.drop, w.dtype, live, defer=may_b,
+                                   with_colsum=not db_in_dw and ctx.act == L.ACT_NONE and want_db and Np == N and N % 8 == 0)
     dz = K.act_bwd(dy2, z, ctx.act) if ctx.act != L.ACT_NONE else dy2
     dx = dw = db = dres = None
     if ctx.needs_input_grad[0]:
-        dx = torch.empty(M, Kd, dtype=x2.dtype, device=x2.device)
-        if _want_wt(M, w):
-            # large token counts: dY W with W^T [K_in, N_out] as a k-major B operand — both operands are then read the way the
-            # forward GEMM reads them (the transpose reads of an mn-major W measured 15-20 % slower on the 31 760-row shapes); the
-            # transposed copy of a <= 5 MB weight costs a few microseconds
-            K.gemm(dz, WEIGHT_TRANSPOSES.get(w), dx, M, Kd, Np, a_kmajor=1, b_kmajor=1, lda=Np, ldb=Np, ldc=Kd, split_k=1,
-                   resid=_flat2d(dxp) if dxp is not None else None, ld_resid=Kd, m_live=live)
-        else:
-            K.gemm(dz, w, dx, M, Kd, Np, a_kmajor=1, b_kmajor=0, lda=Np, ldb=Kd, ldc=Kd, split_k=1,
-                   resid=_flat2d(dxp) if dxp is not None else None, ld_resid=Kd, m_live=live)
-        dx = dx.view(ctx.xshape)
+        dx = _dx_gemm(dz, w, M, use_wt=_want_wt(M, w), like=x2, resid=_flat2d(dxp) if dxp is not None else None,
+                      m_live=live).view(ctx.xshape)
         if live is not None and dxp is None:
             dx = _with_tiles(dx, live)  # a zero row of dz is a zero row of dz W
     if ctx.needs_input_grad[1]:
-        dw = _grad_out(w) if Np == N else None
-        if dw is None:
-            dw = torch.empty(Np, Kd, dtype=w.dtype, device=w.device)
-        if db_in_dw:
-            db = torch.empty(Np, dtype=w.dtype, device=w.device)
-        may = Np == N and _may_defer(w, ctx.bias_obj if db_in_dw else None)
-        # (a small layer's weight gradient runs on the side stream, off the dX chain — kernels.side_gemm; not when dz IS the incoming
-        #  gradient that also travels on as the residual gradient: something upstream might add into it in place)
-        big = not may or not K.dw_colsum_is_fused(Np, Kd, M, w.dtype) or (dz.data_ptr() == dy.data_ptr() and ctx.has_resid)
-        K.side_gemm(big, (dz, x2, live[0] if live is not None else None), dz, x2, dw, Np, Kd, M, a_kmajor=0, b_kmajor=0, lda=Np, ldb=Kd, ldc=Kd,
-                    split_k=-1, k_live=live, colsum=db, defer=may)
+        dw, db = _dw_gemm(dz, x2, w, ctx.bias_obj, M, db_in_dw=db_in_dw, live=live, dz_travels_on=dz.data_ptr() == dy.data_ptr() and ctx.has_resid,
+                          allow_slot=Np == N, allow_defer=Np == N)
         dw = dw[:N]
         if db is not None:
             db = db[:N]
@@ -352,51 +370,19 @@ class _FFNFn(torch.autograd.Function):
         db2_in_dw = gcs and has_b2 and ctx.needs_input_grad[4] and ctx.needs_input_grad[3] and dout % 8 == 0 and K.dw_colsum_is_fused(dout, F_, M, w2.dtype)
         db1_in_dw = gcs and has_b1 and ctx.needs_input_grad[2] and ctx.needs_input_grad[1] and F_ % 8 == 0 and K.dw_colsum_is_fused(F_, d, M, w1.dtype)
         if p_out > 0.0:  # d(fc2 output) = dy * mask_out
-            dyc = dy2 if dy2.is_contiguous() else dy2.contiguous()
-            if not db2_in_dw and has_b2 and ctx.needs_input_grad[4] and dout % 8 == 0 and not _os.environ.get("CST_NO_DROP_COLSUM"):
-                dy2, db2_fused = K.dropout_colsum(dyc, p_out, key_out, w2.dtype, live, defer=_may_defer(w2, b2))  # mask + fc2 bias gradient in one pass
-            else:
-                dy2 = K.dropout(dyc, p_out, key_out)
-        dz1 = torch.empty(M, F_, dtype=dy2.dtype, device=dy2.device)
-        wt = _want_wt(M, w2) and _want_wt(M, w1)  # dX GEMMs with the weights as k-major B operands (see _linear_backward)
-        if wt:
-            K.gemm(dy2, WEIGHT_TRANSPOSES.get(w2), dz1, M, F_, dout, a_kmajor=1, b_kmajor=1, lda=dout, ldb=dout, ldc=F_, dact=act, aux_in=z1, ld_aux_in=F_,
-                   split_k=1, drop_p=p_act, drop_key=key_act, m_live=live)
-        else:
-            K.gemm(dy2, w2, dz1, M, F_, dout, a_kmajor=1, b_kmajor=0, lda=dout, ldb=F_, ldc=F_, dact=act, aux_in=z1, ld_aux_in=F_, split_k=1,
-                   drop_p=p_act, drop_key=key_act, m_live=live)
+            dy2, db2_fused = _drop_grad(dy2, (p_out, key_out), w2.dtype, live, defer=_may_defer(w2, b2),
+                                        with_colsum=not db2_in_dw and has_b2 and ctx.needs_input_grad[4] and dout % 8 == 0)
+        use_wt = _want_wt(M, w2) and _want_wt(M, w1)  # both dX GEMMs or neither
+        dz1 = _dx_gemm(dy2, w2, M, use_wt=use_wt, like=dy2, dact=act, aux_in=z1, drop=(p_act, key_act), m_live=live)
         dx = dw1 = db1 = dw2 = db2 = None
         if ctx.needs_input_grad[3]:
-            dw2 = _grad_out(w2)
-            if dw2 is None:
-                dw2 = torch.empty(dout, F_, dtype=w2.dtype, device=w2.device)
-            if db2_in_dw:
-                db2 = torch.empty(dout, dtype=w2.dtype, device=w2.device)
-            may2 = _may_defer(w2, b2 if db2_in_dw else None)
-            big2 = not may2 or not K.dw_colsum_is_fused(dout, F_, M, w2.dtype) or (dy2.data_ptr() == dy.data_ptr() and has_res)
-            K.side_gemm(big2, (dy2, h, live[0] if live is not None else None), dy2, h, dw2, dout, F_, M, a_kmajor=0, b_kmajor=0, lda=dout, ldb=F_,
-                        ldc=F_, split_k=-1, k_live=live, colsum=db2, defer=may2)
+            dw2, db2 = _dw_gemm(dy2, h, w2, b2, M, db_in_dw=db2_in_dw, live=live, dz_travels_on=dy2.data_ptr() == dy.data_ptr() and has_res)
         if has_b2 and ctx.needs_input_grad[4] and db2 is None:
             db2 = db2_fused if db2_fused is not None else K.colsum(dy2, w2.dtype, live, defer=_may_defer(w2, b2))
         if ctx.needs_input_grad[0]:
-            dx = torch.empty(M, d, dtype=x2.dtype, device=x2.device)
-            if wt:
-                K.gemm(dz1, WEIGHT_TRANSPOSES.get(w1), dx, M, d, F_, a_kmajor=1, b_kmajor=1, lda=F_, ldb=F_, ldc=d, split_k=1,
-                       resid=_flat2d(dy) if ctx.res_is_x else None, ld_resid=d, m_live=live)
-            else:
-                K.gemm(dz1, w1, dx, M, d, F_, a_kmajor=1, b_kmajor=0, lda=F_, ldb=d, ldc=d, split_k=1,
-                       resid=_flat2d(dy) if ctx.res_is_x else None, ld_resid=d, m_live=live)
-            dx = dx.view(xshape)
+            dx = _dx_gemm(dz1, w1, M, use_wt=use_wt, like=x2, resid=_flat2d(dy) if ctx.res_is_x else None, m_live=live).view(xshape)
         if ctx.needs_input_grad[1]:
-            dw1 = _grad_out(w1)
-            if dw1 is None:
-                dw1 = torch.empty(F_, d, dtype=w1.dtype, device=w1.device)
-            if db1_in_dw:
-                db1 = torch.empty(F_, dtype=w1.dtype, device=w1.device)
-            may1 = _may_defer(w1, b1 if db1_in_dw else None)
-            big1 = not may1 or not K.dw_colsum_is_fused(F_, d, M, w1.dtype)
-            K.side_gemm(big1, (dz1, x2, live[0] if live is not None else None), dz1, x2, dw1, F_, d, M, a_kmajor=0, b_kmajor=0, lda=F_, ldb=d,
-                        ldc=d, split_k=-1, k_live=live, colsum=db1, defer=may1)
+            dw1, db1 = _dw_gemm(dz1, x2, w1, b1, M, db_in_dw=db1_in_dw, live=live, dz_travels_on=False)
         if has_b1 and ctx.needs_input_grad[2] and db1 is None:
             db1 = K.colsum(dz1, w1.dtype, live, defer=_may_defer(w1, b1))
         dres = dy if has_res and ctx.needs_input_grad[5] and not (ctx.res_is_x and ctx.needs_input_grad[0]) else None
@@ -521,6 +507,15 @@ def _mask_and_len(key_padding_mask):
     return u8, kvl
 
 
+def _laid_out_like(do, o):
+    """The incoming gradient of an attention output, copied into o's strides where autograd delivers it in others."""
+    if do.stride() == o.stride():
+        return do
+    tmp = torch.empty_like(o)
+    tmp.copy_(do)
+    return tmp
+
+
 class _AttnFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, kpm, kvl, H, causal, scale, layout_q, layout_kv, drop_p, drop_key):
@@ -534,11 +529,7 @@ class _AttnFn(torch.autograd.Function):
     def backward(ctx, do):
         q, k, v, o, lse, kpm, kvl = ctx.saved_tensors
         H, D, causal, scale, lq, lkv, drop_p, drop_key = ctx.cfg
-        if do.stride() != o.stride():
-            tmp = torch.empty_like(o)
-            tmp.copy_(do)
-            do = tmp
-        dq, dk, dv = K.attn_bwd(do, q, k, v, o, lse, H, D, kpm, causal, scale, lq, lkv, drop_p, drop_key, kvl)
+        dq, dk, dv = K.attn_bwd(_laid_out_like(do, o), q, k, v, o, lse, H, D, kpm, causal, scale, lq, lkv, drop_p, drop_key, kvl)
         return dq, dk, dv, None, None, None, None, None, None, None, None, None
 
 
@@ -561,16 +552,9 @@ class _AttnKVFn(torch.autograd.Function):
     def backward(ctx, do):
         q, kv, o, lse, kpm, kvl = ctx.saved_tensors
         H, D, C, scale, drop_p, drop_key = ctx.cfg
-        if do.stride() != o.stride():
-            tmp = torch.empty_like(o)
-            tmp.copy_(do)
-            do = tmp
-        k, v = kv[..., :C], kv[..., C:]
         dq, dkv = torch.empty_like(q), torch.empty_like(kv)
-        delta = torch.empty_like(lse)
-        d = K.attn_desc(q, k, v, o, lse, H, D, kpm, False, scale, "bt", "bt", drop_p, drop_key, kvl)
-        K.attn_bwd_fill(d, do, dq, dkv[..., :C], dkv[..., C:], delta, D, "bt", "bt")
-        K.attn_bwd_desc(d)
+        K.attn_bwd(_laid_out_like(do, o), q, kv[..., :C], kv[..., C:], o, lse, H, D, kpm, False, scale, "bt", "bt", drop_p, drop_key, kvl,
+                   grads=(dq, dkv[..., :C], dkv[..., C:]))
         return dq, dkv, None, None, None, None, None, None
 
 
@@ -632,12 +616,8 @@ class _AttnPackedFn(torch.autograd.Function):
         if not do.is_contiguous():
             do = do.contiguous()
         dqkv = torch.empty_like(qkv)
-        q, k, v = qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:]
-        dq, dk, dv = dqkv[..., :C], dqkv[..., C:2 * C], dqkv[..., 2 * C:]
-        delta = torch.empty_like(lse)
-        d = K.attn_desc(q, k, v, o, lse, H, D, kpm, causal, scale, "bt", "bt", drop_p, drop_key, kvl, seq)
-        K.attn_bwd_fill(d, do, dq, dk, dv, delta, D, "bt", "bt")
-        K.attn_bwd_desc(d)
+        K.attn_bwd(do, qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:], o, lse, H, D, kpm, causal, scale, "bt", "bt", drop_p, drop_key, kvl, seq,
+                   grads=(dqkv[..., :C], dqkv[..., C:2 * C], dqkv[..., 2 * C:]))
         if live is not None:
             # row t of dq|dk|dv is exactly zero when dO_t is (dS_t. = P_t. * 0) AND key t is padding (P_.t = 0): a 64-row tile
             # that is dead in dO and all padding is dead here; every other tile is declared live
@@ -743,13 +723,13 @@ class _PackRowsFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, seq):
         ctx.seq = seq
-        return K.rows_pack(x if x.is_contiguous() else x.contiguous(), seq.offsets, seq.rows, tail_sum=False).unsqueeze(0)
+        return K.rows_pack(x.contiguous(), seq.offsets, seq.rows, tail_sum=False).unsqueeze(0)
 
     @staticmethod
     def backward(ctx, dy):
         s = ctx.seq
         dy2 = dy.reshape(s.rows, dy.shape[-1])
-        return K.rows_unpack(dy2 if dy2.is_contiguous() else dy2.contiguous(), s.offsets, s.B, s.T, tail_broadcast=False), None
+        return K.rows_unpack(dy2.contiguous(), s.offsets, s.B, s.T, tail_broadcast=False), None
 
 
 class _UnpackRowsFn(torch.autograd.Function):
@@ -760,12 +740,12 @@ class _UnpackRowsFn(torch.autograd.Function):
     def forward(ctx, y, seq, broadcast):
         ctx.seq, ctx.broadcast = seq, broadcast
         y2 = y.reshape(seq.rows, y.shape[-1])
-        return K.rows_unpack(y2 if y2.is_contiguous() else y2.contiguous(), seq.offsets, seq.B, seq.T, tail_broadcast=broadcast)
+        return K.rows_unpack(y2.contiguous(), seq.offsets, seq.B, seq.T, tail_broadcast=broadcast)
 
     @staticmethod
     def backward(ctx, dx):
         s = ctx.seq
-        return K.rows_pack(dx if dx.is_contiguous() else dx.contiguous(), s.offsets, s.rows, tail_sum=ctx.broadcast).unsqueeze(0), None, None
+        return K.rows_pack(dx.contiguous(), s.offsets, s.rows, tail_sum=ctx.broadcast).unsqueeze(0), None, None
 
 
 def pack_rows(x, seq):
@@ -780,14 +760,18 @@ def unpack_rows(y, seq, broadcast=True):
 # ------------------------------------------------------------------------------------------------
 # wav2vec2 conv layer 0 + GroupNorm + GELU
 # ------------------------------------------------------------------------------------------------
+def _conv0_args(wav, w, write_limit, grad_limit):
+    """-> (fp32 contiguous wav, w as [C, k], k, the frame limits) of the two layer-0 Functions."""
+    C, _, k = w.shape
+    if _os.environ.get("CST_NO_MLEN") or _os.environ.get("CST_GEMM_NO_KLIVE"):
+        write_limit = grad_limit = None  # (with the GEMM-side skipping off, every frame of this layer is read)
+    return wav.float().contiguous(), w.reshape(C, k).contiguous(), k, write_limit, grad_limit
+
+
 class _Conv0Fn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, wav, w, gamma, beta, stride, eps, write_limit, grad_limit):
-        C, _, k = w.shape
-        w2 = w.reshape(C, k).contiguous()
-        wav = wav.float().contiguous()
-        if _os.environ.get("CST_NO_MLEN") or _os.environ.get("CST_GEMM_NO_KLIVE"):
-            write_limit = grad_limit = None  # (with the GEMM-side skipping off, every frame of this layer is read)
+        wav, w2, k, write_limit, grad_limit = _conv0_args(wav, w, write_limit, grad_limit)
         y, mean, rstd, gram = K.conv0_fwd(wav, w2, gamma, beta, k, stride, eps, frame_limit=write_limit)
         ctx.save_for_backward(wav, w2, gamma, beta, mean, rstd, gram)
         ctx.k, ctx.stride, ctx.grad_limit = k, stride, grad_limit
@@ -813,11 +797,7 @@ def conv0_gn_gelu(wav, weight, gn_weight, gn_bias, stride, eps=1e-5, write_limit
 class _Conv0LnFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, wav, w, bias, gamma, beta, stride, eps, write_limit, grad_limit):
-        C, _, k = w.shape
-        w2 = w.reshape(C, k).contiguous()
-        wav = wav.float().contiguous()
-        if _os.environ.get("CST_NO_MLEN") or _os.environ.get("CST_GEMM_NO_KLIVE"):
-            write_limit = grad_limit = None  # (with the GEMM-side skipping off, every frame of this layer is read)
+        wav, w2, k, write_limit, grad_limit = _conv0_args(wav, w, write_limit, grad_limit)
         y, mean, rstd = K.conv0_ln_fwd(wav, w2, bias, gamma, beta, k, stride, eps, frame_limit=write_limit)
         ctx.save_for_backward(wav, w2, bias, gamma, beta, mean, rstd)
         ctx.k, ctx.stride, ctx.grad_limit = k, stride, grad_limit
@@ -846,7 +826,7 @@ class _LnGeluFn(torch.autograd.Function):
     def forward(ctx, u, gamma, beta, conv_bias, eps, row_limit):
         if _os.environ.get("CST_NO_MLEN"):
             row_limit = None
-        u = u if u.is_contiguous() else u.contiguous()
+        u = u.contiguous()
         y, mean, rstd = K.ln_gelu_fwd(u, gamma, beta, eps, row_limit)
         ctx.save_for_backward(u, gamma, beta, mean, rstd)
         ctx.row_limit = row_limit
@@ -857,7 +837,7 @@ class _LnGeluFn(torch.autograd.Function):
     def backward(ctx, dy):
         u, gamma, beta, mean, rstd = ctx.saved_tensors
         want_bias = ctx.bias_dtype is not None and ctx.needs_input_grad[3]
-        du, dg, db, dc = K.ln_gelu_bwd(dy if dy.is_contiguous() else dy.contiguous(), u, gamma, beta, mean, rstd, ctx.row_limit,
+        du, dg, db, dc = K.ln_gelu_bwd(dy.contiguous(), u, gamma, beta, mean, rstd, ctx.row_limit,
                                        want_colsum=want_bias, padded=True)
         return du, dg.to(gamma.dtype), db.to(gamma.dtype), (dc.to(ctx.bias_dtype) if want_bias else None), None, None
 
@@ -940,8 +920,8 @@ class _Conv1dCLFn(torch.autograd.Function):
         # ---- dz, in a row-padded allocation when the windowed dX GEMMs will read it ----
         dzp = _padded_base(dy, Lout, Cout) if (act == L.ACT_NONE or grad_is_dz) else None
         if dzp is None:
-            dyc = dy if dy.is_contiguous() else dy.contiguous()
-            dzc = K.act_bwd(dyc, z if z.is_contiguous() else z.contiguous(), act) if (act != L.ACT_NONE and not grad_is_dz) else dyc
+            dyc = dy.contiguous()
+            dzc = K.act_bwd(dyc, z.contiguous(), act) if (act != L.ACT_NONE and not grad_is_dz) else dyc
             if fast:
                 dzp = torch.empty(B, Lout + 2, Cout, dtype=dy.dtype, device=dy.device)
                 dzp[:, 0].zero_()
@@ -959,7 +939,7 @@ class _Conv1dCLFn(torch.autograd.Function):
                 if dx_padded:
                     dx_full[:, 0].zero_()
                     dx_full[:, Lin + 1].zero_()
-                pz = prev_z if prev_z is None or dx_padded else (prev_z if prev_z.is_contiguous() else prev_z.contiguous())
+                pz = prev_z if prev_z is None or dx_padded else prev_z.contiguous()
                 pz_base = _padded_base(prev_z, Lin, Cin) if dx_padded else pz
                 w3 = w_cl.view(Cout, k, Cin)
                 for r in range(stride):
@@ -983,7 +963,7 @@ class _Conv1dCLFn(torch.autograd.Function):
                 dz2 = dz_rows.reshape(B * Lout, Cout) if dzp is None else dzp[:, 1:1 + Lout].reshape(B * Lout, Cout)
                 dcol = torch.empty(B * Lout, k * Cin, dtype=dy.dtype, device=dy.device)
                 K.gemm(dz2, w_cl, dcol, B * Lout, k * Cin, Cout, a_kmajor=1, b_kmajor=0, lda=Cout, ldb=k * Cin, ldc=k * Cin, split_k=1)
-                pzc = prev_z if prev_z is None or prev_z.is_contiguous() else prev_z.contiguous()
+                pzc = prev_z if prev_z is None else prev_z.contiguous()
                 dx = K.col2im1d(dcol, pzc, B, Lin, Lout, Cin, k, stride, pad, L.ACT_GELU if prev_z is not None else 0)
         if ctx.needs_input_grad[1]:
             part = torch.empty(B, Cout, k * Cin, dtype=torch.float32, device=dy.device)
@@ -1053,7 +1033,7 @@ class _PosConvFn(torch.autograd.Function):
         wg = weight.view(groups, cg, cg, k).permute(0, 1, 3, 2).contiguous()  # [g][co][j][ci]
         y = torch.empty(B, T, C, dtype=x.dtype, device=x.device)
         z = torch.empty_like(y)
-        xc = x if x.is_contiguous() else x.contiguous()
+        xc = x.contiguous()
         ml = None if lens is None else torch.clamp(lens.to(torch.int32) + padl, max=T).contiguous()
         K.gemm(xg, wg, y, T, cg, k * cg, a_kmajor=1, b_kmajor=1, lda=cg, ldb=k * cg, ldc=C, batch0=B, batch1=groups,
                sa=(Tp * cg, B * Tp * cg), sb=(0, cg * k * cg), sc=(T * C, cg), bias=bias, sbias=(0, cg), act=L.ACT_GELU,
@@ -1205,12 +1185,12 @@ class _DropoutFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, p, key):
         ctx.p, ctx.key = p, key
-        xc = x if x.is_contiguous() else x.contiguous()
+        xc = x.contiguous()
         return K.dropout(xc, p, key).view(x.shape)
 
     @staticmethod
     def backward(ctx, dy):
-        dc = dy if dy.is_contiguous() else dy.contiguous()
+        dc = dy.contiguous()
         return K.dropout(dc, ctx.p, ctx.key).view(dy.shape), None, None
 
 
@@ -1238,7 +1218,7 @@ class _EmbedPosFn(torch.autograd.Function):
     def backward(ctx, dy):
         (tokens,) = ctx.saved_tensors
         scale, pad_idx, p, key, V, gdt = ctx.cfg
-        dy = dy if dy.is_contiguous() else dy.contiguous()
+        dy = dy.contiguous()
         if V:
             dE = K.embed_bwd(dy, tokens, V, scale, pad_idx, p, key, gdt) if ctx.needs_input_grad[2] else None
             return None, None, dE, None, None, None, None, None, None

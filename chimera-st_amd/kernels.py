@@ -132,6 +132,24 @@ def _2d(t):
     return t
 
 
+def _stamps(live, extent, stat):
+    """(pointer, epoch) of the live-tile stamps `live` = (stamps, epoch) over `extent` rows in 64-row tiles; (NULL, 0) without stamps."""
+    if live is None:
+        return None, 0
+    assert live[0].numel() * 64 >= extent and live[0].dtype == torch.int32
+    STATS[stat] = STATS.get(stat, 0) + 1
+    return live[0].data_ptr(), live[1]
+
+
+def _per_batch(v, batch0, stat):
+    """Pointer of an int32 vector with one entry per batch0 index, or NULL."""
+    if v is None:
+        return None
+    assert v.dtype == torch.int32 and v.numel() == batch0 and v.is_contiguous()
+    STATS[stat] = STATS.get(stat, 0) + 1
+    return v.data_ptr()
+
+
 # ------------------------------------------------------------------------------------------------
 def gemm(A, B, C, M, N, K, *, a_kmajor, b_kmajor, lda, ldb, ldc, bias=None, bias_mode=L.BIAS_COL, act=L.ACT_NONE,
          aux_out=None, ld_aux_out=0, dact=L.ACT_NONE, aux_in=None, ld_aux_in=0, resid=None, ld_resid=0, alpha=1.0,
@@ -182,30 +200,10 @@ def gemm(A, B, C, M, N, K, *, a_kmajor, b_kmajor, lda, ldb, ldc, bias=None, bias
     d.sb0, d.sb1 = sb
     d.sc0, d.sc1 = sc
     d.split_k = split_k
-    if k_live is not None:
-        assert k_live[0].numel() * 64 >= K and k_live[0].dtype == torch.int32
-        STATS["gemm_k_live"] = STATS.get("gemm_k_live", 0) + 1
-        d.k_live, d.k_epoch = k_live[0].data_ptr(), k_live[1]
-    else:
-        d.k_live, d.k_epoch = None, 0
-    if m_live is not None:
-        assert m_live[0].numel() * 64 >= M and m_live[0].dtype == torch.int32
-        d.m_live, d.m_epoch = m_live[0].data_ptr(), m_live[1]
-        STATS["gemm_m_live"] = STATS.get("gemm_m_live", 0) + 1
-    else:
-        d.m_live, d.m_epoch = None, 0
-    if k_len is not None:
-        assert k_len.dtype == torch.int32 and k_len.numel() == batch0 and k_len.is_contiguous()
-        d.k_len = k_len.data_ptr()
-        STATS["gemm_k_len"] = STATS.get("gemm_k_len", 0) + 1
-    else:
-        d.k_len = None
-    if m_len is not None:
-        assert m_len.dtype == torch.int32 and m_len.numel() == batch0 and m_len.is_contiguous()
-        d.m_len = m_len.data_ptr()
-        STATS["gemm_m_len"] = STATS.get("gemm_m_len", 0) + 1
-    else:
-        d.m_len = None
+    d.k_live, d.k_epoch = _stamps(k_live, K, "gemm_k_live")
+    d.m_live, d.m_epoch = _stamps(m_live, M, "gemm_m_live")
+    d.k_len = _per_batch(k_len, batch0, "gemm_k_len")
+    d.m_len = _per_batch(m_len, batch0, "gemm_m_len")
     if colsum is not None:
         assert not a_kmajor and colsum.dtype == A.dtype and colsum.is_contiguous() and colsum.numel() == M * batch0 * batch1
         d.colsum = colsum.data_ptr()
@@ -289,6 +287,22 @@ def next_epoch():
     return _EPOCH[0]
 
 
+def _two_stage(wbytes, outs, defer, launch):
+    """A reduction whose kernel leaves fp32 partials [chunks][len(outs)][cols] in a scratch buffer and whose second stage sums them
+    over the chunks into `outs` ([cols] each).  launch(ws, *output pointers) enqueues the kernel.  Normally the scratch is the shared
+    workspace and the kernel runs the second stage itself; with `defer` inside the deferred mode the scratch is private (the flush
+    reads it after this call has returned), the kernel gets NULL outputs and the second stage is handed to DEFER (order 1 of
+    cst_reduce_multi = the summation order of these kernels' own second stages)."""
+    deferred = bool(defer) and DEFER.on > 0
+    dev = outs[0].device
+    ws = torch.empty(wbytes, dtype=torch.uint8, device=dev) if deferred else workspace(wbytes, dev)
+    launch(ws, *[None if deferred else L.ptr(o) for o in outs])
+    if deferred:
+        n, cols = len(outs), outs[0].numel()
+        for i, o in enumerate(outs):
+            DEFER.push(ws.data_ptr() + 4 * cols * i, o, n * cols, cols, wbytes // (4 * n * cols), ws, order=1)
+
+
 def layernorm_bwd(dy, s, gamma, mean, rstd, dres=None, grad_dtype=torch.float32, want_tiles=False, defer=False):
     """dgamma / dbeta come back in `grad_dtype` (fp32, or the parameter dtype: accumulated in fp32, rounded once).
     want_tiles: also returns (stamps int32 [ceil(rows/64)], epoch) marking the 64-row tiles of dx that are not exactly zero.
@@ -299,26 +313,20 @@ def layernorm_bwd(dy, s, gamma, mean, rstd, dres=None, grad_dtype=torch.float32,
     dx = torch.empty_like(s)
     dg = torch.empty(cols, dtype=grad_dtype, device=s.device)
     db = torch.empty(cols, dtype=grad_dtype, device=s.device)
-    wbytes = lib.cst_layernorm_bwd_workspace(rows, cols)
-    defer = bool(defer) and DEFER.on > 0
-    ws = torch.empty(wbytes, dtype=torch.uint8, device=s.device) if defer else workspace(wbytes, s.device)
-    pg, pb = (None, None) if defer else (L.ptr(dg), L.ptr(db))
-    out = (dx, dg, db)
-    if want_tiles:
-        stamps, epoch = torch.empty((rows + 63) // 64, dtype=torch.int32, device=s.device), next_epoch()
-        L.check(lib.cst_layernorm_bwd_tiles(L.ptr(dy), L.ptr(s), L.ptr(gamma), L.ptr(mean), L.ptr(rstd), L.ptr(dres), L.ptr(dx), pg,
-                                            pb, L.ptr(ws), rows, cols, L.dtype_code(s.dtype), L.dtype_code(grad_dtype),
-                                            L.ptr(stamps), epoch, L.stream_ptr()), "cst_layernorm_bwd_tiles")
-        out = (dx, dg, db, (stamps, epoch))
-    else:
-        L.check(lib.cst_layernorm_bwd(L.ptr(dy), L.ptr(s), L.ptr(gamma), L.ptr(mean), L.ptr(rstd), L.ptr(dres), L.ptr(dx), pg,
-                                      pb, L.ptr(ws), rows, cols, L.dtype_code(s.dtype), L.dtype_code(grad_dtype), L.stream_ptr()),
-                "cst_layernorm_bwd")
-    if defer:  # partials: fp32 [blocks][2][cols]
-        blocks = wbytes // (8 * cols)
-        DEFER.push(ws.data_ptr(), dg, 2 * cols, cols, blocks, ws, order=1)
-        DEFER.push(ws.data_ptr() + 4 * cols, db, 2 * cols, cols, blocks, ws, order=1)
-    return out
+    stamps, epoch = (torch.empty((rows + 63) // 64, dtype=torch.int32, device=s.device), next_epoch()) if want_tiles else (None, 0)
+
+    def launch(ws, pg, pb):
+        if want_tiles:
+            L.check(lib.cst_layernorm_bwd_tiles(L.ptr(dy), L.ptr(s), L.ptr(gamma), L.ptr(mean), L.ptr(rstd), L.ptr(dres), L.ptr(dx), pg,
+                                                pb, L.ptr(ws), rows, cols, L.dtype_code(s.dtype), L.dtype_code(grad_dtype),
+                                                L.ptr(stamps), epoch, L.stream_ptr()), "cst_layernorm_bwd_tiles")
+        else:
+            L.check(lib.cst_layernorm_bwd(L.ptr(dy), L.ptr(s), L.ptr(gamma), L.ptr(mean), L.ptr(rstd), L.ptr(dres), L.ptr(dx), pg,
+                                          pb, L.ptr(ws), rows, cols, L.dtype_code(s.dtype), L.dtype_code(grad_dtype), L.stream_ptr()),
+                    "cst_layernorm_bwd")
+
+    _two_stage(lib.cst_layernorm_bwd_workspace(rows, cols), (dg, db), defer, launch)
+    return (dx, dg, db, (stamps, epoch)) if want_tiles else (dx, dg, db)
 
 
 def _bhtd_strides(t, layout):
@@ -451,12 +459,14 @@ def attn_bwd_fill(d, do, dq, dk, dv, delta, D, layout_q="bt", layout_kv="bt"):
     d._bwd_ws_owner = ws
 
 
-def attn_bwd(do, q, k, v, o, lse, H, D, kpm, causal, scale, layout_q="bt", layout_kv="bt", drop_p=0.0, drop_key=0, kv_len=None):
-    dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+def attn_bwd(do, q, k, v, o, lse, H, D, kpm, causal, scale, layout_q="bt", layout_kv="bt", drop_p=0.0, drop_key=0, kv_len=None, seq=None,
+             grads=None):
+    """grads = (dq, dk, dv): where the gradients go (channel slices of one packed buffer); fresh tensors like q, k, v when None."""
+    dq, dk, dv = grads if grads is not None else (torch.empty_like(q), torch.empty_like(k), torch.empty_like(v))
     delta = torch.empty_like(lse)
-    d = attn_desc(q, k, v, o, lse, H, D, kpm, causal, scale, layout_q, layout_kv, drop_p, drop_key, kv_len)
+    d = attn_desc(q, k, v, o, lse, H, D, kpm, causal, scale, layout_q, layout_kv, drop_p, drop_key, kv_len, seq)
     attn_bwd_fill(d, do, dq, dk, dv, delta, D, layout_q, layout_kv)
-    L.check(L.load().cst_attn_bwd(ctypes.byref(d), L.stream_ptr()), "cst_attn_bwd")
+    attn_bwd_desc(d)
     return dq, dk, dv
 
 
@@ -612,19 +622,17 @@ def colsum(x, out_dtype=torch.float32, live=None, defer=False):
     rows, cols = x.shape
     lib = L.load()
     out = torch.empty(cols, dtype=out_dtype, device=x.device)
-    wbytes = lib.cst_colsum_workspace(rows, cols)
-    defer = bool(defer) and DEFER.on > 0
-    ws = torch.empty(wbytes, dtype=torch.uint8, device=x.device) if defer else workspace(wbytes, x.device)
-    po = None if defer else L.ptr(out)
-    if live is not None:  # (stamps, epoch) of x's 64-row tiles: dead tiles are all zero and skipped
-        assert live[0].numel() * 64 >= rows
-        L.check(lib.cst_colsum_typed_live(L.ptr(x), x.stride(0), po, L.ptr(ws), rows, cols, L.dtype_code(x.dtype),
-                                          L.dtype_code(out_dtype), L.ptr(live[0]), live[1], L.stream_ptr()), "cst_colsum_typed_live")
-    else:
-        L.check(lib.cst_colsum_typed(L.ptr(x), x.stride(0), po, L.ptr(ws), rows, cols, L.dtype_code(x.dtype), L.dtype_code(out_dtype),
-                                     L.stream_ptr()), "cst_colsum_typed")
-    if defer:  # partials: fp32 [chunks][cols], the order of colsum_reduce_kernel = order 1 of cst_reduce_multi
-        DEFER.push(ws.data_ptr(), out, cols, cols, wbytes // (4 * cols), ws, order=1)
+
+    def launch(ws, po):
+        if live is not None:  # (stamps, epoch) of x's 64-row tiles: dead tiles are all zero and skipped
+            assert live[0].numel() * 64 >= rows
+            L.check(lib.cst_colsum_typed_live(L.ptr(x), x.stride(0), po, L.ptr(ws), rows, cols, L.dtype_code(x.dtype),
+                                              L.dtype_code(out_dtype), L.ptr(live[0]), live[1], L.stream_ptr()), "cst_colsum_typed_live")
+        else:
+            L.check(lib.cst_colsum_typed(L.ptr(x), x.stride(0), po, L.ptr(ws), rows, cols, L.dtype_code(x.dtype), L.dtype_code(out_dtype),
+                                         L.stream_ptr()), "cst_colsum_typed")
+
+    _two_stage(lib.cst_colsum_workspace(rows, cols), (out,), defer, launch)
     return out
 
 
@@ -637,14 +645,13 @@ def dropout_colsum(x, p, key, out_dtype=torch.float32, live=None, defer=False):
     lib = L.load()
     xd = torch.empty_like(x)
     out = torch.empty(cols, dtype=out_dtype, device=x.device)
-    wbytes = lib.cst_colsum_workspace(rows, cols)
-    defer = bool(defer) and DEFER.on > 0
-    ws = torch.empty(wbytes, dtype=torch.uint8, device=x.device) if defer else workspace(wbytes, x.device)
-    L.check(lib.cst_dropout_colsum(L.ptr(x), L.ptr(xd), None if defer else L.ptr(out), L.ptr(ws), rows, cols, L.dtype_code(x.dtype),
-                                   L.dtype_code(out_dtype), float(p), int(key) & 0xFFFFFFFF, L.ptr(live[0]) if live is not None else None,
-                                   live[1] if live is not None else 0, L.stream_ptr()), "cst_dropout_colsum")
-    if defer:
-        DEFER.push(ws.data_ptr(), out, cols, cols, wbytes // (4 * cols), ws, order=1)
+
+    def launch(ws, po):
+        L.check(lib.cst_dropout_colsum(L.ptr(x), L.ptr(xd), po, L.ptr(ws), rows, cols, L.dtype_code(x.dtype),
+                                       L.dtype_code(out_dtype), float(p), int(key) & 0xFFFFFFFF, L.ptr(live[0]) if live is not None else None,
+                                       live[1] if live is not None else 0, L.stream_ptr()), "cst_dropout_colsum")
+
+    _two_stage(lib.cst_colsum_workspace(rows, cols), (out,), defer, launch)
     return xd, out
 
 
@@ -702,7 +709,6 @@ def dropout(x, p, key):
 def conv_row_limits(nz_last, conv_spec, samples):
     """int32 [L, 1 + smax, B] live-frame limits of every conv layer from the real frame counts behind the last one (include/cst.h:
     cst_conv_row_limits) — one launch instead of ~15 tiny torch kernels per layer."""
-    import ctypes
     Lc = len(conv_spec)
     ks = (ctypes.c_int32 * Lc)(*[int(c[1]) for c in conv_spec])
     st = (ctypes.c_int32 * Lc)(*[int(c[2]) for c in conv_spec])

@@ -68,7 +68,7 @@ class FlatParamBuffers:
             p.data = self.flat_param[o:o + n].view(p.shape)
             self.grad_views.append(self.flat_grad[o:o + n].view(p.shape))
             p.grad = None
-            # functional._linear_backward writes a weight gradient straight into its slot of the flat buffer (grad_slot below)
+            # functional._dw_gemm writes a weight gradient straight into its slot of the flat buffer (grad_slot below)
             p._cst_grad_slot = (weakref.ref(self), len(self.grad_views) - 1)
             p._cst_grad_claim = 0
         if self.flat_param.is_cuda:

@@ -531,7 +531,7 @@ def test_reducer_with_an_unexpected_arrival_order():
 
 # ---- accumulated updates (update_freq > 1) with weight gradients written straight into the flat buffer (optim.grad_slot) --------------
 class _SlotLinear(torch.autograd.Function):
-    """What functional._linear_backward does on the GPU: the weight gradient goes into the parameter's slot of the flat gradient
+    """What functional._dw_gemm does on the GPU: the weight gradient goes into the parameter's slot of the flat gradient
     buffer when optim.grad_slot hands it out (first micro-batch), otherwise it is an ordinary tensor autograd adds in place."""
 
     @staticmethod

@@ -1062,7 +1062,7 @@ def test_transpose2d_is_exact(K, dt, shape):
 
 
 def test_dx_through_transposed_weight_equals_m_major_read():
-    """functional._linear_backward reads W^T k-major above CST_WT_MIN_ROWS rows; the GEMM accumulates the same products in the same
+    """functional._dx_gemm reads W^T k-major above CST_WT_MIN_ROWS rows; the GEMM accumulates the same products in the same
     K order either way, so dX has the same bits as the m-major read it replaces."""
     import os
     from importlib import import_module
@@ -1183,7 +1183,7 @@ def test_gemm8p_at_the_bench_shape_with_its_epilogues(K):
     y = torch.empty(M, K_, dtype=dt, device="cuda")
     k.gemm(h, w2, y, M, K_, N, a_kmajor=1, b_kmajor=1, lda=N, ldb=N, ldc=K_, bias=b2, resid=res, ld_resid=K_, split_k=1)
     check(y, h.float() @ w2.float().t() + b2.float() + res.float(), dt, "fc2 bias + residual")
-    # dz1 = (dy W2) * GELU'(z1) through the transposed-weight copy (both operands k-major, as functional._FFNFn.backward launches it)
+    # dz1 = (dy W2) * GELU'(z1) through the transposed-weight copy (both operands k-major, as functional._dx_gemm launches it for _FFNFn.backward)
     dy = rnd(M, K_, dt=dt, seed=7)
     w2t = w2.t().contiguous()  # [N, K_] = W2^T: dz1[m, n] = sum_c dy[m, c] W2[c, n]
     dz = torch.empty(M, N, dtype=dt, device="cuda")
@@ -1359,6 +1359,39 @@ def test_deferred_reductions_give_the_gradients_of_the_immediate_route():
         z.float().pow(2).sum().backward()
         assert len(Kk.DEFER.items) == 0
     assert all(torch.isfinite(p.grad.float()).all() for p in params)
+
+
+@pytest.mark.parametrize("M,d,F_,dt", [(304, 64, 136, torch.bfloat16), (304, 64, 136, torch.float32), (4064, 512, 2048, torch.bfloat16)])
+def test_ffn_backward_equals_two_linears_bit_for_bit(M, d, F_, dt):
+    """functional.ffn and linear(linear(x, act="relu")) launch their dX / dW / bias-gradient work through the same helpers: without
+    residual and dropout both hand the same operand bits to the same GEMMs (ReLU' is 0 or 1, so fusing it into the dH GEMM's epilogue
+    rounds nothing differently), hence y and every gradient agree bit for bit — immediately and with the reductions deferred.
+    304 rows: below CST_WT_MIN_ROWS (mn-major W read, no split); 4064 x 512 x 2048: W^T copies, split-K dW with the bias gradient as
+    its colsum (the shape of test_deferred_reductions_give_the_gradients_of_the_immediate_route)."""
+    from importlib import import_module
+    load_pkg()
+    CF = import_module("chimera-st_amd.functional")
+    Kk = import_module("chimera-st_amd.kernels")
+    torch.manual_seed(3)
+    w1, w2 = (torch.nn.Parameter((torch.randn(o, i, device="cuda") * i ** -0.5).to(dt)) for o, i in ((F_, d), (d, F_)))
+    b1, b2 = (torch.nn.Parameter(torch.randn(n, device="cuda").to(dt)) for n in (F_, d))
+    x = torch.randn(M, d, device="cuda").to(dt).requires_grad_(True)
+    dy = torch.randn(M, d, device="cuda").to(dt)
+    leaves = (x, w1, b1, w2, b2)
+
+    def run(fn, defer):
+        for p in leaves:
+            p.grad = None
+        with Kk.deferred_reductions(defer):
+            y = fn()
+            y.backward(dy)
+        return [y.detach()] + [p.grad.clone() for p in leaves]
+
+    for defer in (False, True):
+        fused = run(lambda: CF.ffn(x, w1, b1, w2, b2, "relu"), defer)
+        split = run(lambda: CF.linear(CF.linear(x, w1, b1, act="relu"), w2, b2), defer)
+        for name, a, b in zip(("y", "dx", "dw1", "db1", "dw2", "db2"), fused, split):
+            assert torch.isfinite(a.float()).all() and torch.equal(a, b), "%s differs (deferred: %s)" % (name, defer)
 
 
 @pytest.mark.parametrize("M,N,K_,epi", [(31760, 768, 3072, "resid"), (31760, 768, 768, "bias"), (31760, 2304, 768, "bias"), (24100, 768, 1024, "dact"),
