@@ -215,8 +215,8 @@ def corpus_bleu(hyps, refs, max_n=4):
     return 100.0 * bp * math.exp(logp)
 
 
-def generate_main(argv=None):
-    argv = list(sys.argv[1:] if argv is None else argv)
+def generate_parser():
+    """The options of fairseq_generate.py (a subset of fairseq-generate's, same names and defaults)."""
     p = argparse.ArgumentParser(allow_abbrev=False)
     p.add_argument("data")
     p.add_argument("--path", required=True, help="checkpoint(s), colon separated: several files are decoded as an ensemble "
@@ -236,6 +236,8 @@ def generate_main(argv=None):
     p.add_argument("--unkpen", type=float, default=0.0)
     p.add_argument("--temperature", type=float, default=1.0)
     p.add_argument("--unnormalized", action="store_true")
+    p.add_argument("--no-repeat-ngram-size", type=int, default=0, help="no n-gram of this size may occur twice in a hypothesis (0 = off)")
+    p.add_argument("--prefix-size", type=int, default=0, help="force the first K target tokens of every sentence to the reference's")
     p.add_argument("--remove-bpe", "--post-process", nargs="?", const="@@ ", default=None, dest="post_process")
     p.add_argument("--scoring", default="bleu")
     p.add_argument("--results-path", default=None)
@@ -243,7 +245,12 @@ def generate_main(argv=None):
     p.add_argument("--bf16", action="store_true")
     p.add_argument("--seed", type=int, default=1)
     p.add_argument("--quiet", action="store_true")
-    args, ignored = p.parse_known_args(argv)
+    return p
+
+
+def generate_main(argv=None):
+    argv = list(sys.argv[1:] if argv is None else argv)
+    args, ignored = generate_parser().parse_known_args(argv)
     limit_host_threads()
     overrides = {"data": args.data, "config_yaml": args.config_yaml, "max_source_positions": args.max_source_positions,
                  "max_target_positions": args.max_target_positions}
@@ -279,7 +286,12 @@ def generate_main(argv=None):
         # inputs [B, T, F] take the model's storage dtype
         src = src.to("cuda", dtype) if (src.dim() == 3 and src.is_floating_point()) else src.cuda()
         s = {"net_input": {"src_tokens": src, "src_lengths": ni["src_lengths"].cuda()}}
-        results = task.inference_step(gen, models, s)
+        prefix = None
+        if args.prefix_size > 0:  # fairseq_cli/generate.py:189-191
+            if sample.get("target") is None:
+                raise ValueError("--prefix-size needs the references of the subset (no target in this batch)")
+            prefix = sample["target"][:, :args.prefix_size].cuda()
+        results = task.inference_step(gen, models, s, prefix_tokens=prefix)
         for i, sid in enumerate(sample["id"].tolist()):
             ref = tgt_dict.string(sample["target"][i]) if sample.get("target") is not None else None
             h = results[i][0]

@@ -23,6 +23,8 @@ struct BeamP {
   int64_t* tokens; float* scores; int32_t* anc;
   uint8_t* cands_to_ignore; uint8_t* finished; int32_t* nfinal; int32_t* num_remaining;
   int64_t* fin_tokens; float* fin_pos; float* fin_score; int32_t* fin_len;
+  int ngram, prefix_len;          // --no-repeat-ngram-size (0 = off, else >= 2) / width of prefix_tokens (0 = off)
+  const int64_t* prefix_tokens;   // [bsz][prefix_len], padded with `pad`
 };
 
 __global__ void beam_init_kernel(BeamP p, int32_t* ticket) {
@@ -78,7 +80,34 @@ constexpr int BEAM_MAX = 20, KMAX_ALL = 2 * BEAM_MAX;
 // second re-reads the rows (L2 hits) and folds a_n = l_n / T - lse_n into a per-element running (max, sum) over the members, so the
 // exp never sees more than a_n - max_n a_n <= 0 and an element that is -inf in every member stays -inf.  A member whose row has no
 // finite lse (NaN logits, an all -inf row) makes the whole row NaN like the reference's stack + logsumexp; (b) and (c) are shared.
+//
+// CON (the constraints of --prefix-size / --no-repeat-ngram-size, compiled in only where one of them is on):
+//   prefix (sequence_generator.py:336-347, _prefix_tokens :543-575): at steps s < prefix_len, s < max_len every candidate of the
+//   sentence's rows but token t = prefix_tokens[sentence][s] becomes -inf (t == pad: unconstrained); the min-len mask is suspended for
+//   the WHOLE batch at those steps (the reference's `elif`); t == eos: the reference copies tokens, scores and log-probabilities of
+//   the sentence's first beam to all its beams — here every row of that sentence READS the first row (logits, cumulative score,
+//   tokens) and beam_merge_kernel takes the first row as the parent.
+//   n-gram blocking (_no_repeat_ngram :734-767, applied after the prefix / min-len masks, :368-369): with last = tk[s+2-n .. s], every
+//   i in [0, s+1-n] with tk[i .. i+n-2] == last bans token tk[i+n-1].  (The reference also scans the pad tail of its buffer; for
+//   n >= 2 that only ever bans pad, which is -inf already.)  The workgroup's threads test the positions i in parallel and set the
+//   banned tokens' bits in an LDS bitmap, which is consulted where the candidate values are formed: one LDS word per 16-byte vector.
 constexpr int ENS_MAX = 8;
+
+// step s forces prefix tokens (for the sentences whose entry is not pad) and suspends the min-len mask
+__device__ __forceinline__ bool prefix_step(const BeamP& p, int s) { return s < p.prefix_len && s < p.max_len; }
+
+// calls ban(token) for every token that would complete an n-gram the row already holds; tk = the row's tokens tk[0 .. s]
+template <typename F>
+__device__ __forceinline__ void ngram_banned(const int64_t* tk, int s, int n, int tid, int nth, F&& ban) {
+  const int first = s + 2 - n;  // last = tk[first .. s], n - 1 tokens
+  if (n < 2 || first < 0) return;
+  for (int i = tid; i <= s + 1 - n; i += nth) {
+    bool eq = true;
+    for (int k = 0; k < n - 1; ++k) eq = eq && tk[i + k] == tk[first + k];
+    if (eq) ban(tk[i + n - 1]);
+  }
+}
+
 struct EnsP {
   int n;
   float temperature, log_n;
@@ -93,7 +122,7 @@ __device__ __forceinline__ void lse_merge(float& mx, float& sum, float m2, float
   mx = M;
 }
 
-template <typename T, int NV, bool ENS>
+template <typename T, int NV, bool ENS, bool CON>
 __device__ __forceinline__ void beam_row_topk_body(const BeamP& p, const EnsP* ep, float* cand_val, int32_t* cand_tok) {
   constexpr int VEC = DT<T>::VEC, NTH = 512, NW = NTH / 64;
   const int s = *p.step;
@@ -103,8 +132,29 @@ __device__ __forceinline__ void beam_row_topk_body(const BeamP& p, const EnsP* e
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int V = p.vocab, K = 2 * p.beam, L1 = p.max_len + 1;
   const int nvec = (V + VEC - 1) / VEC;
-  const T* lg = reinterpret_cast<const T*>(p.logits) + (int64_t)h * p.ld_logits;
   const float NEG = -INFINITY;
+  // CON: hs = the row whose logits, score and tokens this row reads (the sentence's first row where the prefix holds eos), pt = the
+  // forced token (-1: none), pfx = a prefix step (no min-len mask), ban = the bitmap of n-gram-banned tokens
+  int hs = h, pt = -1;
+  bool pfx = false;
+  __shared__ uint32_t ban[CON ? NV * NTH * VEC / 32 : 1];
+  if constexpr (CON) {
+    pfx = prefix_step(p, s);
+    if (pfx) {
+      const int64_t t = p.prefix_tokens[(int64_t)(h / p.beam) * p.prefix_len + s];
+      if (t != p.pad) pt = (int)t;
+      if (t == p.eos) hs = h - r;
+    }
+#pragma unroll
+    for (int i = 0; i < NV * VEC / 32 + 1; ++i)
+      if (tid + i * NTH < NV * NTH * VEC / 32) ban[tid + i * NTH] = 0u;
+    __syncthreads();
+    const int64_t* tk = p.tokens + ((int64_t)(s & 1) * p.bsz * p.beam + hs) * (p.max_len + 2);
+    ngram_banned(tk, s, p.ngram, tid, NTH, [&](int64_t v) {
+      if (v >= 0 && v < V) atomicOr(&ban[v >> 5], 1u << (v & 31));
+    });  // (visible after the barriers of the statistics pass below)
+  }
+  const T* lg = reinterpret_cast<const T*>(p.logits) + (int64_t)hs * p.ld_logits;
   __shared__ float red_m[NW], red_s[NW];
   __shared__ float sh_lse;
   __shared__ float w_val[NW * KMAX_ALL];
@@ -118,7 +168,7 @@ __device__ __forceinline__ void beam_row_topk_body(const BeamP& p, const EnsP* e
     __shared__ float ens_m[ENS_MAX][NW], ens_s[ENS_MAX][NW], ens_lse[ENS_MAX];
     float t[NV][VEC];
     auto load_member = [&](int n) {  // member n's row / T; -inf behind the vocabulary
-      const T* ln = reinterpret_cast<const T*>(e.logits[n]) + (int64_t)h * p.ld_logits;
+      const T* ln = reinterpret_cast<const T*>(e.logits[n]) + (int64_t)hs * p.ld_logits;
 #pragma unroll
       for (int i = 0; i < NV; ++i) {
         const int vi = tid + i * NTH;
@@ -227,11 +277,13 @@ __device__ __forceinline__ void beam_row_topk_body(const BeamP& p, const EnsP* e
   __syncthreads();
   lse = sh_lse;
   }
-  const float prev = s > 0 ? (p.scores + (int64_t)(s & 1) * p.bsz * p.beam * L1)[(int64_t)h * L1 + s - 1] : 0.0f;
+  const float prev = s > 0 ? (p.scores + (int64_t)(s & 1) * p.bsz * p.beam * L1)[(int64_t)hs * L1 + s - 1] : 0.0f;
   // candidate values replace the logits in the registers
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const int vi = tid + i * NTH;
+    uint32_t bw = 0u;  // the vector's VEC tokens share one word of the bitmap
+    if constexpr (CON) bw = ban[(vi * VEC) >> 5];
 #pragma unroll
     for (int e = 0; e < VEC; ++e) {
       const int v = vi * VEC + e;
@@ -240,7 +292,13 @@ __device__ __forceinline__ void beam_row_topk_body(const BeamP& p, const EnsP* e
       if (v == p.pad) val = NEG;                       // never select pad                        (:313)
       if (v == p.unk) val -= p.unk_penalty;            //                                         (:314)
       if (s >= p.max_len && v != p.eos) val = NEG;     // force eos at max length                 (:317-319)
+      if constexpr (CON) {
+        if (pt >= 0 && v != pt) val = NEG;             // forced prefix token                     (:336-344, :543-553)
+        if (!pfx && s < p.min_len && v == p.eos) val = NEG;  // (`elif`: not at a prefix step)   (:345-347)
+        if ((bw >> (v & 31)) & 1u) val = NEG;          // the token would repeat an n-gram        (:368-369)
+      } else {
       if (s < p.min_len && v == p.eos) val = NEG;      // minimum length constraint               (:329-331)
+      }
       if (s > 0) val += prev;                          // search.py:125
       x[i][e] = (vi < nvec && v < V) ? val : NAN;      // NaN = not a candidate (never compares better)
     }
@@ -344,28 +402,52 @@ __device__ __forceinline__ void beam_row_topk_body(const BeamP& p, const EnsP* e
   }
 }
 
-template <typename T, int NV>
+template <typename T, int NV, bool CON>
 __global__ __launch_bounds__(512) void beam_row_topk_kernel(BeamP p, float* cand_val, int32_t* cand_tok) {
-  beam_row_topk_body<T, NV, false>(p, nullptr, cand_val, cand_tok);
+  beam_row_topk_body<T, NV, false, CON>(p, nullptr, cand_val, cand_tok);
 }
-template <typename T, int NV>
+template <typename T, int NV, bool CON>
 __global__ __launch_bounds__(512) void beam_row_topk_ens_kernel(BeamP p, EnsP e, float* cand_val, int32_t* cand_tok) {
-  beam_row_topk_body<T, NV, true>(p, &e, cand_val, cand_tok);
+  beam_row_topk_body<T, NV, true, CON>(p, &e, cand_val, cand_tok);
 }
 
 // generic-width variant: rows too long for registers are re-read from memory (L2-resident) on every scan
 // (ENS: the members' statistics as in the register kernel; every scan recombines the N rows element by element)
-template <typename T, bool ENS>
+// (CON: the vocabulary has no bound here, so the LDS bitmap is a FILTER of BANW * 32 bits indexed by the token's low bits; a set bit is
+//  confirmed against the row's tokens — banned tokens are few, so almost every element costs the one LDS read.  Every scan consults it.)
+template <typename T, bool ENS, bool CON>
 __device__ __forceinline__ void beam_row_topk_wide_body(const BeamP& p, const EnsP* ep, float* cand_val, int32_t* cand_tok) {
-  constexpr int NTH = 512, NW = NTH / 64;
+  constexpr int NTH = 512, NW = NTH / 64, BANW = 256;
   const int s = *p.step;
   if (s > p.max_len) return;
   const int h = blockIdx.x, r = h % p.beam;
   if (s == 0 && r != 0) return;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int V = p.vocab, K = 2 * p.beam, L1 = p.max_len + 1;
-  const T* lg = reinterpret_cast<const T*>(p.logits) + (int64_t)h * p.ld_logits;
   const float NEG = -INFINITY;
+  int hs = h, pt = -1;  // as in the register kernel
+  bool pfx = false;
+  __shared__ uint32_t ban[CON ? BANW : 1];
+  const int64_t* tk = nullptr;
+  if constexpr (CON) {
+    pfx = prefix_step(p, s);
+    if (pfx) {
+      const int64_t t = p.prefix_tokens[(int64_t)(h / p.beam) * p.prefix_len + s];
+      if (t != p.pad) pt = (int)t;
+      if (t == p.eos) hs = h - r;
+    }
+    if (tid < BANW) ban[tid] = 0u;
+    __syncthreads();
+    tk = p.tokens + ((int64_t)(s & 1) * p.bsz * p.beam + hs) * (p.max_len + 2);
+    ngram_banned(tk, s, p.ngram, tid, NTH, [&](int64_t v) { atomicOr(&ban[(v >> 5) & (BANW - 1)], 1u << (v & 31)); });
+  }
+  auto banned = [&](int v) -> bool {
+    if (!((ban[(v >> 5) & (BANW - 1)] >> (v & 31)) & 1u)) return false;
+    bool hit = false;
+    ngram_banned(tk, s, p.ngram, 0, 1, [&](int64_t b) { hit = hit || b == v; });
+    return hit;
+  };
+  const T* lg = reinterpret_cast<const T*>(p.logits) + (int64_t)hs * p.ld_logits;
   __shared__ float red_m[NW], red_s[NW], wv[NW];
   __shared__ int wi[NW];
   __shared__ float sh_lse;
@@ -376,7 +458,7 @@ __device__ __forceinline__ void beam_row_topk_wide_body(const BeamP& p, const En
   bool bad = false;
   if constexpr (ENS) {
     for (int n = 0; n < ep->n; ++n) {
-      const T* ln = reinterpret_cast<const T*>(ep->logits[n]) + (int64_t)h * p.ld_logits;
+      const T* ln = reinterpret_cast<const T*>(ep->logits[n]) + (int64_t)hs * p.ld_logits;
       float mx = NEG, sum = 0.0f;
       bool nan = false;
       for (int v = tid; v < V; v += NTH) {
@@ -431,7 +513,7 @@ __device__ __forceinline__ void beam_row_topk_wide_body(const BeamP& p, const En
     if constexpr (ENS) {
       float m = NEG, a = 0.0f;
       for (int n = 0; n < ep->n; ++n)
-        lse_merge(m, a, DT<T>::ld(reinterpret_cast<const T*>(ep->logits[n]) + (int64_t)h * p.ld_logits + v) / ep->temperature - ens_lse[n], 1.0f);
+        lse_merge(m, a, DT<T>::ld(reinterpret_cast<const T*>(ep->logits[n]) + (int64_t)hs * p.ld_logits + v) / ep->temperature - ens_lse[n], 1.0f);
       return bad ? NAN : (m == NEG ? NEG : m + (logf(a) - ep->log_n));
     } else {
       return DT<T>::ld(lg + v) * p.inv_temperature - lse;
@@ -441,7 +523,7 @@ __device__ __forceinline__ void beam_row_topk_wide_body(const BeamP& p, const En
     if (ep->lprobs_out)
       for (int v = tid; v < V; v += NTH) ep->lprobs_out[(int64_t)h * p.ld_logits + v] = lprob(v);
   }
-  const float prev = s > 0 ? (p.scores + (int64_t)(s & 1) * p.bsz * p.beam * L1)[(int64_t)h * L1 + s - 1] : 0.0f;
+  const float prev = s > 0 ? (p.scores + (int64_t)(s & 1) * p.bsz * p.beam * L1)[(int64_t)hs * L1 + s - 1] : 0.0f;
   float tv = INFINITY, bv;
   int ti = -1, bi;
   auto rescan = [&]() {
@@ -452,7 +534,13 @@ __device__ __forceinline__ void beam_row_topk_wide_body(const BeamP& p, const En
       if (v == p.pad) val = NEG;
       if (v == p.unk) val -= p.unk_penalty;
       if (s >= p.max_len && v != p.eos) val = NEG;
+      if constexpr (CON) {  // prefix, else min-len, then the n-gram ban: the order of the register kernel
+        if (pt >= 0 && v != pt) val = NEG;
+        if (!pfx && s < p.min_len && v == p.eos) val = NEG;
+        if (val != NEG && banned(v)) val = NEG;
+      } else {
       if (s < p.min_len && v == p.eos) val = NEG;
+      }
       if (s > 0) val += prev;
       const bool open = val < tv || (val == tv && v > ti);
       if (open && cand_better(val, v, bv, bi)) { bv = val; bi = v; }
@@ -483,13 +571,13 @@ __device__ __forceinline__ void beam_row_topk_wide_body(const BeamP& p, const En
   }
 }
 
-template <typename T>
+template <typename T, bool CON>
 __global__ __launch_bounds__(512) void beam_row_topk_wide_kernel(BeamP p, float* cand_val, int32_t* cand_tok) {
-  beam_row_topk_wide_body<T, false>(p, nullptr, cand_val, cand_tok);
+  beam_row_topk_wide_body<T, false, CON>(p, nullptr, cand_val, cand_tok);
 }
-template <typename T>
+template <typename T, bool CON>
 __global__ __launch_bounds__(512) void beam_row_topk_wide_ens_kernel(BeamP p, EnsP e, float* cand_val, int32_t* cand_tok) {
-  beam_row_topk_wide_body<T, true>(p, &e, cand_val, cand_tok);
+  beam_row_topk_wide_body<T, true, CON>(p, &e, cand_val, cand_tok);
 }
 
 // ---- beam search step, kernel 2 of 2: one workgroup per SENTENCE -------------------------------------------------------------
@@ -497,6 +585,9 @@ __global__ __launch_bounds__(512) void beam_row_topk_wide_ens_kernel(BeamP p, En
 // beam*V + token, ties to the smaller flat index), then (d) the eos / finalize / active-hypothesis bookkeeping of
 // sequence_generator.py:340-499 and finalize_hypos :575-696, (e) the token / score / ancestry rows of the next step written
 // into the other half of the ping-pong buffers; the last workgroup to finish advances the step counter.
+// PFX (a prefix is given): where the sentence's prefix token of this step is eos, its rows all searched the FIRST row's distribution
+// (see CON above), so that row is the parent of every candidate: `beam` identical hypotheses are finalised, as in the reference.
+template <bool PFX>
 __global__ __launch_bounds__(256) void beam_merge_kernel(BeamP p, const float* cand_val, const int32_t* cand_tok, int32_t* ticket) {
   const int s = *p.step;
   const int sent = blockIdx.x, tid = threadIdx.x;
@@ -517,6 +608,8 @@ __global__ __launch_bounds__(256) void beam_merge_kernel(BeamP p, const float* c
   __shared__ int c_tok[KMAX_ALL], c_beam[KMAX_ALL], c_em[KMAX_ALL];
   __shared__ int act[BEAM_MAX], rec_k[BEAM_MAX], rec_r[BEAM_MAX], n_rec;
   __shared__ int ign[BEAM_MAX], ign_new[BEAM_MAX];
+  bool first_row_parent = false;
+  if constexpr (PFX) first_row_parent = prefix_step(p, s) && p.prefix_tokens[(int64_t)sent * p.prefix_len + s] == p.eos;
   if (s <= p.max_len) {
     for (int i = tid; i < rows * K; i += blockDim.x) {
       l_val[i] = cand_val[(int64_t)sent * beam * K + i];
@@ -535,7 +628,7 @@ __global__ __launch_bounds__(256) void beam_merge_kernel(BeamP p, const float* c
         const float vo = l_val[o];
         rank += (vo > v || (vo == v && o < i)) ? 1 : 0;   // lists are sorted within a row, so o < i orders equal values by (row, position)
       }
-      if (rank < K) { c_score[rank] = v; c_tok[rank] = l_tok[i]; c_beam[rank] = r; }
+      if (rank < K) { c_score[rank] = v; c_tok[rank] = l_tok[i]; c_beam[rank] = first_row_parent ? 0 : r; }
     }
     __syncthreads();
     if (tid == 0) {
@@ -930,6 +1023,7 @@ int to_params(const cst_beam_desc* d, BeamP& p) {
   p.step = d->step; p.tokens = d->tokens; p.scores = d->scores; p.anc = d->anc;
   p.cands_to_ignore = d->cands_to_ignore; p.finished = d->finished; p.nfinal = d->nfinal; p.num_remaining = d->num_remaining;
   p.fin_tokens = d->fin_tokens; p.fin_pos = d->fin_pos; p.fin_score = d->fin_score; p.fin_len = d->fin_len;
+  p.ngram = 0; p.prefix_len = 0; p.prefix_tokens = nullptr;  // cst_beam_step sets them
   return CST_OK;
 }
 
@@ -1161,6 +1255,17 @@ int cst_beam_step(const cst_beam_desc* d, cst_stream stream) {
   CST_REQUIRE(d->ld_logits % vec == 0 && d->ld_logits >= cst_ceil_div(d->vocab, vec) * vec && ((uintptr_t)d->logits % 16) == 0,
               "cst_beam_step: logits rows must be 16-byte aligned and padded to a multiple of %lld elements", (long long)vec);
   CST_REQUIRE(d->workspace != nullptr && ((uintptr_t)d->workspace % 16) == 0, "cst_beam_step: workspace of cst_beam_workspace() bytes required");
+  // constraints (ABI 10): both off in a zero-filled tail -> the kernels without them
+  CST_REQUIRE(d->no_repeat_ngram == 0 || (d->no_repeat_ngram >= 2 && d->no_repeat_ngram <= INT_MAX),
+              "cst_beam_step: no_repeat_ngram %lld (0 = off, else >= 2: 1 would ban the initial eos and no hypothesis could finish)",
+              (long long)d->no_repeat_ngram);
+  CST_REQUIRE(d->prefix_len >= 0 && d->prefix_len <= d->max_len, "cst_beam_step: prefix_len %lld outside [0, max_len %lld]",
+              (long long)d->prefix_len, (long long)d->max_len);
+  CST_REQUIRE(d->prefix_len == 0 || d->prefix_tokens != nullptr, "cst_beam_step: prefix_len %lld without prefix_tokens", (long long)d->prefix_len);
+  p.ngram = (int)d->no_repeat_ngram;
+  p.prefix_len = (int)d->prefix_len;
+  p.prefix_tokens = d->prefix_len > 0 ? d->prefix_tokens : nullptr;
+  const bool con = p.ngram > 0 || p.prefix_len > 0;
   // checkpoint ensembles: members >= 2 (0 and 1 both mean the single matrix `logits`, today's kernels with today's arguments)
   CST_REQUIRE(d->members >= 0 && d->members <= ENS_MAX, "cst_beam_step: %lld ensemble members (at most %d)", (long long)d->members, ENS_MAX);
   EnsP e;
@@ -1184,19 +1289,23 @@ int cst_beam_step(const cst_beam_desc* d, cst_stream stream) {
   {
     CstProfScope prof(CST_K_ELEMENTWISE, s, 0.0, (double)rows * p.vocab * cst_dtype_size(d->dtype) * (ens ? 2 * e.n : 1));
     const int64_t nvec = cst_ceil_div(d->vocab, vec), per_thread = cst_ceil_div(nvec, 512);
-#define CST_TOPK(T, NV) hipLaunchKernelGGL((beam_row_topk_kernel<T, NV>), dim3((unsigned)rows), dim3(512), 0, s, p, cand_val, cand_tok)
-#define CST_TOPK_T(T) do { if (per_thread <= 1) CST_TOPK(T, 1); else if (per_thread <= 3) CST_TOPK(T, 3); else if (per_thread <= 5) CST_TOPK(T, 5); \
-                            else hipLaunchKernelGGL((beam_row_topk_wide_kernel<T>), dim3((unsigned)rows), dim3(512), 0, s, p, cand_val, cand_tok); } while (0)
-#define CST_TOPK_E(T, NV) hipLaunchKernelGGL((beam_row_topk_ens_kernel<T, NV>), dim3((unsigned)rows), dim3(512), 0, s, p, e, cand_val, cand_tok)
-#define CST_TOPK_ET(T) do { if (per_thread <= 1) CST_TOPK_E(T, 1); else if (per_thread <= 3) CST_TOPK_E(T, 3); else if (per_thread <= 5) CST_TOPK_E(T, 5); \
-                            else hipLaunchKernelGGL((beam_row_topk_wide_ens_kernel<T>), dim3((unsigned)rows), dim3(512), 0, s, p, e, cand_val, cand_tok); } while (0)
-    if (ens) { if (d->dtype == CST_BF16) CST_TOPK_ET(bf16_t); else CST_TOPK_ET(float); }
-    else if (d->dtype == CST_BF16) CST_TOPK_T(bf16_t); else CST_TOPK_T(float);
+#define CST_TOPK(T, NV, C) hipLaunchKernelGGL((beam_row_topk_kernel<T, NV, C>), dim3((unsigned)rows), dim3(512), 0, s, p, cand_val, cand_tok)
+#define CST_TOPK_T(T, C) do { if (per_thread <= 1) CST_TOPK(T, 1, C); else if (per_thread <= 3) CST_TOPK(T, 3, C); else if (per_thread <= 5) CST_TOPK(T, 5, C); \
+                              else hipLaunchKernelGGL((beam_row_topk_wide_kernel<T, C>), dim3((unsigned)rows), dim3(512), 0, s, p, cand_val, cand_tok); } while (0)
+#define CST_TOPK_E(T, NV, C) hipLaunchKernelGGL((beam_row_topk_ens_kernel<T, NV, C>), dim3((unsigned)rows), dim3(512), 0, s, p, e, cand_val, cand_tok)
+#define CST_TOPK_ET(T, C) do { if (per_thread <= 1) CST_TOPK_E(T, 1, C); else if (per_thread <= 3) CST_TOPK_E(T, 3, C); else if (per_thread <= 5) CST_TOPK_E(T, 5, C); \
+                               else hipLaunchKernelGGL((beam_row_topk_wide_ens_kernel<T, C>), dim3((unsigned)rows), dim3(512), 0, s, p, e, cand_val, cand_tok); } while (0)
+    // (the constraints are a template flag: with both off the step launches the instantiations it always did)
+#define CST_TOPK_ALL(C) do { if (ens) { if (d->dtype == CST_BF16) CST_TOPK_ET(bf16_t, C); else CST_TOPK_ET(float, C); } \
+                             else if (d->dtype == CST_BF16) CST_TOPK_T(bf16_t, C); else CST_TOPK_T(float, C); } while (0)
+    if (con) CST_TOPK_ALL(true); else CST_TOPK_ALL(false);
+#undef CST_TOPK_ALL
 #undef CST_TOPK_ET
 #undef CST_TOPK_E
 #undef CST_TOPK_T
 #undef CST_TOPK
-    hipLaunchKernelGGL(beam_merge_kernel, dim3(p.bsz), dim3(256), 0, s, p, (const float*)cand_val, (const int32_t*)cand_tok, ticket);
+    if (p.prefix_len > 0) hipLaunchKernelGGL(beam_merge_kernel<true>, dim3(p.bsz), dim3(256), 0, s, p, (const float*)cand_val, (const int32_t*)cand_tok, ticket);
+    else hipLaunchKernelGGL(beam_merge_kernel<false>, dim3(p.bsz), dim3(256), 0, s, p, (const float*)cand_val, (const int32_t*)cand_tok, ticket);
   }
   return cst_check_launch("cst_beam_step");
 }

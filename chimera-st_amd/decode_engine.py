@@ -29,7 +29,7 @@ from .optim import PARAM_EPOCH
 
 class BeamDecodeEngine:
     def __init__(self, decoder, tgt_dict, beam_size, max_len, min_len=1, normalize_scores=True, len_penalty=1.0,
-                 unk_penalty=0.0, temperature=1.0, use_graph=True, poll=8, cross_kernel=None, lanes=None):
+                 unk_penalty=0.0, temperature=1.0, use_graph=True, poll=8, cross_kernel=None, lanes=None, no_repeat_ngram_size=0):
         # a checkpoint ensemble (--path a.pt:b.pt:c.pt) is a LIST of decoders: every member keeps its own packed weights, K/V caches,
         # encoder K/V and logits buffer; the beam state (tokens / scores / ancestry, step counter, finalized hypotheses) is shared —
         # all members follow the same hypotheses, so one ancestry table serves every member's append-only caches
@@ -42,6 +42,9 @@ class BeamDecodeEngine:
         self.normalize_scores, self.len_penalty = bool(normalize_scores), float(len_penalty)
         self.unk_penalty, self.temperature = float(unk_penalty), float(temperature)
         self.use_graph, self.poll = use_graph, max(1, int(poll))
+        # --no-repeat-ngram-size: a parameter of cst_beam_step's row kernel (0 = off: the kernels without the constraint code)
+        self.no_repeat_ngram_size = int(no_repeat_ngram_size)
+        assert self.no_repeat_ngram_size == 0 or self.no_repeat_ngram_size >= 2, "no_repeat_ngram_size is 0 (off) or at least 2"
         # cross attention per step: "flash" = cst_attn_fwd with batch = sentence and the beam rows as the query axis (37 us per
         # layer at 32 x beam 5 x 750 source positions, bf16); "flash_hm" = the same kernel over head-major K/V (contiguous per-head
         # streams: no faster, 0.811 vs 0.812 ms per step); "shared" = cst_dec_cross_attn (VALU kernel, one pass with online
@@ -189,11 +192,13 @@ class BeamDecodeEngine:
             proj=z(bsz * S, C), kpm=z(bsz, S, dt=torch.uint8) if has_mask else None,
             gemm_ws=z(8 * bbsz * C * 4 if bbsz <= 256 else 0, dt=torch.uint8))  # split-K partials of the fc2 projection (own buffer: captured)
 
-    def _alloc(self, lane, bsz, S, dtype, device, has_mask):
-        """S / has_mask: one value per member (members may differ in encoder output length)."""
+    def _alloc(self, lane, bsz, S, dtype, device, has_mask, prefix_len=0):
+        """S / has_mask: one value per member (members may differ in encoder output length).  prefix_len and no_repeat_ngram_size are
+        kernel parameters baked into the captured graph, so they are part of the state key; the prefix TOKENS live in a buffer the
+        state owns (st["prefix"]), which every call overwrites: a replayed graph reads the new call's prefix."""
         S = tuple(S) if isinstance(S, (list, tuple)) else (S,) * len(self.decs)
         has_mask = tuple(has_mask) if isinstance(has_mask, (list, tuple)) else (has_mask,) * len(self.decs)
-        key = (lane, bsz, S, dtype, device, has_mask)
+        key = (lane, bsz, S, dtype, device, has_mask, prefix_len, self.no_repeat_ngram_size)
         st = self._state.get(key)
         if st is not None:
             return st
@@ -229,6 +234,10 @@ class BeamDecodeEngine:
         d.fin_tokens, d.fin_pos, d.fin_score, d.fin_len = (st[k].data_ptr() for k in ("fin_tokens", "fin_pos", "fin_score", "fin_len"))
         st["beam_ws"] = torch.zeros(L.load().cst_beam_workspace(bsz, beam), dtype=torch.uint8, device=device)
         d.workspace = st["beam_ws"].data_ptr()
+        d.no_repeat_ngram = self.no_repeat_ngram_size
+        st["prefix"] = torch.full((bsz, prefix_len), self.pad, dtype=torch.int64, device=device) if prefix_len > 0 else None
+        if prefix_len > 0:
+            d.prefix_tokens, d.prefix_len = st["prefix"].data_ptr(), prefix_len
         st["desc"] = d
         self._state[key] = st
         return st
@@ -358,10 +367,14 @@ class BeamDecodeEngine:
 
     # ------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def generate(self, encoder_out, bsz):
+    def generate(self, encoder_out, bsz, prefix_tokens=None):
         """encoder_out: EncoderOut with encoder_out [S, B, C] (T x B x C view) and encoder_padding_mask [B, S] or None — for an
         ensemble a list with one EncoderOut per member (each member's own encoder; lengths S and widths may differ).
+        prefix_tokens: None or int64 [bsz, K] padded with pad, K <= max_len: the tokens forced at the first K steps (--prefix-size);
+        it is copied into the engine's own buffer (the caller's tensor is never captured).
         Returns the reference's `finalized` structure (list over sentences of hypothesis dicts, best first)."""
+        prefix_len = 0 if prefix_tokens is None else int(prefix_tokens.shape[1])
+        assert prefix_tokens is None or (prefix_tokens.dim() == 2 and prefix_tokens.shape[0] == bsz and prefix_len <= self.max_len)
         eouts = [encoder_out] if hasattr(encoder_out, "encoder_out") else list(encoder_out)  # (an EncoderOut is itself a tuple)
         assert len(eouts) == len(self.decs), "one encoder output per ensemble member"
         encs = [e.encoder_out for e in eouts]
@@ -374,7 +387,7 @@ class BeamDecodeEngine:
         pk = self._pack(dtype, device)
         lanes = min(self.lanes, bsz)
         bounds = [(bsz * i // lanes, bsz * (i + 1) // lanes) for i in range(lanes)]
-        cfg = (tuple(b1 - b0 for b0, b1 in bounds), S, dtype, device, has_mask)
+        cfg = (tuple(b1 - b0 for b0, b1 in bounds), S, dtype, device, has_mask, prefix_len)
         if cfg != self._cfg:
             self._state.clear()  # one resident configuration (the caches are the large buffers)
             self._cfg = cfg
@@ -390,7 +403,9 @@ class BeamDecodeEngine:
             if stream is not main:
                 stream.wait_stream(main)
             with torch.cuda.stream(stream):
-                st = self._alloc(i, b1 - b0, S, dtype, device, has_mask)
+                st = self._alloc(i, b1 - b0, S, dtype, device, has_mask, prefix_len)
+                if prefix_len > 0:  # the lane's sentences' prefixes, into the buffer the (captured) beam step reads
+                    st["prefix"].copy_(prefix_tokens[b0:b1].to(device=device, dtype=torch.int64))
                 done = self._begin(st, pk, [e[b0:b1] for e in encb], [m[b0:b1] if m is not None else None for m in masks], b1 - b0)
             runs.append(dict(stream=stream, st=st, bsz=b1 - b0, steps=done, remaining=b1 - b0))
         while any(r["steps"] < total and r["remaining"] > 0 for r in runs):

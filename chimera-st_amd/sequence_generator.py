@@ -2,7 +2,9 @@
 finalize_hypos :575-696, EnsembleModel.forward_encoder/forward_decoder :800-868) and fairseq/search.py BeamSearch.step
 (:109-144), for one model or a checkpoint ensemble (`--path a.pt:b.pt:c.pt`: the members' next-token distributions are
 averaged at every step).  Decoder steps run through the incremental-state path of the HIP modules (K/V caches kept
-batch-major [B*beam, T, C]; single-query fused attention).
+batch-major [B*beam, T, C]; single-query fused attention).  The constraints `no_repeat_ngram_size` (_no_repeat_ngram :734-767) and
+`prefix_tokens` (_prefix_tokens :543-575) run inside the beam-step kernel on the engine and as tensor operations on the device
+in the host loop (the reference copies the token matrix to the host every step and keys Python dictionaries by strings).
 
 Differences that do not change results: finished sentences are masked out instead of being removed from the batch
 (the reference shrinks the batch, :427-463 — an optimisation only; every sentence's search is independent)."""
@@ -52,7 +54,12 @@ class SequenceGenerator:
         self.max_len_a, self.max_len_b, self.min_len = max_len_a, max_len_b, min_len
         self.normalize_scores, self.len_penalty, self.unk_penalty = normalize_scores, len_penalty, unk_penalty
         self.temperature = temperature
-        assert temperature > 0 and not match_source_len and no_repeat_ngram_size == 0
+        assert temperature > 0 and not match_source_len
+        if no_repeat_ngram_size < 0 or no_repeat_ngram_size == 1:
+            raise ValueError("no_repeat_ngram_size must be 0 (off) or at least 2, got %d: with 1 the initial eos of every hypothesis is "
+                             "itself a banned 1-gram, so eos can never be emitted and no hypothesis can finish (the reference dies "
+                             "with a bare AssertionError there)" % no_repeat_ngram_size)
+        self.no_repeat_ngram_size = int(no_repeat_ngram_size)
         self.search = BeamSearch(tgt_dict) if search_strategy is None else search_strategy
         # fused=True (default): the device-resident loop of decode_engine.py (one captured HIP graph per step, no per-step host
         # sync); fused=False: the module-by-module mirror of the reference loop below (same kernels, host-driven) — kept as the
@@ -65,8 +72,40 @@ class SequenceGenerator:
 
     @torch.no_grad()
     def generate(self, models, sample, prefix_tokens=None, **kwargs):
-        assert prefix_tokens is None
-        return self._generate(sample)
+        return self._generate(sample, prefix_tokens=prefix_tokens)
+
+    def _check_prefix(self, prefix_tokens, bsz, max_len):
+        if prefix_tokens.dim() != 2 or prefix_tokens.size(0) != bsz:
+            raise ValueError("prefix_tokens must be [batch %d, width], got %s" % (bsz, tuple(prefix_tokens.shape)))
+        if prefix_tokens.size(1) > max_len:
+            raise ValueError("prefix_tokens is %d tokens wide, the step limit max_len is %d" % (prefix_tokens.size(1), max_len))
+        first = prefix_tokens[:, 0]
+        if bool((first.eq(self.eos) | first.eq(self.pad)).any()):
+            raise ValueError("a row of prefix_tokens starts with eos or pad: every sentence needs at least one real prefix token")
+
+    def _ban_repeated_ngrams(self, tokens, lprobs, step):
+        """_no_repeat_ngram (:734-767) as tensor operations: with last = tokens[:, step+2-n : step+1], every window
+        tokens[:, i : i+n-1] (i <= step+1-n) equal to it makes tokens[:, i+n-1] -inf.  (The reference also scans the pad tail of the
+        buffer; for n >= 2 that only ever bans pad.)"""
+        n = self.no_repeat_ngram_size
+        if step + 1 - n < 0:
+            return lprobs
+        last = tokens[:, step + 2 - n:step + 1]
+        windows = tokens[:, :step].unfold(1, n - 1, 1)                       # [rows, step+2-n, n-1]
+        match = windows.eq(last.unsqueeze(1)).all(dim=-1)
+        follow = tokens[:, n - 1:step + 1]                                   # the token after each window
+        zero = torch.zeros((), dtype=lprobs.dtype, device=lprobs.device)
+        return lprobs.scatter_add(1, follow, torch.where(match, zero - math.inf, zero))  # x + 0 = x; x + -inf = -inf in any order
+
+    def _force_prefix(self, step, lprobs, scores, tokens, prefix_tokens, beam_size):
+        """_prefix_tokens (:543-575): rows whose prefix token t is not pad keep only t; where t is eos, the sentence's first beam is
+        copied over its other beams (tokens, scores, lprobs)."""
+        t = prefix_tokens[:, step].repeat_interleave(beam_size).unsqueeze(1)
+        only_t = torch.full_like(lprobs, -math.inf).scatter(1, t, lprobs.gather(1, t))
+        lprobs = torch.where(t.ne(self.pad), only_t, lprobs)
+        rows = torch.arange(lprobs.size(0), device=lprobs.device)
+        src = torch.where(t.squeeze(1).eq(self.eos), rows - rows % beam_size, rows)
+        return lprobs[src], tokens[src], scores[src]
 
     def _forward_decoder(self, tokens, encoder_outs, incremental_states):
         """sequence_generator.py:806-868: per member the last-step logits / temperature -> fp32 log-softmax; an ensemble averages the
@@ -82,7 +121,7 @@ class SequenceGenerator:
             return log_probs[0]
         return torch.logsumexp(torch.stack(log_probs, dim=0), dim=0) - math.log(len(log_probs))
 
-    def _generate(self, sample):
+    def _generate(self, sample, prefix_tokens=None):
         net_input = sample["net_input"]
         src_tokens = net_input["src_tokens"]
         bsz, src_len = src_tokens.size()[:2]
@@ -90,6 +129,11 @@ class SequenceGenerator:
         device = src_tokens.device
         max_len = min(int(self.max_len_a * src_len + self.max_len_b), min(m.max_decoder_positions() for m in self.models) - 1)  # :796-797
         assert self.min_len <= max_len
+        if prefix_tokens is not None:
+            prefix_tokens = prefix_tokens.to(device=device, dtype=torch.long)
+            self._check_prefix(prefix_tokens, bsz, max_len)
+            if prefix_tokens.size(1) == 0:
+                prefix_tokens = None
         encoder_outs = [m.encoder.forward_torchscript(net_input) for m in self.models]
         if self.fused:
             from .decode_engine import BeamDecodeEngine
@@ -98,8 +142,9 @@ class SequenceGenerator:
                     decs = [m.decoder for m in self.models]
                     self._engine = BeamDecodeEngine(decs if len(decs) > 1 else decs[0], self.tgt_dict, beam_size, max_len, self.min_len,
                                                     self.normalize_scores, self.len_penalty, self.unk_penalty, self.temperature,
-                                                    use_graph=self.use_graph, cross_kernel=self.cross_kernel)
-                return self._engine.generate(encoder_outs if len(encoder_outs) > 1 else encoder_outs[0], bsz)
+                                                    use_graph=self.use_graph, cross_kernel=self.cross_kernel,
+                                                    no_repeat_ngram_size=self.no_repeat_ngram_size)
+                return self._engine.generate(encoder_outs if len(encoder_outs) > 1 else encoder_outs[0], bsz, prefix_tokens=prefix_tokens)
         new_order = torch.arange(bsz, device=device).view(-1, 1).repeat(1, beam_size).view(-1)
         encoder_outs = [m.encoder.reorder_encoder_out(e, new_order) for m, e in zip(self.models, encoder_outs)]
         incremental_states: List[Dict[str, Dict[str, Optional[Tensor]]]] = [{} for _ in self.models]
@@ -128,8 +173,12 @@ class SequenceGenerator:
             if step >= max_len:
                 lprobs[:, :self.eos] = -math.inf
                 lprobs[:, self.eos + 1:] = -math.inf
-            if step < self.min_len:
+            if prefix_tokens is not None and step < prefix_tokens.size(1) and step < max_len:
+                lprobs, tokens, scores = self._force_prefix(step, lprobs, scores, tokens, prefix_tokens, beam_size)
+            elif step < self.min_len:  # (not at a prefix step of the batch)
                 lprobs[:, self.eos] = -math.inf
+            if self.no_repeat_ngram_size > 0:
+                lprobs = self._ban_repeated_ngrams(tokens, lprobs, step)
             cand_scores, cand_indices, cand_beams = self.search.step(
                 step, lprobs.view(bsz, -1, self.vocab_size), scores.view(bsz, beam_size, -1)[:, :, :step])
             cand_bbsz_idx = cand_beams.add(bbsz_offsets)

@@ -104,7 +104,8 @@ class FairseqTask:
             models, self.target_dictionary, beam_size=getattr(args, "beam", 5), max_len_a=getattr(args, "max_len_a", 0),
             max_len_b=getattr(args, "max_len_b", 200), min_len=getattr(args, "min_len", 1),
             normalize_scores=(not getattr(args, "unnormalized", False)), len_penalty=getattr(args, "lenpen", 1),
-            unk_penalty=getattr(args, "unkpen", 0), temperature=getattr(args, "temperature", 1.0))
+            unk_penalty=getattr(args, "unkpen", 0), temperature=getattr(args, "temperature", 1.0),
+            no_repeat_ngram_size=getattr(args, "no_repeat_ngram_size", 0))
 
 
 def _load_dict(args, default_size):

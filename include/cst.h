@@ -31,9 +31,10 @@ extern "C" {
 /* Bumps on any change of a signature or a descriptor layout (3: cst_gemm_desc.m_len, cst_attn_desc.seq_offsets, workspaces of the
  * fixed-order reductions; 4: cst_attn_desc.kpm_bits / bwd_ws, the separable attention-dropout mask; 5: cst_gemm_desc.colsum;
  * 6: cst_dec_ln_q_cross_attn; 7: cst_fbank_desc, cst_fbank, cst_fbank_workspace_bytes; 8: cst_conv0_ln_gelu_fwd / _bwd,
- * cst_ln_gelu_fwd / _bwd and their workspaces; 9: cst_beam_desc.members / logits_n / lprobs_out — checkpoint ensembles).
+ * cst_ln_gelu_fwd / _bwd and their workspaces; 9: cst_beam_desc.members / logits_n / lprobs_out — checkpoint ensembles;
+ * 10: cst_beam_desc.no_repeat_ngram / prefix_tokens / prefix_len — n-gram blocking and forced prefixes).
  * cst_version() returns the value the library was built with; chimera-st_amd/lib.py refuses a mismatch. */
-#define CST_ABI_VERSION 9
+#define CST_ABI_VERSION 10
 
 typedef enum { CST_F32 = 0, CST_BF16 = 1 } cst_dtype;
 
@@ -521,6 +522,18 @@ int cst_adam_step(float* master, float* exp_avg, float* exp_avg_sq, const void* 
  *   per-element maximum over the members is taken out before the exp; -inf in every member stays -inf; a member whose row
  *   has NaN logits or no finite entry makes the row NaN -> -inf, as the reference's stack + logsumexp does).  The
  *   temperature divides every member's logits BEFORE its softmax.  Masks, scores, top-2*beam and bookkeeping are unchanged.
+ *   Constraints (ABI 10; both are off in a zero-filled descriptor tail, and a step with both off launches the kernels without them):
+ *   no_repeat_ngram = n >= 2 (--no-repeat-ngram-size, sequence_generator.py:_no_repeat_ngram :734-767): with tk[0 .. s] the row's tokens
+ *   (tk[0] = eos) and last = tk[s+2-n .. s], every i in [0, s+1-n] with tk[i .. i+n-2] == last makes token tk[i+n-1] -inf.  It is applied
+ *   after the NaN / pad / unk / max-len / prefix / min-len masks and before the cumulative score is added, inside the row kernel (an LDS
+ *   bitmap built by the workgroup; no extra launch).  n == 1 or n < 0: CST_ERR_BAD_ARG (1 would ban the initial eos for good).
+ *   prefix_tokens int64[bsz][prefix_len], padded with `pad` (--prefix-size, :336-347 and _prefix_tokens :543-575): at steps
+ *   s < prefix_len, s < max_len, with t = prefix_tokens[sentence][s]: t != pad -> every candidate of the sentence's rows except t becomes
+ *   -inf (t keeps its log-probability after the unk penalty); t == pad -> unconstrained; at those steps the min-len mask is applied to NO
+ *   row of the batch (the reference's `elif`); t == eos -> the sentence's rows all read the logits, cumulative score and tokens of its
+ *   FIRST row and that row is the parent of every candidate (the reference copies the first beam over the others): `beam` identical
+ *   hypotheses are finalised.  The buffer is read at every step, so a captured step sees the contents of the moment it runs.
+ *   prefix_len > 0 with a null pointer, prefix_len < 0 or > max_len: CST_ERR_BAD_ARG.
  * ------------------------------------------------------------------------------------------ */
 typedef struct {
   int dtype;                         /* storage type of logits */
@@ -537,6 +550,9 @@ typedef struct {
   int64_t members;                   /* checkpoint ensemble (ABI 9): 0 or 1 = the single matrix `logits`; N >= 2 = `logits` and logits_n[0 .. N-2] */
   const void* logits_n[7];           /* members 1 .. N-1: same rows, vocab, ld_logits, dtype and alignment as `logits` */
   float* lprobs_out;                 /* optional, members >= 2: fp32 [bbsz][ld_logits], the combined log-probabilities before the masks */
+  int64_t no_repeat_ngram;           /* ABI 10: 0 = off, else n >= 2 */
+  const int64_t* prefix_tokens;      /* ABI 10: device [bsz][prefix_len], padded with `pad`; read when prefix_len > 0 */
+  int64_t prefix_len;                /* ABI 10: 0 = off, at most max_len */
 } cst_beam_desc;
 int64_t cst_beam_workspace(int64_t bsz, int64_t beam);
 int cst_beam_init(const cst_beam_desc* d, cst_stream stream);

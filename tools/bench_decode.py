@@ -3,6 +3,7 @@
 6 decoder layers, 10 000-way tied vocabulary), filter-bank input, beam 5, incremental-state decode, 1 x MI355X, bf16.
 
   python tools/bench_decode.py [--batch 32] [--frames 3000] [--beam 5] [--max-len 200] [--reps 3] [--mirror] [--ensemble N]
+                               [--no-repeat-ngram-size N]
 
 Prints one JSON line: utterances/s and generated tokens/s of the device-resident loop (decode_engine.py: one captured HIP
 graph per step), the per-step time, the encoder time, and — with --mirror — the same numbers for the host-driven
@@ -37,6 +38,7 @@ def main():
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--cross-kernel", default="flash", choices=["flash", "flash_hm", "shared"])
     ap.add_argument("--ensemble", type=int, default=1, help="decode N independently seeded copies of the model as an ensemble")
+    ap.add_argument("--no-repeat-ngram-size", type=int, default=0, help="decode with n-gram blocking (0 = off)")
     ap.add_argument("--profile", action="store_true", help="per-class GPU time of one eager decode loop (hipEvent pairs)")
     args = ap.parse_args()
 
@@ -85,13 +87,16 @@ def main():
         enc_s = (time.perf_counter() - t0) / args.reps
 
     fused = SG(models, task.target_dictionary, beam_size=args.beam, max_len_a=0, max_len_b=args.max_len, use_graph=not args.no_graph,
-               cross_kernel=args.cross_kernel)
+               cross_kernel=args.cross_kernel, no_repeat_ngram_size=args.no_repeat_ngram_size)
     t_f, ntok = timed(fused)
     steps = args.max_len + 1
     out = {"metric": "decode utterances/sec, s2t_transformer_l beam 5, 1 MI355X", "config": {"arch": args.arch, "batch": args.batch,
            "beam": args.beam, "max_frames": args.frames, "max_len": args.max_len, "dtype": args.dtype, "graph": not args.no_graph},
            "utterances_per_s": args.batch / t_f, "tokens_per_s": ntok / t_f, "best_hyp_tokens": ntok, "s_per_batch": t_f,
            "encoder_s": enc_s, "ms_per_step": (t_f - enc_s) / steps * 1e3, "hyp_rows_per_step": args.batch * args.beam}
+    if args.no_repeat_ngram_size:
+        out["config"]["no_repeat_ngram_size"] = args.no_repeat_ngram_size
+        out["nodes_per_step"] = fused._engine.nodes_per_step(dt, args.batch * args.beam)
     if args.ensemble > 1:
         out["models"] = args.ensemble
         out["nodes_per_step"] = fused._engine.nodes_per_step(dt, args.batch * args.beam)
