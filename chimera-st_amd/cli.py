@@ -238,6 +238,12 @@ def generate_parser():
     p.add_argument("--unnormalized", action="store_true")
     p.add_argument("--no-repeat-ngram-size", type=int, default=0, help="no n-gram of this size may occur twice in a hypothesis (0 = off)")
     p.add_argument("--prefix-size", type=int, default=0, help="force the first K target tokens of every sentence to the reference's")
+    p.add_argument("--sampling", action="store_true", help="draw every token from the model's distribution instead of beam search: each of "
+                   "the --beam hypotheses of a sentence is an independent sample (--seed selects the stream of draws)")
+    p.add_argument("--sampling-topk", type=int, default=-1, help="draw among the k most probable tokens only (requires --sampling)")
+    p.add_argument("--sampling-topp", type=float, default=-1.0, help="draw from the smallest set of tokens with probability mass p "
+                   "(nucleus sampling; requires --sampling, wins over --sampling-topk)")
+    p.add_argument("--nbest", type=int, default=1, help="hypotheses printed per sentence (at most --beam)")
     p.add_argument("--remove-bpe", "--post-process", nargs="?", const="@@ ", default=None, dest="post_process")
     p.add_argument("--scoring", default="bleu")
     p.add_argument("--results-path", default=None)
@@ -248,9 +254,21 @@ def generate_parser():
     return p
 
 
+def check_generate_args(args):
+    """The combinations fairseq-generate refuses (fairseq_cli/generate.py:49-54, fairseq_task.py:343-344), before anything is loaded."""
+    if args.nbest < 1 or args.nbest > args.beam:
+        raise ValueError("--nbest %d must be between 1 and --beam %d" % (args.nbest, args.beam))
+    if args.sampling_topk >= 0 and not args.sampling:
+        raise ValueError("--sampling-topk requires --sampling")
+    if args.sampling_topp >= 0 and not args.sampling:
+        raise ValueError("--sampling-topp requires --sampling")
+    return args
+
+
 def generate_main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     args, ignored = generate_parser().parse_known_args(argv)
+    check_generate_args(args)
     limit_host_threads()
     overrides = {"data": args.data, "config_yaml": args.config_yaml, "max_source_positions": args.max_source_positions,
                  "max_target_positions": args.max_target_positions}
@@ -294,14 +312,16 @@ def generate_main(argv=None):
         results = task.inference_step(gen, models, s, prefix_tokens=prefix)
         for i, sid in enumerate(sample["id"].tolist()):
             ref = tgt_dict.string(sample["target"][i]) if sample.get("target") is not None else None
-            h = results[i][0]
-            hyp = tgt_dict.string(h["tokens"].cpu())
-            if not args.quiet:
-                if ref is not None:
-                    print("T-%d\t%s" % (sid, ref), file=out)
-                print("H-%d\t%.6f\t%s" % (sid, float(h["score"]) / math.log(2), hyp), file=out)
-                print("D-%d\t%.6f\t%s" % (sid, float(h["score"]) / math.log(2), detok(hyp)), file=out)
-                print("P-%d\t%s" % (sid, " ".join("%.4f" % (x / math.log(2)) for x in h["positional_scores"].tolist())), file=out)
+            if not args.quiet and ref is not None:
+                print("T-%d\t%s" % (sid, ref), file=out)
+            for j, hj in enumerate(results[i][:args.nbest]):  # fairseq_cli/generate.py: hypos[i][:args.nbest]
+                hyp_j = tgt_dict.string(hj["tokens"].cpu())
+                if not args.quiet:
+                    print("H-%d\t%.6f\t%s" % (sid, float(hj["score"]) / math.log(2), hyp_j), file=out)
+                    print("D-%d\t%.6f\t%s" % (sid, float(hj["score"]) / math.log(2), detok(hyp_j)), file=out)
+                    print("P-%d\t%s" % (sid, " ".join("%.4f" % (x / math.log(2)) for x in hj["positional_scores"].tolist())), file=out)
+                if j == 0:  # BLEU and the token count come from the best hypothesis
+                    h, hyp = hj, hyp_j
             hyps.append(detok(hyp))
             refs.append(detok(ref) if ref is not None else "")
             ntok += len(h["tokens"])
@@ -310,6 +330,7 @@ def generate_main(argv=None):
     dt = time.time() - t0
     summary = {"event": "generate", "subset": args.gen_subset, "sentences": nsent, "tokens": ntok, "seconds": dt,
                "sentences_per_s": nsent / max(dt, 1e-9), "tokens_per_s": ntok / max(dt, 1e-9), "beam": args.beam, "models": len(models),
+               "sampling": bool(args.sampling), "nbest": args.nbest, "seed": args.seed,
                "bleu4_whitespace": corpus_bleu(hyps, refs) if any(refs) else None, "ignored_flags": ignored}
     print(json.dumps(summary), file=out, flush=True)
     if out is not sys.stdout:

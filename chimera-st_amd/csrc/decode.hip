@@ -25,6 +25,9 @@ struct BeamP {
   int64_t* fin_tokens; float* fin_pos; float* fin_score; int32_t* fin_len;
   int ngram, prefix_len;          // --no-repeat-ngram-size (0 = off, else >= 2) / width of prefix_tokens (0 = off)
   const int64_t* prefix_tokens;   // [bsz][prefix_len], padded with `pad`
+  int sample_topk;                // --sampling-topk (0 = off); read by the sampling kernels only
+  float sample_topp;              // --sampling-topp (<= 0 = off; wins over top-k)
+  const uint32_t* sample_key;     // device [1]: the 32-bit key of this call's draws, read at every step
 };
 
 __global__ void beam_init_kernel(BeamP p, int32_t* ticket) {
@@ -122,7 +125,231 @@ __device__ __forceinline__ void lse_merge(float& mx, float& sum, float m2, float
   mx = M;
 }
 
-template <typename T, int NV, bool ENS, bool CON>
+// ---- sampling (search.py Sampling.step :676-742): stage (c) of the row kernel when cst_beam_desc.sampling is set -------------------
+// In: x = the row's masked log-probabilities in registers (NaN = not a candidate), BEFORE the cumulative score is added.  With
+// q_v = exp(x_v) (not renormalised after the masks, like the reference's multinomial input):
+//   cut   top-p (p > 0, wins): in the total order (value desc, token asc — cand_better) element j is kept iff the mass in front of it is
+//         < p (_sample_topp :630-673: cumsum.lt(p) plus one more element; whole mass < p: everything).  Found WITHOUT sorting: values map
+//         to order-preserving 32-bit keys, and 32 block-wide sums S(c) = sum of q over {key >= c} build, bit by bit, the largest c with
+//         S(c) >= p — the key of the last kept value.  Elements that share that key are kept in token order while the mass in front of
+//         them stays < p: the number m of them follows from S(> key) and their common q, and where m is less than their number a second
+//         bisection (15 block-wide counts, over the token id) finds the m-th of them.
+//         top-k (k > 0): the same bisection over COUNTS: the largest c with #{key >= c} >= k; ties at the k-th value in token order.
+//   draw  u = (cst_drop_bits32(key, cst_drop_key2(key), idx) >> 8) * 2^-24, idx = (sentence * beam + slot) * (max_len + 1) + step, key read
+//         from device memory; the token is the smallest kept v whose inclusive kept mass in VOCABULARY order exceeds u * Z (Z = kept
+//         mass).  Vocabulary order is (vector i, thread, element): per i a wave-wide inclusive scan of the threads' sums by shuffles, the
+//         wave totals through LDS, added by every thread in the fixed order (i, wave); each thread then walks its own elements.  The
+//         block-wide minimum over the threads' first hits is the draw; if rounding lets no element exceed u * Z (u * Z within an ulp of
+//         Z), the last kept element with q > 0 is taken.  A step-0 row draws `beam` tokens (slots 0 .. beam-1, with replacement), any
+//         other row one (its own slot).  Output: (x_v + cumulative score, v) at cand[sentence * beam + slot]; a row without mass
+//         writes (-inf, pad) — what the selection kernel writes for a missing candidate.
+// Every sum has a fixed order (no floating-point atomics): thread-serial over (i, element), a shuffle tree, then the waves in wave
+// order.  LONGEST ADDITION CHAIN of a sum that decides the cut or the draw: 64 (NV * VEC = 40 in a thread + 6 shuffle levels + 8 waves
+// for the masses; 7 + 6 for a wave total, NV * 8 = 40 wave totals, + 1 + 8 inside the thread for an inclusive kept mass).
+__device__ __forceinline__ uint32_t samp_key(float v) {  // order-preserving: larger value <-> larger key; NaN (not a candidate) -> 0
+  const uint32_t b = __float_as_uint(v + 0.0f);           // (-0 -> +0)
+  return v != v ? 0u : ((b & 0x80000000u) ? ~b : (b | 0x80000000u));
+}
+__device__ __forceinline__ float samp_unkey(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+
+template <int NV, int VEC>
+__device__ __forceinline__ void beam_row_sample_tail(const BeamP& p, float (&x)[NV][VEC], int s, int h, float prev, float* cand_val,
+                                                     int32_t* cand_tok) {
+  constexpr int NTH = 512, NW = NTH / 64;
+  static_assert(NV * NTH * VEC <= 32768, "the tie bisection walks 15 bits of the token id");
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  __shared__ float sm_f[2][NW];
+  __shared__ int sm_i[2][NW];
+  __shared__ float sm_tot[NV][NW];
+  __shared__ int sm_pick[BEAM_MAX][NW], sm_last[NW];
+  int par = 0;
+  // block-wide sums whose result is the same bit pattern in every thread (one barrier each: the two LDS rows alternate)
+  auto block_sum_f = [&](float v) -> float {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    if (lane == 0) sm_f[par][wave] = v;
+    __syncthreads();
+    float t = sm_f[par][0];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) t += sm_f[par][w];
+    par ^= 1;
+    return t;
+  };
+  auto block_sum_i = [&](int v) -> int {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    if (lane == 0) sm_i[par][wave] = v;
+    __syncthreads();
+    int t = sm_i[par][0];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) t += sm_i[par][w];
+    par ^= 1;
+    return t;
+  };
+  float q[NV][VEC];
+#pragma unroll
+  for (int i = 0; i < NV; ++i)
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) q[i][e] = x[i][e] == x[i][e] ? expf(x[i][e]) : 0.0f;
+  const bool topp = p.sample_topp > 0.0f, topk = !topp && p.sample_topk > 0;
+  if (topp || topk) {
+    const float pp = p.sample_topp;
+    const int kk = p.sample_topk;
+    uint32_t F = 0u;  // the largest c with S(c) >= p / #(c) >= k: the key of the last kept value (0: everything is kept)
+    for (int b = 31; b >= 0; --b) {
+      const uint32_t c = F | (1u << b);
+      bool ge;
+      if (topp) {
+        float part = 0.0f;
+#pragma unroll
+        for (int i = 0; i < NV; ++i)
+#pragma unroll
+          for (int e = 0; e < VEC; ++e) part += samp_key(x[i][e]) >= c ? q[i][e] : 0.0f;
+        ge = block_sum_f(part) >= pp;
+      } else {
+        int part = 0;
+#pragma unroll
+        for (int i = 0; i < NV; ++i)
+#pragma unroll
+          for (int e = 0; e < VEC; ++e) part += samp_key(x[i][e]) >= c ? 1 : 0;
+        ge = block_sum_i(part) >= kk;
+      }
+      if (ge) F = c;
+    }
+    // the elements that share the key F: n_tie of them, the first m in token order are kept
+    int tie_part = 0, gt_cnt = 0;
+    float gt_part = 0.0f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i)
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) {
+        const uint32_t k = samp_key(x[i][e]);
+        tie_part += k == F ? 1 : 0;
+        gt_cnt += k > F ? 1 : 0;
+        gt_part += k > F ? q[i][e] : 0.0f;
+      }
+    const int n_tie = block_sum_i(tie_part);
+    int m = n_tie;
+    if (F != 0u) {
+      if (topp) {
+#pragma clang fp contract(off)
+        const float s_gt = block_sum_f(gt_part), qs = expf(samp_unkey(F));  // (the same expf of the same value as the elements' own q)
+        if (qs > 0.0f && n_tie > 1) {
+          // the smallest j with s_gt + j * qs >= p: ties 0 .. j-1 have less than p in front of them
+          float jf = ceilf((pp - s_gt) / qs);
+          jf = fminf(fmaxf(jf, 1.0f), (float)n_tie);
+          int j = (int)jf;
+          while (j > 1 && s_gt + (float)(j - 1) * qs >= pp) --j;
+          while (j < n_tie && s_gt + (float)j * qs < pp) ++j;
+          m = j < n_tie ? j : n_tie;
+        }
+      } else {
+        m = kk - block_sum_i(gt_cnt);
+        m = m < n_tie ? m : n_tie;
+      }
+    }
+    int cut = INT_MAX;  // ties are kept up to this token id
+    if (m < n_tie) {    // (block-uniform) the m-th tie in token order: the largest c with #{ties with token < c} < m
+      cut = 0;
+      for (int b = 14; b >= 0; --b) {
+        const int c = cut | (1 << b);
+        int part = 0;
+#pragma unroll
+        for (int i = 0; i < NV; ++i)
+#pragma unroll
+          for (int e = 0; e < VEC; ++e) part += (samp_key(x[i][e]) == F && (tid + i * NTH) * VEC + e < c) ? 1 : 0;
+        if (block_sum_i(part) < m) cut = c;
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < NV; ++i)
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) {
+        const uint32_t k = samp_key(x[i][e]);
+        const bool kept = k > F || (k == F && (tid + i * NTH) * VEC + e <= cut);
+        q[i][e] = kept ? q[i][e] : 0.0f;
+      }
+  }
+  // inclusive kept mass in vocabulary order
+  float base[NV], exc[NV];
+  int last = -1;  // this thread's last element with kept mass
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    float t = q[i][0];
+#pragma unroll
+    for (int e = 1; e < VEC; ++e) t += q[i][e];
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) last = q[i][e] > 0.0f ? (tid + i * NTH) * VEC + e : last;
+    float inc = t;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const float n = __shfl_up(inc, o, 64);
+      if (lane >= o) inc += n;
+    }
+    const float up = __shfl_up(inc, 1, 64);
+    exc[i] = lane == 0 ? 0.0f : up;
+    if (lane == 63) sm_tot[i][wave] = inc;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { const int l2 = __shfl_xor(last, o, 64); last = l2 > last ? l2 : last; }
+  if (lane == 0) sm_last[wave] = last;
+  __syncthreads();
+  float run = 0.0f;
+#pragma unroll
+  for (int i = 0; i < NV; ++i)
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+      if (w == wave) base[i] = run;
+      run += sm_tot[i][w];
+    }
+  const float Z = run;
+  const int nd = s == 0 ? p.beam : 1;
+  const uint32_t key = *p.sample_key, key2 = cst_drop_key2(key);
+  const int L1 = p.max_len + 1;
+  for (int d = 0; d < nd; ++d) {
+    const float u = (float)(cst_drop_bits32(key, key2, (uint32_t)((h + d) * L1 + s)) >> 8) * 5.9604644775390625e-8f;
+    const float target = u * Z;
+    int pick = INT_MAX;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      float c = base[i] + exc[i];
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) {
+        c += q[i][e];
+        const bool hit = (q[i][e] > 0.0f) & (c > target) & (pick == INT_MAX);
+        pick = hit ? (tid + i * NTH) * VEC + e : pick;
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { const int p2 = __shfl_xor(pick, o, 64); pick = p2 < pick ? p2 : pick; }
+    if (lane == 0) sm_pick[d][wave] = pick;
+  }
+  __syncthreads();
+  int fall = sm_last[0];
+#pragma unroll
+  for (int w = 1; w < NW; ++w) fall = sm_last[w] > fall ? sm_last[w] : fall;
+  for (int d = 0; d < nd; ++d) {
+    int tok = sm_pick[d][0];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) tok = sm_pick[d][w] < tok ? sm_pick[d][w] : tok;
+    if (tok == INT_MAX) tok = fall;
+    if (!(Z > 0.0f) || tok < 0) {  // no mass: a missing candidate
+      if (tid == 0) { cand_val[h + d] = -INFINITY; cand_tok[h + d] = p.pad; }
+      continue;
+    }
+    // the thread that holds the token writes it
+#pragma unroll
+    for (int i = 0; i < NV; ++i)
+#pragma unroll
+      for (int e = 0; e < VEC; ++e)
+        if ((tid + i * NTH) * VEC + e == tok) {
+          cand_val[h + d] = s > 0 ? x[i][e] + prev : x[i][e];
+          cand_tok[h + d] = tok;
+        }
+  }
+}
+
+template <typename T, int NV, bool ENS, bool CON, bool SAMP = false>
 __device__ __forceinline__ void beam_row_topk_body(const BeamP& p, const EnsP* ep, float* cand_val, int32_t* cand_tok) {
   constexpr int VEC = DT<T>::VEC, NTH = 512, NW = NTH / 64;
   const int s = *p.step;
@@ -299,9 +526,15 @@ __device__ __forceinline__ void beam_row_topk_body(const BeamP& p, const EnsP* e
       } else {
       if (s < p.min_len && v == p.eos) val = NEG;      // minimum length constraint               (:329-331)
       }
+      if constexpr (!SAMP) {
       if (s > 0) val += prev;                          // search.py:125
+      }
       x[i][e] = (vi < nvec && v < V) ? val : NAN;      // NaN = not a candidate (never compares better)
     }
+  }
+  if constexpr (SAMP) {  // x holds the masked log-probabilities WITHOUT the cumulative score: (c) is a draw, not a selection
+    beam_row_sample_tail<NV, VEC>(p, x, s, h, prev, cand_val, cand_tok);
+    return;
   }
   // local best that is strictly worse than (tv, ti) — the thread's previously taken candidate
   float tv = INFINITY, bv;
@@ -409,6 +642,15 @@ __global__ __launch_bounds__(512) void beam_row_topk_kernel(BeamP p, float* cand
 template <typename T, int NV, bool CON>
 __global__ __launch_bounds__(512) void beam_row_topk_ens_kernel(BeamP p, EnsP e, float* cand_val, int32_t* cand_tok) {
   beam_row_topk_body<T, NV, true, CON>(p, &e, cand_val, cand_tok);
+}
+
+template <typename T, int NV, bool CON>
+__global__ __launch_bounds__(512) void beam_row_sample_kernel(BeamP p, float* cand_val, int32_t* cand_tok) {
+  beam_row_topk_body<T, NV, false, CON, true>(p, nullptr, cand_val, cand_tok);
+}
+template <typename T, int NV, bool CON>
+__global__ __launch_bounds__(512) void beam_row_sample_ens_kernel(BeamP p, EnsP e, float* cand_val, int32_t* cand_tok) {
+  beam_row_topk_body<T, NV, true, CON, true>(p, &e, cand_val, cand_tok);
 }
 
 // generic-width variant: rows too long for registers are re-read from memory (L2-resident) on every scan
@@ -587,11 +829,14 @@ __global__ __launch_bounds__(512) void beam_row_topk_wide_ens_kernel(BeamP p, En
 // into the other half of the ping-pong buffers; the last workgroup to finish advances the step counter.
 // PFX (a prefix is given): where the sentence's prefix token of this step is eos, its rows all searched the FIRST row's distribution
 // (see CON above), so that row is the parent of every candidate: `beam` identical hypotheses are finalised, as in the reference.
-template <bool PFX>
+// SAMP (sampling, search.py Sampling.step :733-742): the sentence has K = beam candidates, candidate k drawn by row k from its own
+// distribution (beams_buf = arange(beam); row 0 at step 0 and where the prefix holds eos) — there is nothing to rank, and (d), (e) run
+// over K = beam: every slot yields exactly one sample.
+template <bool PFX, bool SAMP = false>
 __global__ __launch_bounds__(256) void beam_merge_kernel(BeamP p, const float* cand_val, const int32_t* cand_tok, int32_t* ticket) {
   const int s = *p.step;
   const int sent = blockIdx.x, tid = threadIdx.x;
-  const int beam = p.beam, K = 2 * beam, bbsz = p.bsz * beam;
+  const int beam = p.beam, K = SAMP ? beam : 2 * beam, bbsz = p.bsz * beam;
   const int L1 = p.max_len + 1, LT = p.max_len + 2;
   const int rows = s == 0 ? 1 : beam;
   const int cur = s & 1, nxt = cur ^ 1;
@@ -611,6 +856,15 @@ __global__ __launch_bounds__(256) void beam_merge_kernel(BeamP p, const float* c
   bool first_row_parent = false;
   if constexpr (PFX) first_row_parent = prefix_step(p, s) && p.prefix_tokens[(int64_t)sent * p.prefix_len + s] == p.eos;
   if (s <= p.max_len) {
+    if constexpr (SAMP) {
+      if (tid < beam) {
+        c_score[tid] = cand_val[(int64_t)sent * beam + tid];
+        c_tok[tid] = cand_tok[(int64_t)sent * beam + tid];
+        c_beam[tid] = (s == 0 || first_row_parent) ? 0 : tid;
+        ign[tid] = p.cands_to_ignore[sent * beam + tid];
+      }
+      __syncthreads();
+    } else {
     for (int i = tid; i < rows * K; i += blockDim.x) {
       l_val[i] = cand_val[(int64_t)sent * beam * K + i];
       l_tok[i] = cand_tok[(int64_t)sent * beam * K + i];
@@ -631,6 +885,7 @@ __global__ __launch_bounds__(256) void beam_merge_kernel(BeamP p, const float* c
       if (rank < K) { c_score[rank] = v; c_tok[rank] = l_tok[i]; c_beam[rank] = first_row_parent ? 0 : r; }
     }
     __syncthreads();
+    }
     if (tid == 0) {
       // ---- (d) bookkeeping (LDS / registers only: a global access inside these serial loops costs a memory round trip each) ----
       bool any_top_eos = false;
@@ -1024,6 +1279,7 @@ int to_params(const cst_beam_desc* d, BeamP& p) {
   p.cands_to_ignore = d->cands_to_ignore; p.finished = d->finished; p.nfinal = d->nfinal; p.num_remaining = d->num_remaining;
   p.fin_tokens = d->fin_tokens; p.fin_pos = d->fin_pos; p.fin_score = d->fin_score; p.fin_len = d->fin_len;
   p.ngram = 0; p.prefix_len = 0; p.prefix_tokens = nullptr;  // cst_beam_step sets them
+  p.sample_topk = 0; p.sample_topp = 0.0f; p.sample_key = nullptr;
   return CST_OK;
 }
 
@@ -1266,6 +1522,21 @@ int cst_beam_step(const cst_beam_desc* d, cst_stream stream) {
   p.prefix_len = (int)d->prefix_len;
   p.prefix_tokens = d->prefix_len > 0 ? d->prefix_tokens : nullptr;
   const bool con = p.ngram > 0 || p.prefix_len > 0;
+  // sampling (ABI 11): off in a zero-filled tail -> the selection kernels, launched as before
+  CST_REQUIRE(d->sample_topk >= 0 && d->sample_topk <= d->vocab, "cst_beam_step: sample_topk %lld outside [0, vocab %lld]",
+              (long long)d->sample_topk, (long long)d->vocab);
+  const bool samp = d->sampling != 0;
+  CST_REQUIRE(!samp || d->sample_key != nullptr, "cst_beam_step: sampling without sample_key (a device buffer holding the 32-bit key of the draws)");
+  if (samp) {
+    p.sample_topk = (int)d->sample_topk;
+    p.sample_topp = d->sample_topp;
+    p.sample_key = d->sample_key;
+    if (cst_ceil_div(cst_ceil_div(d->vocab, d->dtype == CST_BF16 ? 8 : 4), 512) > 5) {
+      cst_set_error("cst_beam_step: sampling covers the register-resident row kernels (vocabulary %lld needs the wide kernel, which only "
+                    "selects): decode such vocabularies with the host loop", (long long)d->vocab);
+      return CST_ERR_UNSUPPORTED;
+    }
+  }
   // checkpoint ensembles: members >= 2 (0 and 1 both mean the single matrix `logits`, today's kernels with today's arguments)
   CST_REQUIRE(d->members >= 0 && d->members <= ENS_MAX, "cst_beam_step: %lld ensemble members (at most %d)", (long long)d->members, ENS_MAX);
   EnsP e;
@@ -1298,13 +1569,27 @@ int cst_beam_step(const cst_beam_desc* d, cst_stream stream) {
     // (the constraints are a template flag: with both off the step launches the instantiations it always did)
 #define CST_TOPK_ALL(C) do { if (ens) { if (d->dtype == CST_BF16) CST_TOPK_ET(bf16_t, C); else CST_TOPK_ET(float, C); } \
                              else if (d->dtype == CST_BF16) CST_TOPK_T(bf16_t, C); else CST_TOPK_T(float, C); } while (0)
-    if (con) CST_TOPK_ALL(true); else CST_TOPK_ALL(false);
+#define CST_SAMP(T, C) do { if (ens) { if (per_thread <= 1) hipLaunchKernelGGL((beam_row_sample_ens_kernel<T, 1, C>), dim3((unsigned)rows), dim3(512), 0, s, p, e, cand_val, cand_tok); \
+                                       else if (per_thread <= 3) hipLaunchKernelGGL((beam_row_sample_ens_kernel<T, 3, C>), dim3((unsigned)rows), dim3(512), 0, s, p, e, cand_val, cand_tok); \
+                                       else hipLaunchKernelGGL((beam_row_sample_ens_kernel<T, 5, C>), dim3((unsigned)rows), dim3(512), 0, s, p, e, cand_val, cand_tok); } \
+                             else { if (per_thread <= 1) hipLaunchKernelGGL((beam_row_sample_kernel<T, 1, C>), dim3((unsigned)rows), dim3(512), 0, s, p, cand_val, cand_tok); \
+                                    else if (per_thread <= 3) hipLaunchKernelGGL((beam_row_sample_kernel<T, 3, C>), dim3((unsigned)rows), dim3(512), 0, s, p, cand_val, cand_tok); \
+                                    else hipLaunchKernelGGL((beam_row_sample_kernel<T, 5, C>), dim3((unsigned)rows), dim3(512), 0, s, p, cand_val, cand_tok); } } while (0)
+#define CST_SAMP_ALL(C) do { if (d->dtype == CST_BF16) CST_SAMP(bf16_t, C); else CST_SAMP(float, C); } while (0)
+    if (samp) { if (con) CST_SAMP_ALL(true); else CST_SAMP_ALL(false); }
+    else if (con) CST_TOPK_ALL(true); else CST_TOPK_ALL(false);
+#undef CST_SAMP_ALL
+#undef CST_SAMP
 #undef CST_TOPK_ALL
 #undef CST_TOPK_ET
 #undef CST_TOPK_E
 #undef CST_TOPK_T
 #undef CST_TOPK
-    if (p.prefix_len > 0) hipLaunchKernelGGL(beam_merge_kernel<true>, dim3(p.bsz), dim3(256), 0, s, p, (const float*)cand_val, (const int32_t*)cand_tok, ticket);
+    if (samp) {
+      if (p.prefix_len > 0) hipLaunchKernelGGL((beam_merge_kernel<true, true>), dim3(p.bsz), dim3(256), 0, s, p, (const float*)cand_val, (const int32_t*)cand_tok, ticket);
+      else hipLaunchKernelGGL((beam_merge_kernel<false, true>), dim3(p.bsz), dim3(256), 0, s, p, (const float*)cand_val, (const int32_t*)cand_tok, ticket);
+    }
+    else if (p.prefix_len > 0) hipLaunchKernelGGL(beam_merge_kernel<true>, dim3(p.bsz), dim3(256), 0, s, p, (const float*)cand_val, (const int32_t*)cand_tok, ticket);
     else hipLaunchKernelGGL(beam_merge_kernel<false>, dim3(p.bsz), dim3(256), 0, s, p, (const float*)cand_val, (const int32_t*)cand_tok, ticket);
   }
   return cst_check_launch("cst_beam_step");

@@ -29,7 +29,8 @@ from .optim import PARAM_EPOCH
 
 class BeamDecodeEngine:
     def __init__(self, decoder, tgt_dict, beam_size, max_len, min_len=1, normalize_scores=True, len_penalty=1.0,
-                 unk_penalty=0.0, temperature=1.0, use_graph=True, poll=8, cross_kernel=None, lanes=None, no_repeat_ngram_size=0):
+                 unk_penalty=0.0, temperature=1.0, use_graph=True, poll=8, cross_kernel=None, lanes=None, no_repeat_ngram_size=0,
+                 sampling=False, topk=0, topp=0.0):
         # a checkpoint ensemble (--path a.pt:b.pt:c.pt) is a LIST of decoders: every member keeps its own packed weights, K/V caches,
         # encoder K/V and logits buffer; the beam state (tokens / scores / ancestry, step counter, finalized hypotheses) is shared —
         # all members follow the same hypotheses, so one ancestry table serves every member's append-only caches
@@ -45,6 +46,9 @@ class BeamDecodeEngine:
         # --no-repeat-ngram-size: a parameter of cst_beam_step's row kernel (0 = off: the kernels without the constraint code)
         self.no_repeat_ngram_size = int(no_repeat_ngram_size)
         assert self.no_repeat_ngram_size == 0 or self.no_repeat_ngram_size >= 2, "no_repeat_ngram_size is 0 (off) or at least 2"
+        # --sampling / --sampling-topk / --sampling-topp: cst_beam_step draws one token per row instead of selecting the top 2 * beam
+        # (sequence_generator.Sampling is the readable form).  The key of a call's draws lives in a buffer the state owns.
+        self.sampling, self.topk, self.topp = bool(sampling), max(int(topk), 0), max(float(topp), 0.0)
         # cross attention per step: "flash" = cst_attn_fwd with batch = sentence and the beam rows as the query axis (37 us per
         # layer at 32 x beam 5 x 750 source positions, bf16); "flash_hm" = the same kernel over head-major K/V (contiguous per-head
         # streams: no faster, 0.811 vs 0.812 ms per step); "shared" = cst_dec_cross_attn (VALU kernel, one pass with online
@@ -61,6 +65,8 @@ class BeamDecodeEngine:
         # (32 x beam 5, s2t_transformer_l): 1 lane 0.877 ms per step, 2 lanes 0.910, 3 lanes 1.60, 4 lanes 1.63 — the step graphs of
         # different streams do not overlap on this stack (a half-batch step costs 0.455 ms, two of them 0.91), so the default is 1.
         self.lanes = max(1, int(os.environ.get("CST_DEC_LANES", "1") if lanes is None else lanes))
+        if self.sampling:
+            self.lanes = 1  # the index of a draw holds the sentence's position in the WHOLE batch
         self._packed = None
         self._state = {}
         self._cfg = None
@@ -80,6 +86,13 @@ class BeamDecodeEngine:
             return bool(ok)
         except AttributeError:
             return False
+
+    @staticmethod
+    def sampling_supported(vocab, dtype):
+        """cst_beam_step samples in its register-resident row kernels: at most 5 * 512 16-byte vectors per row (20480 symbols in bf16,
+        10240 in fp32).  Beyond that it returns CST_ERR_UNSUPPORTED, so the generator takes the host loop up front."""
+        vec = 8 if dtype == torch.bfloat16 else 4
+        return -(-(-(-int(vocab) // vec)) // 512) <= 5
 
     def invalidate(self):
         """Drop the packed / folded weight copies and the captured graphs (call after changing decoder weights by any other route)."""
@@ -198,7 +211,7 @@ class BeamDecodeEngine:
         state owns (st["prefix"]), which every call overwrites: a replayed graph reads the new call's prefix."""
         S = tuple(S) if isinstance(S, (list, tuple)) else (S,) * len(self.decs)
         has_mask = tuple(has_mask) if isinstance(has_mask, (list, tuple)) else (has_mask,) * len(self.decs)
-        key = (lane, bsz, S, dtype, device, has_mask, prefix_len, self.no_repeat_ngram_size)
+        key = (lane, bsz, S, dtype, device, has_mask, prefix_len, self.no_repeat_ngram_size, self.sampling, self.topk, self.topp)
         st = self._state.get(key)
         if st is not None:
             return st
@@ -238,6 +251,9 @@ class BeamDecodeEngine:
         st["prefix"] = torch.full((bsz, prefix_len), self.pad, dtype=torch.int64, device=device) if prefix_len > 0 else None
         if prefix_len > 0:
             d.prefix_tokens, d.prefix_len = st["prefix"].data_ptr(), prefix_len
+        st["sample_key"] = z(1, dt=torch.int32) if self.sampling else None  # (the 32 bits of the key; the kernel reads them unsigned)
+        if self.sampling:
+            d.sampling, d.sample_topk, d.sample_topp, d.sample_key = 1, self.topk, self.topp, st["sample_key"].data_ptr()
         st["desc"] = d
         self._state[key] = st
         return st
@@ -367,11 +383,13 @@ class BeamDecodeEngine:
 
     # ------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def generate(self, encoder_out, bsz, prefix_tokens=None):
+    def generate(self, encoder_out, bsz, prefix_tokens=None, sample_key=0):
         """encoder_out: EncoderOut with encoder_out [S, B, C] (T x B x C view) and encoder_padding_mask [B, S] or None — for an
         ensemble a list with one EncoderOut per member (each member's own encoder; lengths S and widths may differ).
         prefix_tokens: None or int64 [bsz, K] padded with pad, K <= max_len: the tokens forced at the first K steps (--prefix-size);
         it is copied into the engine's own buffer (the caller's tensor is never captured).
+        sample_key: the 32-bit key of this call's draws (sampling only), written into the state's buffer before the first step: the
+        captured step graph reads it there, so a replay draws with the key of the call that replays it.
         Returns the reference's `finalized` structure (list over sentences of hypothesis dicts, best first)."""
         prefix_len = 0 if prefix_tokens is None else int(prefix_tokens.shape[1])
         assert prefix_tokens is None or (prefix_tokens.dim() == 2 and prefix_tokens.shape[0] == bsz and prefix_len <= self.max_len)
@@ -406,6 +424,9 @@ class BeamDecodeEngine:
                 st = self._alloc(i, b1 - b0, S, dtype, device, has_mask, prefix_len)
                 if prefix_len > 0:  # the lane's sentences' prefixes, into the buffer the (captured) beam step reads
                     st["prefix"].copy_(prefix_tokens[b0:b1].to(device=device, dtype=torch.int64))
+                if self.sampling:
+                    k32 = int(sample_key) & 0xFFFFFFFF
+                    st["sample_key"].fill_(k32 - (1 << 32) if k32 >= (1 << 31) else k32)
                 done = self._begin(st, pk, [e[b0:b1] for e in encb], [m[b0:b1] if m is not None else None for m in masks], b1 - b0)
             runs.append(dict(stream=stream, st=st, bsz=b1 - b0, steps=done, remaining=b1 - b0))
         while any(r["steps"] < total and r["remaining"] > 0 for r in runs):

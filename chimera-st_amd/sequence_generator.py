@@ -6,13 +6,20 @@ batch-major [B*beam, T, C]; single-query fused attention).  The constraints `no_
 `prefix_tokens` (_prefix_tokens :543-575) run inside the beam-step kernel on the engine and as tensor operations on the device
 in the host loop (the reference copies the token matrix to the host every step and keys Python dictionaries by strings).
 
+`Sampling` (search.py:621-742: --sampling, --sampling-topk, --sampling-topp) is the one search strategy besides beam search that the
+device engine runs (cst_beam_step draws inside its row kernel); its draws are counter-based — a function of (key, sentence, slot,
+step), like the dropout masks of rng.py — so the engine and the host loop below draw the same tokens from the same distributions.
+
 Differences that do not change results: finished sentences are masked out instead of being removed from the batch
 (the reference shrinks the batch, :427-463 — an optimisation only; every sentence's search is independent)."""
 import math
 from typing import Dict, List, Optional
 
+import numpy as np
 import torch
 from torch import Tensor
+
+from . import rng
 
 
 class BeamSearch:
@@ -35,10 +42,85 @@ class BeamSearch:
         return scores_buf, indices_buf, beams_buf
 
 
+def sample_uniforms(key, idx):
+    """The uniforms of the sampling draws, u = (cst_drop_bits32(key, cst_drop_key2(key), idx) >> 8) * 2^-24 in [0, 1) (float64, exact):
+    the numpy twin of the device code (csrc/cst_common.h).  idx: integer array, idx = (sentence * beam + slot) * (max_len + 1) + step."""
+    key = int(key) & 0xFFFFFFFF
+    key2 = (key * 0x2C1B3C6D + 0x297A2D39) & 0xFFFFFFFF
+    bits = rng._bits32(key, key2, np.asarray(idx, dtype=np.uint64) & np.uint64(0xFFFFFFFF))
+    return (bits >> np.uint64(8)).astype(np.float64) * 2.0 ** -24
+
+
+def sample_key_of(seed, ordinal):
+    """The 32-bit key of the `ordinal`-th generate() call of a generator seeded with `seed` (rng.DropoutState.next_key's mixing)."""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    return rng._hash32((seed & 0xFFFFFFFF) ^ rng._hash32(int(ordinal) * 0x9E3779B1 + (seed >> 32)))
+
+
+class Sampling:
+    """search.py:621-742 with counter-based draws.  After the generator's masks, q_v = exp(lprob_v) (not renormalised):
+      top-p (sampling_topp > 0, wins): in the order (value descending, token ascending) keep every element with less than p of mass in
+            front of it (_sample_topp :630-673: cumsum.lt(p) plus one more element; whole mass < p: everything);
+      top-k (sampling_topk > 0): keep the first k of that order;
+      draw: the smallest kept token v whose inclusive kept mass in vocabulary order exceeds u * Z (Z = the kept mass), u from
+            sample_uniforms(key, (sentence * beam + slot) * (max_len + 1) + step).
+    Step 0 draws `beam` tokens from each sentence's first row; later steps one token per row, and row i continues hypothesis i.  The
+    score of a draw is its masked log-probability + the row's cumulative score.  A row without mass yields (-inf, pad)."""
+
+    def __init__(self, tgt_dict, sampling_topk=-1, sampling_topp=-1.0):
+        self.pad, self.unk, self.eos = tgt_dict.pad(), tgt_dict.unk(), tgt_dict.eos()
+        self.vocab_size = len(tgt_dict)
+        self.sampling_topk, self.sampling_topp = int(sampling_topk), float(sampling_topp)
+        if self.sampling_topk > self.vocab_size:
+            raise ValueError("sampling_topk %d exceeds the vocabulary (%d symbols)" % (self.sampling_topk, self.vocab_size))
+
+    def kept(self, lprobs):
+        """bool [..., V]: the elements the draw chooses among."""
+        if self.sampling_topp <= 0 and self.sampling_topk <= 0:
+            return torch.ones_like(lprobs, dtype=torch.bool)
+        val, order = torch.sort(lprobs, dim=-1, descending=True, stable=True)  # equal values keep their token order
+        if self.sampling_topp > 0:
+            q = val.exp().double()
+            keep = (q.cumsum(-1) - q) < self.sampling_topp
+        else:
+            keep = torch.arange(lprobs.size(-1), device=lprobs.device).expand_as(val) < self.sampling_topk
+        return torch.zeros_like(keep).scatter(-1, order, keep)
+
+    def step(self, step: int, lprobs, scores, key=0, max_len=None):
+        """lprobs [bsz, beam, V] after the generator's masks, scores [bsz, beam, >= step] cumulative; key: the call's 32-bit key;
+        max_len: the generator's step limit (part of the draw index).  Returns `beam` candidates per sentence."""
+        bsz, beam_size, V = lprobs.size()
+        assert max_len is not None, "Sampling.step needs the generator's max_len: it is part of the index of a draw"
+        if step == 0:
+            lprobs = lprobs[:, ::beam_size, :]  # the first row of every sentence serves all its slots
+        q = torch.where(self.kept(lprobs), lprobs.exp(), torch.zeros_like(lprobs)).double()
+        cdf = q.cumsum(-1)
+        Z = cdf[..., -1:]
+        slot = np.arange(bsz * beam_size, dtype=np.int64) * (max_len + 1) + step
+        u = torch.from_numpy(sample_uniforms(key, slot)).to(lprobs.device).view(bsz, beam_size, 1)
+        if step == 0:
+            q, cdf, lprobs = (t.expand(bsz, beam_size, V) for t in (q, cdf, lprobs))
+        ids = torch.arange(V, device=lprobs.device).expand(bsz, beam_size, V)
+        hit = (cdf > u * Z) & (q > 0)
+        tok = torch.where(hit, ids, torch.full_like(ids, V)).amin(-1)
+        last = torch.where(q > 0, ids, torch.full_like(ids, -1)).amax(-1)  # (rounding at the top of the CDF: the last kept token)
+        tok = torch.where(tok == V, last, tok)
+        none = tok < 0
+        tok = torch.where(none, torch.full_like(tok, self.pad), tok)
+        scores_buf = lprobs.gather(2, tok.unsqueeze(-1)).squeeze(-1)
+        scores_buf = torch.where(none, torch.full_like(scores_buf, -math.inf), scores_buf)
+        if step == 0:
+            beams_buf = torch.zeros_like(tok)
+        else:
+            beams_buf = torch.arange(beam_size, device=tok.device).repeat(bsz, 1)
+            scores_buf = scores_buf + scores[:, :, step - 1]
+        return scores_buf, tok, beams_buf
+
+
 class SequenceGenerator:
     def __init__(self, models, tgt_dict, beam_size=1, max_len_a=0, max_len_b=200, min_len=1, normalize_scores=True,
                  len_penalty=1.0, unk_penalty=0.0, temperature=1.0, match_source_len=False, no_repeat_ngram_size=0,
-                 search_strategy=None, eos=None, fused=True, use_graph=True, cross_kernel=None):
+                 search_strategy=None, eos=None, fused=True, use_graph=True, cross_kernel=None, seed=1):
         self.models = list(models) if isinstance(models, (list, tuple)) else [models]
         self.model = self.models[0]
         self.tgt_dict = tgt_dict
@@ -63,16 +145,21 @@ class SequenceGenerator:
         self.search = BeamSearch(tgt_dict) if search_strategy is None else search_strategy
         # fused=True (default): the device-resident loop of decode_engine.py (one captured HIP graph per step, no per-step host
         # sync); fused=False: the module-by-module mirror of the reference loop below (same kernels, host-driven) — kept as the
-        # readable restatement and as the cross-check of the engine.  A custom search strategy needs the host loop.
-        self.fused = bool(fused) and search_strategy is None and (eos is None or eos == tgt_dict.eos())
+        # readable restatement and as the cross-check of the engine.  A custom search strategy needs the host loop — except Sampling
+        # (exactly that class: a subclass may draw differently), which cst_beam_step runs itself.
+        self.sampling = isinstance(self.search, Sampling)  # (the host loop hands key and max_len to any Sampling, a subclass included)
+        self.fused = bool(fused) and (search_strategy is None or type(self.search) is Sampling) and (eos is None or eos == tgt_dict.eos())
+        # sampling: the key of a call's draws = hash of (seed, the call's ordinal in this generator)
+        self.seed, self.calls = int(seed), 0
         self._engine = None
         self.use_graph, self.cross_kernel = use_graph, cross_kernel
         for m in self.models:
             m.eval()
 
     @torch.no_grad()
-    def generate(self, models, sample, prefix_tokens=None, **kwargs):
-        return self._generate(sample, prefix_tokens=prefix_tokens)
+    def generate(self, models, sample, prefix_tokens=None, sample_key=None, **kwargs):
+        """sample_key: the 32-bit key of this call's draws (sampling only); default: the next key of the generator's own stream."""
+        return self._generate(sample, prefix_tokens=prefix_tokens, sample_key=sample_key)
 
     def _check_prefix(self, prefix_tokens, bsz, max_len):
         if prefix_tokens.dim() != 2 or prefix_tokens.size(0) != bsz:
@@ -121,7 +208,9 @@ class SequenceGenerator:
             return log_probs[0]
         return torch.logsumexp(torch.stack(log_probs, dim=0), dim=0) - math.log(len(log_probs))
 
-    def _generate(self, sample, prefix_tokens=None):
+    def _generate(self, sample, prefix_tokens=None, sample_key=None):
+        self.calls += 1
+        key = (sample_key_of(self.seed, self.calls) if sample_key is None else int(sample_key) & 0xFFFFFFFF) if self.sampling else 0
         net_input = sample["net_input"]
         src_tokens = net_input["src_tokens"]
         bsz, src_len = src_tokens.size()[:2]
@@ -137,14 +226,20 @@ class SequenceGenerator:
         encoder_outs = [m.encoder.forward_torchscript(net_input) for m in self.models]
         if self.fused:
             from .decode_engine import BeamDecodeEngine
-            if len(self.models) <= 8 and all(BeamDecodeEngine.supported(m.decoder) for m in self.models):  # else the whole ensemble takes the host loop
+            ok = len(self.models) <= 8 and all(BeamDecodeEngine.supported(m.decoder) for m in self.models)  # else the whole ensemble takes the host loop
+            if self.sampling:  # (the wide-vocabulary row kernel only selects: such vocabularies are sampled by the host loop)
+                ok = ok and BeamDecodeEngine.sampling_supported(self.vocab_size, encoder_outs[0].encoder_out.dtype)
+            if ok:
                 if self._engine is None or self._engine.max_len != max_len:
                     decs = [m.decoder for m in self.models]
                     self._engine = BeamDecodeEngine(decs if len(decs) > 1 else decs[0], self.tgt_dict, beam_size, max_len, self.min_len,
                                                     self.normalize_scores, self.len_penalty, self.unk_penalty, self.temperature,
                                                     use_graph=self.use_graph, cross_kernel=self.cross_kernel,
-                                                    no_repeat_ngram_size=self.no_repeat_ngram_size)
-                return self._engine.generate(encoder_outs if len(encoder_outs) > 1 else encoder_outs[0], bsz, prefix_tokens=prefix_tokens)
+                                                    no_repeat_ngram_size=self.no_repeat_ngram_size, sampling=self.sampling,
+                                                    topk=self.search.sampling_topk if self.sampling else 0,
+                                                    topp=self.search.sampling_topp if self.sampling else 0.0)
+                return self._engine.generate(encoder_outs if len(encoder_outs) > 1 else encoder_outs[0], bsz, prefix_tokens=prefix_tokens,
+                                             sample_key=key)
         new_order = torch.arange(bsz, device=device).view(-1, 1).repeat(1, beam_size).view(-1)
         encoder_outs = [m.encoder.reorder_encoder_out(e, new_order) for m, e in zip(self.models, encoder_outs)]
         incremental_states: List[Dict[str, Dict[str, Optional[Tensor]]]] = [{} for _ in self.models]
@@ -179,8 +274,9 @@ class SequenceGenerator:
                 lprobs[:, self.eos] = -math.inf
             if self.no_repeat_ngram_size > 0:
                 lprobs = self._ban_repeated_ngrams(tokens, lprobs, step)
+            extra = dict(key=key, max_len=max_len) if self.sampling else {}  # (Sampling returns beam candidates per sentence, not 2 * beam)
             cand_scores, cand_indices, cand_beams = self.search.step(
-                step, lprobs.view(bsz, -1, self.vocab_size), scores.view(bsz, beam_size, -1)[:, :, :step])
+                step, lprobs.view(bsz, -1, self.vocab_size), scores.view(bsz, beam_size, -1)[:, :, :step], **extra)
             cand_bbsz_idx = cand_beams.add(bbsz_offsets)
             eos_mask = cand_indices.eq(self.eos) & cand_scores.ne(-math.inf)
             eos_mask[:, :beam_size][cands_to_ignore] = False

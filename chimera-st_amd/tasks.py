@@ -97,15 +97,21 @@ class FairseqTask:
                                     required_batch_size_multiple, seed, num_shards, shard_id, epoch)
 
     def build_generator(self, models, args, seq_gen_cls=None, extra_gen_cls_kwargs=None):
-        """fairseq_task.py:309-412, beam-search branch."""
-        from .sequence_generator import SequenceGenerator
+        """fairseq_task.py:309-412: beam search, or Sampling with --sampling (:329-357)."""
+        from .sequence_generator import Sampling, SequenceGenerator
 
+        sampling = getattr(args, "sampling", False)
+        sampling_topk = getattr(args, "sampling_topk", -1)
+        sampling_topp = getattr(args, "sampling_topp", -1.0)
+        assert sampling_topk < 0 or sampling, "--sampling-topk requires --sampling"
+        assert sampling_topp < 0 or sampling, "--sampling-topp requires --sampling"
+        search = Sampling(self.target_dictionary, sampling_topk, sampling_topp) if sampling else None
         return SequenceGenerator(
             models, self.target_dictionary, beam_size=getattr(args, "beam", 5), max_len_a=getattr(args, "max_len_a", 0),
             max_len_b=getattr(args, "max_len_b", 200), min_len=getattr(args, "min_len", 1),
             normalize_scores=(not getattr(args, "unnormalized", False)), len_penalty=getattr(args, "lenpen", 1),
             unk_penalty=getattr(args, "unkpen", 0), temperature=getattr(args, "temperature", 1.0),
-            no_repeat_ngram_size=getattr(args, "no_repeat_ngram_size", 0))
+            no_repeat_ngram_size=getattr(args, "no_repeat_ngram_size", 0), search_strategy=search, seed=getattr(args, "seed", 1))
 
 
 def _load_dict(args, default_size):

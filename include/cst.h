@@ -32,9 +32,10 @@ extern "C" {
  * fixed-order reductions; 4: cst_attn_desc.kpm_bits / bwd_ws, the separable attention-dropout mask; 5: cst_gemm_desc.colsum;
  * 6: cst_dec_ln_q_cross_attn; 7: cst_fbank_desc, cst_fbank, cst_fbank_workspace_bytes; 8: cst_conv0_ln_gelu_fwd / _bwd,
  * cst_ln_gelu_fwd / _bwd and their workspaces; 9: cst_beam_desc.members / logits_n / lprobs_out — checkpoint ensembles;
- * 10: cst_beam_desc.no_repeat_ngram / prefix_tokens / prefix_len — n-gram blocking and forced prefixes).
+ * 10: cst_beam_desc.no_repeat_ngram / prefix_tokens / prefix_len — n-gram blocking and forced prefixes;
+ * 11: cst_beam_desc.sampling / sample_topk / sample_topp / sample_key — sampling decode).
  * cst_version() returns the value the library was built with; chimera-st_amd/lib.py refuses a mismatch. */
-#define CST_ABI_VERSION 10
+#define CST_ABI_VERSION 11
 
 typedef enum { CST_F32 = 0, CST_BF16 = 1 } cst_dtype;
 
@@ -534,6 +535,22 @@ int cst_adam_step(float* master, float* exp_avg, float* exp_avg_sq, const void* 
  *   FIRST row and that row is the parent of every candidate (the reference copies the first beam over the others): `beam` identical
  *   hypotheses are finalised.  The buffer is read at every step, so a captured step sees the contents of the moment it runs.
  *   prefix_len > 0 with a null pointer, prefix_len < 0 or > max_len: CST_ERR_BAD_ARG.
+ *   Sampling (ABI 11; off in a zero-filled tail, and a step with it off launches exactly the kernels above; search.py Sampling.step
+ *   :676-742): sampling != 0 replaces the top-2*beam selection by one DRAW per row, still two launches.  After the masks above, with
+ *   q_v = exp(masked log-probability) (not renormalised): sample_topp > 0 keeps, in the order (value descending, token ascending), every
+ *   element with less than p of mass in front of it (_sample_topp :630-673; whole mass < p: everything); else sample_topk = k > 0 keeps
+ *   the first k of that order; else everything.  Step 0 uses the sentence's first row and draws `beam` tokens with replacement (slots
+ *   0 .. beam-1); later steps draw one token per row, and row i continues hypothesis i (no competition between beams; where the
+ *   prefix holds eos, every row draws from the first row, which is then the parent).  The draw of (sentence, slot) at step s:
+ *     u = (cst_drop_bits32(key, cst_drop_key2(key), (sentence * beam + slot) * (max_len + 1) + s) >> 8) * 2^-24,   key = *sample_key,
+ *   token = the smallest kept v with sum of q_w over kept w <= v exceeding u * Z, Z = the kept mass (inverse CDF in vocabulary order).
+ *   Its score is its masked log-probability + the row's cumulative score (NOT the renormalised probability); a row without mass yields
+ *   (-inf, pad).  The sentence has `beam` candidates: an eos candidate whose slot is not ignored is finalised, the next rows are the
+ *   non-eos candidates in slot order followed by the others, which are ignored for good — every slot yields exactly one sample.
+ *   sample_key is read from device memory at every step: a captured step draws with the key of the call that replays it.  All sums that
+ *   decide the cut or the draw have a fixed order (no floating-point atomics; longest addition chain 64), so a call is reproducible.
+ *   sample_topk < 0 or > vocab, sampling with a null sample_key: CST_ERR_BAD_ARG.  Vocabularies beyond the register-resident row
+ *   kernels (more than 5 * 512 16-byte vectors per row): CST_ERR_UNSUPPORTED — nothing is launched in either case.
  * ------------------------------------------------------------------------------------------ */
 typedef struct {
   int dtype;                         /* storage type of logits */
@@ -553,6 +570,10 @@ typedef struct {
   int64_t no_repeat_ngram;           /* ABI 10: 0 = off, else n >= 2 */
   const int64_t* prefix_tokens;      /* ABI 10: device [bsz][prefix_len], padded with `pad`; read when prefix_len > 0 */
   int64_t prefix_len;                /* ABI 10: 0 = off, at most max_len */
+  int64_t sampling;                  /* ABI 11: 0 = off (beam search), else every row DRAWS its next token */
+  int64_t sample_topk;               /* ABI 11: 0 = off, else draw among the k most probable tokens (at most vocab) */
+  float sample_topp;                 /* ABI 11: <= 0 = off, else draw from the nucleus of mass p (wins over sample_topk) */
+  const uint32_t* sample_key;        /* ABI 11: device [1], the 32-bit key of the draws; read at every step (required when sampling) */
 } cst_beam_desc;
 int64_t cst_beam_workspace(int64_t bsz, int64_t beam);
 int cst_beam_init(const cst_beam_desc* d, cst_stream stream);

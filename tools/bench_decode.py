@@ -3,14 +3,15 @@
 6 decoder layers, 10 000-way tied vocabulary), filter-bank input, beam 5, incremental-state decode, 1 x MI355X, bf16.
 
   python tools/bench_decode.py [--batch 32] [--frames 3000] [--beam 5] [--max-len 200] [--reps 3] [--mirror] [--ensemble N]
-                               [--no-repeat-ngram-size N]
+                               [--no-repeat-ngram-size N] [--sampling [--sampling-topk K] [--sampling-topp P]]
 
 Prints one JSON line: utterances/s and generated tokens/s of the device-resident loop (decode_engine.py: one captured HIP
 graph per step), the per-step time, the encoder time, and — with --mirror — the same numbers for the host-driven
 module-by-module loop (fused=False).  Random-init weights emit eos only when forced, so every sentence runs the full
 max_len + 1 steps: the reported rate is the worst case for the configured max_len.
 --ensemble N decodes N independently seeded copies of the model as a checkpoint ensemble (every member's encoder and decoder run;
-one beam step over the N logits matrices) and adds "models" and "nodes_per_step" to the line."""
+one beam step over the N logits matrices) and adds "models" and "nodes_per_step" to the line.
+--sampling decodes with the Sampling strategy (every hypothesis an independent sample) on the same engine."""
 import argparse
 import importlib
 import json
@@ -39,6 +40,9 @@ def main():
     ap.add_argument("--cross-kernel", default="flash", choices=["flash", "flash_hm", "shared"])
     ap.add_argument("--ensemble", type=int, default=1, help="decode N independently seeded copies of the model as an ensemble")
     ap.add_argument("--no-repeat-ngram-size", type=int, default=0, help="decode with n-gram blocking (0 = off)")
+    ap.add_argument("--sampling", action="store_true", help="sample instead of beam search")
+    ap.add_argument("--sampling-topk", type=int, default=-1)
+    ap.add_argument("--sampling-topp", type=float, default=-1.0)
     ap.add_argument("--profile", action="store_true", help="per-class GPU time of one eager decode loop (hipEvent pairs)")
     args = ap.parse_args()
 
@@ -48,6 +52,7 @@ def main():
     reg = importlib.import_module("chimera-st_amd.registry")
     lib = importlib.import_module("chimera-st_amd.lib")
     SG = importlib.import_module("chimera-st_amd.sequence_generator").SequenceGenerator
+    Sampling = importlib.import_module("chimera-st_amd.sequence_generator").Sampling
     lib.load()
     dt = torch.bfloat16 if args.dtype == "bf16" else torch.float32
     torch.manual_seed(1)
@@ -86,14 +91,18 @@ def main():
         torch.cuda.synchronize()
         enc_s = (time.perf_counter() - t0) / args.reps
 
+    strategy = lambda: Sampling(task.target_dictionary, args.sampling_topk, args.sampling_topp) if args.sampling else None
     fused = SG(models, task.target_dictionary, beam_size=args.beam, max_len_a=0, max_len_b=args.max_len, use_graph=not args.no_graph,
-               cross_kernel=args.cross_kernel, no_repeat_ngram_size=args.no_repeat_ngram_size)
+               cross_kernel=args.cross_kernel, no_repeat_ngram_size=args.no_repeat_ngram_size, search_strategy=strategy())
     t_f, ntok = timed(fused)
     steps = args.max_len + 1
     out = {"metric": "decode utterances/sec, s2t_transformer_l beam 5, 1 MI355X", "config": {"arch": args.arch, "batch": args.batch,
            "beam": args.beam, "max_frames": args.frames, "max_len": args.max_len, "dtype": args.dtype, "graph": not args.no_graph},
            "utterances_per_s": args.batch / t_f, "tokens_per_s": ntok / t_f, "best_hyp_tokens": ntok, "s_per_batch": t_f,
            "encoder_s": enc_s, "ms_per_step": (t_f - enc_s) / steps * 1e3, "hyp_rows_per_step": args.batch * args.beam}
+    if args.sampling:
+        out["config"].update(sampling=True, sampling_topk=args.sampling_topk, sampling_topp=args.sampling_topp)
+        out["nodes_per_step"] = fused._engine.nodes_per_step(dt, args.batch * args.beam)
     if args.no_repeat_ngram_size:
         out["config"]["no_repeat_ngram_size"] = args.no_repeat_ngram_size
         out["nodes_per_step"] = fused._engine.nodes_per_step(dt, args.batch * args.beam)
@@ -101,7 +110,8 @@ def main():
         out["models"] = args.ensemble
         out["nodes_per_step"] = fused._engine.nodes_per_step(dt, args.batch * args.beam)
     if args.mirror:
-        mirror = SG(models, task.target_dictionary, beam_size=args.beam, max_len_a=0, max_len_b=args.max_len, fused=False)
+        mirror = SG(models, task.target_dictionary, beam_size=args.beam, max_len_a=0, max_len_b=args.max_len, fused=False,
+                    search_strategy=strategy())
         t_m, ntok_m = timed(mirror)
         out["mirror_host_loop"] = {"utterances_per_s": args.batch / t_m, "tokens_per_s": ntok_m / t_m, "s_per_batch": t_m,
                                    "ms_per_step": (t_m - enc_s) / steps * 1e3}
