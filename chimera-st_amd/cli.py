@@ -243,6 +243,11 @@ def generate_parser():
     p.add_argument("--sampling-topk", type=int, default=-1, help="draw among the k most probable tokens only (requires --sampling)")
     p.add_argument("--sampling-topp", type=float, default=-1.0, help="draw from the smallest set of tokens with probability mass p "
                    "(nucleus sampling; requires --sampling, wins over --sampling-topk)")
+    p.add_argument("--diverse-beam-groups", type=int, default=-1, help="diverse beam search: the --beam hypotheses are dealt to this many "
+                   "groups, and a group is penalised for tokens the groups before it chose at the same step (--beam must be divisible)")
+    p.add_argument("--diverse-beam-strength", type=float, default=0.5, help="the penalty per earlier choice of a token (diverse beam search)")
+    p.add_argument("--diversity-rate", type=float, default=-1.0, help="diverse siblings search: the p-th best continuation of a hypothesis "
+                   "loses p times this rate (0 equals beam search; negative = off)")
     p.add_argument("--nbest", type=int, default=1, help="hypotheses printed per sentence (at most --beam)")
     p.add_argument("--remove-bpe", "--post-process", nargs="?", const="@@ ", default=None, dest="post_process")
     p.add_argument("--scoring", default="bleu")
@@ -262,6 +267,10 @@ def check_generate_args(args):
         raise ValueError("--sampling-topk requires --sampling")
     if args.sampling_topp >= 0 and not args.sampling:
         raise ValueError("--sampling-topp requires --sampling")
+    if sum(int(bool(c)) for c in (args.sampling, args.diverse_beam_groups > 0, args.diversity_rate > 0)) > 1:
+        raise ValueError("Provided Search parameters are mutually exclusive.")
+    if args.diverse_beam_groups > 0 and args.beam % args.diverse_beam_groups != 0:
+        raise ValueError("DiverseBeamSearch requires --beam to be divisible by the number of groups")
     return args
 
 
@@ -331,6 +340,8 @@ def generate_main(argv=None):
     summary = {"event": "generate", "subset": args.gen_subset, "sentences": nsent, "tokens": ntok, "seconds": dt,
                "sentences_per_s": nsent / max(dt, 1e-9), "tokens_per_s": ntok / max(dt, 1e-9), "beam": args.beam, "models": len(models),
                "sampling": bool(args.sampling), "nbest": args.nbest, "seed": args.seed,
+               "diverse_beam_groups": args.diverse_beam_groups, "diverse_beam_strength": args.diverse_beam_strength,
+               "diversity_rate": args.diversity_rate,
                "bleu4_whitespace": corpus_bleu(hyps, refs) if any(refs) else None, "ignored_flags": ignored}
     print(json.dumps(summary), file=out, flush=True)
     if out is not sys.stdout:

@@ -28,6 +28,9 @@ struct BeamP {
   int sample_topk;                // --sampling-topk (0 = off); read by the sampling kernels only
   float sample_topp;              // --sampling-topp (<= 0 = off; wins over top-k)
   const uint32_t* sample_key;     // device [1]: the 32-bit key of this call's draws, read at every step
+  int div_groups;                 // --diverse-beam-groups G (read by the DIV == 1 merge kernels only)
+  float div_strength;             // --diverse-beam-strength S >= 0
+  float sibling_rate;             // --diversity-rate R >= 0 (read by the DIV == 2 merge kernels only)
 };
 
 __global__ void beam_init_kernel(BeamP p, int32_t* ticket) {
@@ -832,7 +835,26 @@ __global__ __launch_bounds__(512) void beam_row_topk_wide_ens_kernel(BeamP p, En
 // SAMP (sampling, search.py Sampling.step :733-742): the sentence has K = beam candidates, candidate k drawn by row k from its own
 // distribution (beams_buf = arange(beam); row 0 at step 0 and where the prefix holds eos) — there is nothing to rank, and (d), (e) run
 // over K = beam: every slot yields exactly one sample.
-template <bool PFX, bool SAMP = false>
+// DIV = 1 (beam groups, search.py DiverseBeamSearch.step :568-618, Hamming diversity): with G = div_groups, mb = beam / G, group g owns
+// the rows r with r % G == g (the reference's lprobs[:, g::G]) and selects, in the order g = 0 .. G-1, its top 2*mb over its mb * V
+// candidates by  value = fl(fl(lp + cumulative score) + fl(-S * count_g(token)))  — the row kernel's candidate value plus the penalty;
+// the reference adds the penalty to lp first, a difference of one fp32 rounding of the cumulative score.  count_g(t) = how many of the
+// 2*mb selections of each of the groups 0 .. g-1 of this sentence at this step have token t (all of them: duplicates, eos and -inf
+// candidates included, like the reference's scatter_add_).  Ties go to the smaller flat index local_row * V + token.  The group's j-th
+// selection is the sentence's candidate j * G + g (torch.stack(..., dim=2)) with parent row local_row * G + g; the penalised value is
+// the score that (d) and (e) write.  Step 0: every group searches the first row's list (the rows are equal there) and the parent is
+// the first row.
+// The rows' top 2*beam lists suffice: with S >= 0 the penalty only lowers values, and only those of the at most 2*beam - 2*mb distinct
+// tokens the earlier groups selected.  A token outside its row's unpenalised top 2*beam has at least 2*beam tokens of that row in front
+// of it, at least 2*mb of them unpenalised, which keep a value at least as large: it cannot enter the group's top 2*mb.
+// The G rounds run inside the one workgroup: (1) one thread per candidate of the group's rows forms the penalised value (the count is a
+// scan of an LDS list of at most 2*beam - 2*mb <= 38 tokens), (2) the one-thread-per-candidate rank loop below over the round's
+// mb * 2*beam values, (3) rank < 2*mb writes the candidate and appends its token to the list.  Two barriers per round, no global
+// traffic, no atomics.
+// DIV = 2 (diverse siblings, search.py DiverseSiblingsSearch.step :765-814): at steps s > 0 the candidate at position p (from 0) of a
+// row's sorted list has the value fl(v - fl((p + 1) * R)), formed where the lists are staged; the lists stay sorted, so the rank loop
+// and its tie rule (smaller row * 2*beam + p) are the plain ones.  Step 0 is plain beam search.
+template <bool PFX, bool SAMP = false, int DIV = 0>
 __global__ __launch_bounds__(256) void beam_merge_kernel(BeamP p, const float* cand_val, const int32_t* cand_tok, int32_t* ticket) {
   const int s = *p.step;
   const int sent = blockIdx.x, tid = threadIdx.x;
@@ -866,11 +888,48 @@ __global__ __launch_bounds__(256) void beam_merge_kernel(BeamP p, const float* c
       __syncthreads();
     } else {
     for (int i = tid; i < rows * K; i += blockDim.x) {
-      l_val[i] = cand_val[(int64_t)sent * beam * K + i];
+      float v = cand_val[(int64_t)sent * beam * K + i];
+      if constexpr (DIV == 2) { if (s > 0) v = __fsub_rn(v, __fmul_rn((float)(i % K + 1), p.sibling_rate)); }  // (no contraction to an fma)
+      l_val[i] = v;
       l_tok[i] = cand_tok[(int64_t)sent * beam * K + i];
     }
     if (tid < beam) ign[tid] = p.cands_to_ignore[sent * beam + tid];
     __syncthreads();
+    if constexpr (DIV == 1) {
+      __shared__ float g_val[BEAM_MAX * KMAX_ALL];
+      __shared__ int g_key[BEAM_MAX * KMAX_ALL];   // local_row * V + token (beam * V < INT_MAX)
+      __shared__ int sel_tok[KMAX_ALL];            // the tokens the earlier groups selected at this step
+      const int G = p.div_groups, mb = beam / G, Kg = 2 * mb, ng = (s == 0 ? 1 : mb) * K;
+      const float alpha = -p.div_strength;
+      for (int g = 0; g < G; ++g) {
+        for (int i = tid; i < ng; i += blockDim.x) {
+          const int lr = i / K, src = (s == 0 ? 0 : lr * G + g) * K + (i - lr * K);
+          const int t = l_tok[src];
+          int cnt = 0;
+          for (int q = 0; q < g * Kg; ++q) cnt += sel_tok[q] == t ? 1 : 0;
+          const float v = l_val[src];
+          g_val[i] = cnt ? __fadd_rn(v, __fmul_rn(alpha, (float)cnt)) : v;
+          g_key[i] = lr * p.vocab + t;
+        }
+        __syncthreads();
+        for (int i = tid; i < ng; i += blockDim.x) {
+          const float v = g_val[i];
+          const int key = g_key[i];
+          int rank = 0;
+          for (int o = 0; o < ng; ++o) {
+            const float vo = g_val[o];
+            const int ko = g_key[o];
+            rank += (vo > v || (vo == v && (ko < key || (ko == key && o < i)))) ? 1 : 0;  // (equal keys: missing candidates, (-inf, pad))
+          }
+          if (rank < Kg) {
+            const int lr = i / K, k = rank * G + g, t = key - lr * p.vocab;
+            c_score[k] = v; c_tok[k] = t; c_beam[k] = (s == 0 || first_row_parent) ? 0 : lr * G + g;
+            sel_tok[g * Kg + rank] = t;
+          }
+        }
+        __syncthreads();
+      }
+    } else {
     // rank of every row candidate among the sentence's rows*K candidates (ordered by value desc, then row asc = flat index asc,
     // then position in the row's list): rank < K -> it is the sentence's candidate number `rank`.  One thread per candidate; a
     // serial K-round head merge by one thread cost ~8 us of dependent LDS round trips.
@@ -885,6 +944,7 @@ __global__ __launch_bounds__(256) void beam_merge_kernel(BeamP p, const float* c
       if (rank < K) { c_score[rank] = v; c_tok[rank] = l_tok[i]; c_beam[rank] = first_row_parent ? 0 : r; }
     }
     __syncthreads();
+    }
     }
     if (tid == 0) {
       // ---- (d) bookkeeping (LDS / registers only: a global access inside these serial loops costs a memory round trip each) ----
@@ -1280,6 +1340,7 @@ int to_params(const cst_beam_desc* d, BeamP& p) {
   p.fin_tokens = d->fin_tokens; p.fin_pos = d->fin_pos; p.fin_score = d->fin_score; p.fin_len = d->fin_len;
   p.ngram = 0; p.prefix_len = 0; p.prefix_tokens = nullptr;  // cst_beam_step sets them
   p.sample_topk = 0; p.sample_topp = 0.0f; p.sample_key = nullptr;
+  p.div_groups = 0; p.div_strength = 0.0f; p.sibling_rate = 0.0f;
   return CST_OK;
 }
 
@@ -1537,6 +1598,23 @@ int cst_beam_step(const cst_beam_desc* d, cst_stream stream) {
       return CST_ERR_UNSUPPORTED;
     }
   }
+  // diverse decoding (ABI 12): both strategies off in a zero-filled tail -> the merge kernels above, launched as before
+  CST_REQUIRE(d->diverse_groups >= 0, "cst_beam_step: diverse_groups %lld (0 = off, else G >= 1)", (long long)d->diverse_groups);
+  const bool groups = d->diverse_groups > 0, siblings = d->diverse_siblings != 0;
+  CST_REQUIRE((samp ? 1 : 0) + (groups ? 1 : 0) + (siblings ? 1 : 0) <= 1,
+              "cst_beam_step: sampling, diverse_groups and diverse_siblings are mutually exclusive search strategies");
+  if (groups) {
+    CST_REQUIRE(d->diverse_groups <= d->beam && d->beam % d->diverse_groups == 0,
+                "cst_beam_step: beam %lld must be divisible by diverse_groups %lld", (long long)d->beam, (long long)d->diverse_groups);
+    CST_REQUIRE(d->diverse_strength >= 0.0f, "cst_beam_step: diverse_strength %g must be >= 0 (a reward would reach tokens outside the "
+                "rows' top 2 * beam lists)", (double)d->diverse_strength);
+    p.div_groups = (int)d->diverse_groups;
+    p.div_strength = d->diverse_strength;
+  }
+  if (siblings) {
+    CST_REQUIRE(d->sibling_rate >= 0.0f, "cst_beam_step: sibling_rate %g must be >= 0", (double)d->sibling_rate);
+    p.sibling_rate = d->sibling_rate;
+  }
   // checkpoint ensembles: members >= 2 (0 and 1 both mean the single matrix `logits`, today's kernels with today's arguments)
   CST_REQUIRE(d->members >= 0 && d->members <= ENS_MAX, "cst_beam_step: %lld ensemble members (at most %d)", (long long)d->members, ENS_MAX);
   EnsP e;
@@ -1588,6 +1666,12 @@ int cst_beam_step(const cst_beam_desc* d, cst_stream stream) {
     if (samp) {
       if (p.prefix_len > 0) hipLaunchKernelGGL((beam_merge_kernel<true, true>), dim3(p.bsz), dim3(256), 0, s, p, (const float*)cand_val, (const int32_t*)cand_tok, ticket);
       else hipLaunchKernelGGL((beam_merge_kernel<false, true>), dim3(p.bsz), dim3(256), 0, s, p, (const float*)cand_val, (const int32_t*)cand_tok, ticket);
+    }
+    else if (groups || siblings) {
+#define CST_MERGE_DIV(PF, DV) hipLaunchKernelGGL((beam_merge_kernel<PF, false, DV>), dim3(p.bsz), dim3(256), 0, s, p, (const float*)cand_val, (const int32_t*)cand_tok, ticket)
+      if (groups) { if (p.prefix_len > 0) CST_MERGE_DIV(true, 1); else CST_MERGE_DIV(false, 1); }
+      else { if (p.prefix_len > 0) CST_MERGE_DIV(true, 2); else CST_MERGE_DIV(false, 2); }
+#undef CST_MERGE_DIV
     }
     else if (p.prefix_len > 0) hipLaunchKernelGGL(beam_merge_kernel<true>, dim3(p.bsz), dim3(256), 0, s, p, (const float*)cand_val, (const int32_t*)cand_tok, ticket);
     else hipLaunchKernelGGL(beam_merge_kernel<false>, dim3(p.bsz), dim3(256), 0, s, p, (const float*)cand_val, (const int32_t*)cand_tok, ticket);

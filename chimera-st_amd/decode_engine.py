@@ -30,7 +30,7 @@ from .optim import PARAM_EPOCH
 class BeamDecodeEngine:
     def __init__(self, decoder, tgt_dict, beam_size, max_len, min_len=1, normalize_scores=True, len_penalty=1.0,
                  unk_penalty=0.0, temperature=1.0, use_graph=True, poll=8, cross_kernel=None, lanes=None, no_repeat_ngram_size=0,
-                 sampling=False, topk=0, topp=0.0):
+                 sampling=False, topk=0, topp=0.0, diverse_groups=0, diverse_strength=0.0, sibling_rate=None):
         # a checkpoint ensemble (--path a.pt:b.pt:c.pt) is a LIST of decoders: every member keeps its own packed weights, K/V caches,
         # encoder K/V and logits buffer; the beam state (tokens / scores / ancestry, step counter, finalized hypotheses) is shared —
         # all members follow the same hypotheses, so one ancestry table serves every member's append-only caches
@@ -49,6 +49,11 @@ class BeamDecodeEngine:
         # --sampling / --sampling-topk / --sampling-topp: cst_beam_step draws one token per row instead of selecting the top 2 * beam
         # (sequence_generator.Sampling is the readable form).  The key of a call's draws lives in a buffer the state owns.
         self.sampling, self.topk, self.topp = bool(sampling), max(int(topk), 0), max(float(topp), 0.0)
+        # --diverse-beam-groups / --diverse-beam-strength and --diversity-rate (sibling_rate None = off; 0 is a legal rate): parameters of
+        # cst_beam_step's merge kernel, for every vocabulary width (sequence_generator.DiverseBeamSearch / DiverseSiblingsSearch are the
+        # readable forms).  cst_beam_step refuses bad values and combinations.
+        self.diverse_groups, self.diverse_strength = max(int(diverse_groups), 0), float(diverse_strength)
+        self.sibling_rate = None if sibling_rate is None else float(sibling_rate)
         # cross attention per step: "flash" = cst_attn_fwd with batch = sentence and the beam rows as the query axis (37 us per
         # layer at 32 x beam 5 x 750 source positions, bf16); "flash_hm" = the same kernel over head-major K/V (contiguous per-head
         # streams: no faster, 0.811 vs 0.812 ms per step); "shared" = cst_dec_cross_attn (VALU kernel, one pass with online
@@ -211,7 +216,8 @@ class BeamDecodeEngine:
         state owns (st["prefix"]), which every call overwrites: a replayed graph reads the new call's prefix."""
         S = tuple(S) if isinstance(S, (list, tuple)) else (S,) * len(self.decs)
         has_mask = tuple(has_mask) if isinstance(has_mask, (list, tuple)) else (has_mask,) * len(self.decs)
-        key = (lane, bsz, S, dtype, device, has_mask, prefix_len, self.no_repeat_ngram_size, self.sampling, self.topk, self.topp)
+        key = (lane, bsz, S, dtype, device, has_mask, prefix_len, self.no_repeat_ngram_size, self.sampling, self.topk, self.topp,
+               self.diverse_groups, self.diverse_strength, self.sibling_rate)
         st = self._state.get(key)
         if st is not None:
             return st
@@ -254,6 +260,10 @@ class BeamDecodeEngine:
         st["sample_key"] = z(1, dt=torch.int32) if self.sampling else None  # (the 32 bits of the key; the kernel reads them unsigned)
         if self.sampling:
             d.sampling, d.sample_topk, d.sample_topp, d.sample_key = 1, self.topk, self.topp, st["sample_key"].data_ptr()
+        if self.diverse_groups > 0:
+            d.diverse_groups, d.diverse_strength = self.diverse_groups, self.diverse_strength
+        if self.sibling_rate is not None:
+            d.diverse_siblings, d.sibling_rate = 1, self.sibling_rate
         st["desc"] = d
         self._state[key] = st
         return st

@@ -9,7 +9,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libcst_hip.so")
-ABI_VERSION = 11  # include/cst.h: CST_ABI_VERSION
+ABI_VERSION = 12  # include/cst.h: CST_ABI_VERSION
 
 F32, BF16 = 0, 1
 ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
@@ -94,6 +94,7 @@ class BeamDesc(ctypes.Structure):
         ("members", c_i64), ("logits_n", c_p * 7), ("lprobs_out", c_p),
         ("no_repeat_ngram", c_i64), ("prefix_tokens", c_p), ("prefix_len", c_i64),
         ("sampling", c_i64), ("sample_topk", c_i64), ("sample_topp", c_f), ("sample_key", c_p),
+        ("diverse_groups", c_i64), ("diverse_strength", c_f), ("diverse_siblings", c_i64), ("sibling_rate", c_f),
     ]
 
 

@@ -10,6 +10,10 @@ in the host loop (the reference copies the token matrix to the host every step a
 device engine runs (cst_beam_step draws inside its row kernel); its draws are counter-based — a function of (key, sentence, slot,
 step), like the dropout masks of rng.py — so the engine and the host loop below draw the same tokens from the same distributions.
 
+`DiverseBeamSearch` (search.py:551-618: --diverse-beam-groups, --diverse-beam-strength) and `DiverseSiblingsSearch` (search.py:745-814:
+--diversity-rate) are the two diverse strategies; the engine runs both inside the per-sentence merge kernel of cst_beam_step
+(include/cst.h, ABI 12), the classes below are the host loop's form of the same selections.
+
 Differences that do not change results: finished sentences are masked out instead of being removed from the batch
 (the reference shrinks the batch, :427-463 — an optimisation only; every sentence's search is independent)."""
 import math
@@ -117,6 +121,60 @@ class Sampling:
         return scores_buf, tok, beams_buf
 
 
+class DiverseBeamSearch:
+    """search.py:551-618, Hamming diversity.  The `beam` rows of a sentence are dealt to `num_groups` groups (group g: rows g, g + G,
+    ...).  The groups search one after the other, each a beam search of width beam / G over its own rows, and every token loses
+    diversity_strength per candidate that an earlier group selected with that token at this step (all 2 * beam / G candidates of a group
+    count, whatever their value).  The groups' candidate lists are interleaved: the j-th candidate of group g is the sentence's
+    candidate j * G + g, its parent row local_row * G + g.  The penalised value is the score a hypothesis carries on."""
+
+    def __init__(self, tgt_dict, num_groups, diversity_strength):
+        self.pad, self.unk, self.eos = tgt_dict.pad(), tgt_dict.unk(), tgt_dict.eos()
+        self.vocab_size = len(tgt_dict)
+        self.num_groups, self.diversity_strength = int(num_groups), float(diversity_strength)
+        if self.num_groups < 1:
+            raise ValueError("DiverseBeamSearch needs at least one group, got %d" % self.num_groups)
+        self.beam = BeamSearch(tgt_dict)
+
+    def step(self, step: int, lprobs, scores):
+        bsz, beam_size, V = lprobs.size()
+        G = self.num_groups
+        if beam_size % G != 0:
+            raise ValueError("DiverseBeamSearch requires --beam to be divisible by the number of groups")
+        counts = torch.zeros(bsz, V, dtype=lprobs.dtype, device=lprobs.device)  # selections of the earlier groups, per token
+        out = []
+        for g in range(G):
+            lp = lprobs[:, g::G, :]
+            if g > 0:
+                lp = torch.add(lp, counts.unsqueeze(1), alpha=-self.diversity_strength)
+            sc, tok, parent = self.beam.step(step, lp, scores[:, g::G, :] if step > 0 else None)
+            out.append((sc, tok, parent * G + g))
+            counts.scatter_add_(1, tok, torch.ones_like(sc))
+        return tuple(torch.stack([o[i] for o in out], dim=2).view(bsz, -1) for i in range(3))
+
+
+class DiverseSiblingsSearch:
+    """search.py:745-814.  Step 0 is plain beam search.  Later every row lists its own best 2 * beam continuations (cumulative score
+    added), the one at position p (from 0) loses (p + 1) * diversity_rate, and the sentence's best 2 * beam of the beam * 2 * beam
+    penalised values are its candidates: the siblings of one hypothesis compete on unequal terms.  Rate 0 is plain beam search."""
+
+    def __init__(self, tgt_dict, diversity_rate):
+        self.pad, self.unk, self.eos = tgt_dict.pad(), tgt_dict.unk(), tgt_dict.eos()
+        self.vocab_size = len(tgt_dict)
+        self.diversity_rate = float(diversity_rate)
+        self.beam = BeamSearch(tgt_dict)
+
+    def step(self, step: int, lprobs, scores):
+        if step == 0:
+            return self.beam.step(step, lprobs, scores)
+        bsz, beam_size, V = lprobs.size()
+        k = min(2 * beam_size, beam_size * V - 1)
+        val, tok = torch.topk(lprobs + scores[:, :, step - 1].unsqueeze(-1), k, dim=2)          # [bsz, beam, k], sorted
+        val = val - torch.arange(1, k + 1, device=val.device).to(val) * self.diversity_rate
+        scores_buf, pick = torch.topk(val.view(bsz, -1), k)
+        return scores_buf, tok.view(bsz, -1).gather(1, pick), pick // k
+
+
 class SequenceGenerator:
     def __init__(self, models, tgt_dict, beam_size=1, max_len_a=0, max_len_b=200, min_len=1, normalize_scores=True,
                  len_penalty=1.0, unk_penalty=0.0, temperature=1.0, match_source_len=False, no_repeat_ngram_size=0,
@@ -145,10 +203,21 @@ class SequenceGenerator:
         self.search = BeamSearch(tgt_dict) if search_strategy is None else search_strategy
         # fused=True (default): the device-resident loop of decode_engine.py (one captured HIP graph per step, no per-step host
         # sync); fused=False: the module-by-module mirror of the reference loop below (same kernels, host-driven) — kept as the
-        # readable restatement and as the cross-check of the engine.  A custom search strategy needs the host loop — except Sampling
-        # (exactly that class: a subclass may draw differently), which cst_beam_step runs itself.
+        # readable restatement and as the cross-check of the engine.  A custom search strategy needs the host loop — except Sampling,
+        # DiverseBeamSearch and DiverseSiblingsSearch (exactly those classes: a subclass may select differently), which cst_beam_step
+        # runs itself.
         self.sampling = isinstance(self.search, Sampling)  # (the host loop hands key and max_len to any Sampling, a subclass included)
-        self.fused = bool(fused) and (search_strategy is None or type(self.search) is Sampling) and (eos is None or eos == tgt_dict.eos())
+        on_engine = search_strategy is None or type(self.search) in (Sampling, DiverseBeamSearch, DiverseSiblingsSearch)
+        # (a negative strength or rate is a reward: the reference accepts it, cst_beam_step does not — a reward can lift tokens from
+        #  outside the rows' top 2 * beam lists or unsort them — so such a search takes the host loop)
+        if type(self.search) is DiverseBeamSearch and not self.search.diversity_strength >= 0:
+            on_engine = False
+        if type(self.search) is DiverseSiblingsSearch and not self.search.diversity_rate >= 0:
+            on_engine = False
+        self.fused = bool(fused) and on_engine and (eos is None or eos == tgt_dict.eos())
+        if isinstance(self.search, DiverseBeamSearch) and self.beam_size % self.search.num_groups != 0:
+            raise ValueError("DiverseBeamSearch requires --beam to be divisible by the number of groups (beam %d, %d groups)"
+                             % (self.beam_size, self.search.num_groups))
         # sampling: the key of a call's draws = hash of (seed, the call's ordinal in this generator)
         self.seed, self.calls = int(seed), 0
         self._engine = None
@@ -237,7 +306,10 @@ class SequenceGenerator:
                                                     use_graph=self.use_graph, cross_kernel=self.cross_kernel,
                                                     no_repeat_ngram_size=self.no_repeat_ngram_size, sampling=self.sampling,
                                                     topk=self.search.sampling_topk if self.sampling else 0,
-                                                    topp=self.search.sampling_topp if self.sampling else 0.0)
+                                                    topp=self.search.sampling_topp if self.sampling else 0.0,
+                                                    diverse_groups=self.search.num_groups if type(self.search) is DiverseBeamSearch else 0,
+                                                    diverse_strength=getattr(self.search, "diversity_strength", 0.0),
+                                                    sibling_rate=self.search.diversity_rate if type(self.search) is DiverseSiblingsSearch else None)
                 return self._engine.generate(encoder_outs if len(encoder_outs) > 1 else encoder_outs[0], bsz, prefix_tokens=prefix_tokens,
                                              sample_key=key)
         new_order = torch.arange(bsz, device=device).view(-1, 1).repeat(1, beam_size).view(-1)

@@ -97,15 +97,29 @@ class FairseqTask:
                                     required_batch_size_multiple, seed, num_shards, shard_id, epoch)
 
     def build_generator(self, models, args, seq_gen_cls=None, extra_gen_cls_kwargs=None):
-        """fairseq_task.py:309-412: beam search, or Sampling with --sampling (:329-357)."""
-        from .sequence_generator import Sampling, SequenceGenerator
+        """fairseq_task.py:309-412: beam search, Sampling with --sampling (:329-357), DiverseBeamSearch with --diverse-beam-groups
+        (:358-361), DiverseSiblingsSearch with --diversity-rate (:373-376) — the reference's selection: exclusivity is tested with
+        `diversity_rate > 0`, the sibling search is chosen with `diversity_rate > -1` (so rate 0 builds it and equals beam search)."""
+        from .sequence_generator import DiverseBeamSearch, DiverseSiblingsSearch, Sampling, SequenceGenerator
 
         sampling = getattr(args, "sampling", False)
         sampling_topk = getattr(args, "sampling_topk", -1)
         sampling_topp = getattr(args, "sampling_topp", -1.0)
+        diverse_beam_groups = getattr(args, "diverse_beam_groups", -1)
+        diverse_beam_strength = getattr(args, "diverse_beam_strength", 0.5)
+        diversity_rate = getattr(args, "diversity_rate", -1.0)
+        if sum(int(bool(c)) for c in (sampling, diverse_beam_groups > 0, diversity_rate > 0)) > 1:
+            raise ValueError("Provided Search parameters are mutually exclusive.")
         assert sampling_topk < 0 or sampling, "--sampling-topk requires --sampling"
         assert sampling_topp < 0 or sampling, "--sampling-topp requires --sampling"
-        search = Sampling(self.target_dictionary, sampling_topk, sampling_topp) if sampling else None
+        if sampling:
+            search = Sampling(self.target_dictionary, sampling_topk, sampling_topp)
+        elif diverse_beam_groups > 0:
+            search = DiverseBeamSearch(self.target_dictionary, diverse_beam_groups, diverse_beam_strength)
+        elif diversity_rate > -1:
+            search = DiverseSiblingsSearch(self.target_dictionary, diversity_rate)
+        else:
+            search = None
         return SequenceGenerator(
             models, self.target_dictionary, beam_size=getattr(args, "beam", 5), max_len_a=getattr(args, "max_len_a", 0),
             max_len_b=getattr(args, "max_len_b", 200), min_len=getattr(args, "min_len", 1),

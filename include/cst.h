@@ -33,9 +33,10 @@ extern "C" {
  * 6: cst_dec_ln_q_cross_attn; 7: cst_fbank_desc, cst_fbank, cst_fbank_workspace_bytes; 8: cst_conv0_ln_gelu_fwd / _bwd,
  * cst_ln_gelu_fwd / _bwd and their workspaces; 9: cst_beam_desc.members / logits_n / lprobs_out — checkpoint ensembles;
  * 10: cst_beam_desc.no_repeat_ngram / prefix_tokens / prefix_len — n-gram blocking and forced prefixes;
- * 11: cst_beam_desc.sampling / sample_topk / sample_topp / sample_key — sampling decode).
+ * 11: cst_beam_desc.sampling / sample_topk / sample_topp / sample_key — sampling decode;
+ * 12: cst_beam_desc.diverse_groups / diverse_strength / diverse_siblings / sibling_rate — diverse beam groups and diverse siblings).
  * cst_version() returns the value the library was built with; chimera-st_amd/lib.py refuses a mismatch. */
-#define CST_ABI_VERSION 11
+#define CST_ABI_VERSION 12
 
 typedef enum { CST_F32 = 0, CST_BF16 = 1 } cst_dtype;
 
@@ -551,6 +552,31 @@ int cst_adam_step(float* master, float* exp_avg, float* exp_avg_sq, const void* 
  *   decide the cut or the draw have a fixed order (no floating-point atomics; longest addition chain 64), so a call is reproducible.
  *   sample_topk < 0 or > vocab, sampling with a null sample_key: CST_ERR_BAD_ARG.  Vocabularies beyond the register-resident row
  *   kernels (more than 5 * 512 16-byte vectors per row): CST_ERR_UNSUPPORTED — nothing is launched in either case.
+ *   Diverse decoding (ABI 12; both strategies are off in a zero-filled tail, and a step with both off launches exactly the kernels above).
+ *   Both act on the rows' sorted top-2*beam lists inside the per-sentence merge kernel: still two launches, every row kernel (wide
+ *   vocabularies, ensembles, constraints) unchanged, and everything after the selection — eos handling, finalisation, cands_to_ignore,
+ *   the next rows — runs over the resulting 2*beam candidates as before.  The PENALISED value is the cumulative score that is written.
+ *   Beam groups (search.py DiverseBeamSearch.step :568-618, Hamming diversity): diverse_groups = G >= 1, mb = beam / G.  Group g owns the
+ *   sentence's rows r with r % G == g (lprobs[:, g::G]); the groups are processed in the order g = 0 .. G-1.  A candidate (row r, token
+ *   t) of group g has the value
+ *     fl(fl(lp + cumulative score of r) + fl(-diverse_strength * count_g(t))),
+ *   count_g(t) = the number of candidates selected at this step by the groups 0 .. g-1 of the sentence whose token is t — all 2*mb of
+ *   each group, duplicates, eos and -inf candidates included (scatter_add_ :610).  ORDER OF THE ADDITIONS: the reference forms
+ *   fl(fl(lp + alpha * count) + score); here the penalty is added to the row kernel's candidate value, which differs by the rounding of
+ *   one fp32 addition (at most one ulp of the cumulative score).  The group keeps its top 2*mb of its mb * vocab candidates, ties to the
+ *   smaller local_row * vocab + token; its j-th selection is the sentence's candidate j * G + g (the interleave of torch.stack(...,
+ *   dim=2) :615-617) with parent row local_row * G + g.  At step 0 every group searches the sentence's first row, which is the recorded
+ *   parent (in a decode the rows are equal there).  G == 1 equals plain beam search bit for bit.  The rows' top 2*beam suffice because
+ *   diverse_strength >= 0 only lowers values (argument at beam_merge_kernel).  diverse_groups < 0 or > beam, beam % G != 0 (the
+ *   reference's ValueError), diverse_strength < 0: CST_ERR_BAD_ARG.
+ *   Diverse siblings (search.py DiverseSiblingsSearch.step :765-814): on iff diverse_siblings != 0 — a switch of its own, so that a
+ *   zero-filled tail is off although 0 is a legal rate; sibling_rate = R is read only then.  Step 0 is plain beam search; at later steps
+ *   the candidate at position p (from 0) of a row's sorted list has the value fl(v - fl((p + 1) * R)), v = fl(lp + cumulative score),
+ *   and the sentence's top 2*beam is taken over the beam * 2*beam penalised candidates, ties to the smaller row * 2*beam + p; parent =
+ *   the row.  R == 0 equals plain beam search bit for bit.  R < 0 (or NaN): CST_ERR_BAD_ARG.
+ *   sampling, diverse_groups > 0 and diverse_siblings != 0 are mutually exclusive (fairseq_task.py:338-350): two of them together are
+ *   CST_ERR_BAD_ARG.  Either diverse strategy composes with members, no_repeat_ngram and prefix_tokens (where the step's prefix token is
+ *   eos, the parent is the sentence's first row as above).  Nothing is launched on an error.
  * ------------------------------------------------------------------------------------------ */
 typedef struct {
   int dtype;                         /* storage type of logits */
@@ -574,6 +600,10 @@ typedef struct {
   int64_t sample_topk;               /* ABI 11: 0 = off, else draw among the k most probable tokens (at most vocab) */
   float sample_topp;                 /* ABI 11: <= 0 = off, else draw from the nucleus of mass p (wins over sample_topk) */
   const uint32_t* sample_key;        /* ABI 11: device [1], the 32-bit key of the draws; read at every step (required when sampling) */
+  int64_t diverse_groups;            /* ABI 12: 0 = off, else G >= 1 beam groups (beam % G == 0) */
+  float diverse_strength;            /* ABI 12: S >= 0, the Hamming diversity penalty per earlier selection of the token */
+  int64_t diverse_siblings;          /* ABI 12: 0 = off, else the sibling penalty below is applied */
+  float sibling_rate;                /* ABI 12: R >= 0, read when diverse_siblings != 0 (a negative rate is an error, not "off") */
 } cst_beam_desc;
 int64_t cst_beam_workspace(int64_t bsz, int64_t beam);
 int cst_beam_init(const cst_beam_desc* d, cst_stream stream);

@@ -4,6 +4,7 @@
 
   python tools/bench_decode.py [--batch 32] [--frames 3000] [--beam 5] [--max-len 200] [--reps 3] [--mirror] [--ensemble N]
                                [--no-repeat-ngram-size N] [--sampling [--sampling-topk K] [--sampling-topp P]]
+                               [--diverse-beam-groups G [--diverse-beam-strength S]] [--diversity-rate R]
 
 Prints one JSON line: utterances/s and generated tokens/s of the device-resident loop (decode_engine.py: one captured HIP
 graph per step), the per-step time, the encoder time, and — with --mirror — the same numbers for the host-driven
@@ -11,7 +12,8 @@ module-by-module loop (fused=False).  Random-init weights emit eos only when for
 max_len + 1 steps: the reported rate is the worst case for the configured max_len.
 --ensemble N decodes N independently seeded copies of the model as a checkpoint ensemble (every member's encoder and decoder run;
 one beam step over the N logits matrices) and adds "models" and "nodes_per_step" to the line.
---sampling decodes with the Sampling strategy (every hypothesis an independent sample) on the same engine."""
+--sampling decodes with the Sampling strategy (every hypothesis an independent sample) on the same engine; --diverse-beam-groups and
+--diversity-rate with DiverseBeamSearch / DiverseSiblingsSearch (both inside the beam step's merge kernel)."""
 import argparse
 import importlib
 import json
@@ -43,8 +45,15 @@ def main():
     ap.add_argument("--sampling", action="store_true", help="sample instead of beam search")
     ap.add_argument("--sampling-topk", type=int, default=-1)
     ap.add_argument("--sampling-topp", type=float, default=-1.0)
+    ap.add_argument("--diverse-beam-groups", type=int, default=-1, help="diverse beam search with this many groups (--beam divisible)")
+    ap.add_argument("--diverse-beam-strength", type=float, default=0.5)
+    ap.add_argument("--diversity-rate", type=float, default=-1.0, help="diverse siblings search with this rate (negative = off)")
     ap.add_argument("--profile", action="store_true", help="per-class GPU time of one eager decode loop (hipEvent pairs)")
     args = ap.parse_args()
+    if sum((args.sampling, args.diverse_beam_groups > 0, args.diversity_rate > 0)) > 1:
+        ap.error("--sampling, --diverse-beam-groups and --diversity-rate are mutually exclusive")
+    if args.diverse_beam_groups > 0 and args.beam % args.diverse_beam_groups != 0:
+        ap.error("--beam must be divisible by --diverse-beam-groups")
 
     importlib.import_module("chimera-st_amd")
     s2t = importlib.import_module("chimera-st_amd.s2t_transformer")
@@ -52,7 +61,8 @@ def main():
     reg = importlib.import_module("chimera-st_amd.registry")
     lib = importlib.import_module("chimera-st_amd.lib")
     SG = importlib.import_module("chimera-st_amd.sequence_generator").SequenceGenerator
-    Sampling = importlib.import_module("chimera-st_amd.sequence_generator").Sampling
+    sg_mod = importlib.import_module("chimera-st_amd.sequence_generator")
+    Sampling, DiverseBeamSearch, DiverseSiblingsSearch = sg_mod.Sampling, sg_mod.DiverseBeamSearch, sg_mod.DiverseSiblingsSearch
     lib.load()
     dt = torch.bfloat16 if args.dtype == "bf16" else torch.float32
     torch.manual_seed(1)
@@ -91,7 +101,15 @@ def main():
         torch.cuda.synchronize()
         enc_s = (time.perf_counter() - t0) / args.reps
 
-    strategy = lambda: Sampling(task.target_dictionary, args.sampling_topk, args.sampling_topp) if args.sampling else None
+    def strategy():
+        if args.sampling:
+            return Sampling(task.target_dictionary, args.sampling_topk, args.sampling_topp)
+        if args.diverse_beam_groups > 0:
+            return DiverseBeamSearch(task.target_dictionary, args.diverse_beam_groups, args.diverse_beam_strength)
+        if args.diversity_rate > -1:
+            return DiverseSiblingsSearch(task.target_dictionary, args.diversity_rate)
+        return None
+
     fused = SG(models, task.target_dictionary, beam_size=args.beam, max_len_a=0, max_len_b=args.max_len, use_graph=not args.no_graph,
                cross_kernel=args.cross_kernel, no_repeat_ngram_size=args.no_repeat_ngram_size, search_strategy=strategy())
     t_f, ntok = timed(fused)
@@ -102,6 +120,12 @@ def main():
            "encoder_s": enc_s, "ms_per_step": (t_f - enc_s) / steps * 1e3, "hyp_rows_per_step": args.batch * args.beam}
     if args.sampling:
         out["config"].update(sampling=True, sampling_topk=args.sampling_topk, sampling_topp=args.sampling_topp)
+        out["nodes_per_step"] = fused._engine.nodes_per_step(dt, args.batch * args.beam)
+    if args.diverse_beam_groups > 0:
+        out["config"].update(diverse_beam_groups=args.diverse_beam_groups, diverse_beam_strength=args.diverse_beam_strength)
+        out["nodes_per_step"] = fused._engine.nodes_per_step(dt, args.batch * args.beam)
+    elif args.diversity_rate > -1 and not args.sampling:
+        out["config"].update(diversity_rate=args.diversity_rate)
         out["nodes_per_step"] = fused._engine.nodes_per_step(dt, args.batch * args.beam)
     if args.no_repeat_ngram_size:
         out["config"]["no_repeat_ngram_size"] = args.no_repeat_ngram_size
