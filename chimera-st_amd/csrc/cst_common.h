@@ -88,6 +88,12 @@ __device__ __forceinline__ void load8(const bf16_t* p, float (&v)[8]) {
     v[2 * i + 1] = __uint_as_float(r[i] & 0xffff0000u);
   }
 }
+// 16-byte vector of T -> floats
+template <typename T>
+__device__ __forceinline__ void ld_vec(const T* p, float (&v)[DT<T>::VEC]) {
+  if constexpr (DT<T>::VEC == 8) { float v8[8]; load8(p, v8); for (int e = 0; e < 8; ++e) v[e] = v8[e]; }
+  else { const f32x4 a = *reinterpret_cast<const f32x4*>(p); for (int e = 0; e < 4; ++e) v[e] = a[e]; }
+}
 __device__ __forceinline__ void store8(float* p, const float (&v)[8]) {
   f32x4 a = {v[0], v[1], v[2], v[3]}, b = {v[4], v[5], v[6], v[7]};
   *reinterpret_cast<f32x4*>(p) = a;

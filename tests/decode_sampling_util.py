@@ -5,7 +5,7 @@ of tests/decode_constraints_util.py.
 
 For every draw the restatement also says whether the draw is DECIDABLE: the kernel forms its sums in fp32 in its own fixed order, so
 where a decision hangs on less than the rounding of such a sum, two correct evaluations may differ.  With
-    DELTA = (longest addition chain stated in the kernel comment of csrc/decode.hip + 8) * 2^-24 = (64 + 8) * 2^-24 = 4.3e-6
+    DELTA = (longest addition chain stated in the kernel comment of csrc/beam_search.hip + 8) * 2^-24 = (64 + 8) * 2^-24 = 4.3e-6
 a draw is decidable when no exclusive prefix mass of the descending order lies within DELTA * (the row's mass) of p (top-p), and
 u * Z is not within DELTA * Z of an edge of the kept CDF.  (The 8 covers what is not an addition: the fp32 log-softmax the kernel's
 q = exp(x) starts from — x carries about an ulp of a number below 16, 1e-6, which scales q by 1 +- 1e-6 — and expf itself.)
@@ -17,7 +17,7 @@ import torch
 
 from decode_constraints_util import BEAM, BSZ, EOS, HOT, MAX_LEN, PAD, PREFIX, UNK, banned_tokens  # noqa: F401
 
-CHAIN = 64  # csrc/decode.hip, comment of beam_row_sample_tail: "LONGEST ADDITION CHAIN ... 64"
+CHAIN = 64  # csrc/beam_search.hip, comment of beam_row_sample_tail: "LONGEST ADDITION CHAIN ... 64"
 DELTA = (CHAIN + 8) * 2.0 ** -24
 _M32 = 0xFFFFFFFF
 

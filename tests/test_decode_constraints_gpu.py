@@ -1,4 +1,4 @@
-"""GPU tests of the decoding constraints --no-repeat-ngram-size / --prefix-size (decode.hip cst_beam_step, decode_engine.py,
+"""GPU tests of the decoding constraints --no-repeat-ngram-size / --prefix-size (beam_search.hip cst_beam_step, decode_engine.py,
 sequence_generator.py, cli.py):
   * cst_beam_step called directly, every dispatch family, against the torch restatement of tests/decode_constraints_util.py;
   * the engine and the host loop against the hypotheses of the REAL reference's SequenceGenerator (decode_constraints_tiny.npz);

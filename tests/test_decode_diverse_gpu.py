@@ -1,4 +1,4 @@
-"""GPU tests of the diverse decoding strategies --diverse-beam-groups / --diverse-beam-strength and --diversity-rate (decode.hip
+"""GPU tests of the diverse decoding strategies --diverse-beam-groups / --diverse-beam-strength and --diversity-rate (beam_search.hip
 cst_beam_step ABI 12, decode_engine.py, sequence_generator.py, cli.py):
   * cst_beam_step called directly, one case per row-kernel family, step by step against the torch restatement of
     tests/decode_diverse_util.py; identity of G = 1 and R = 0 with a plain step; bad arguments;

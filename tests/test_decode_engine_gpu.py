@@ -1,4 +1,4 @@
-"""GPU tests of the device-resident decode loop (decode.hip + decode_engine.py):
+"""GPU tests of the device-resident decode loop (decode.hip, beam_search.hip + decode_engine.py):
   * cst_beam_init/step against the oracle's search loop (oracle.beam_search_with) on a synthetic next-token table at the
     real vocabulary size — bit-exact token ids, finalisation order, scores to fp32 rounding;
   * cst_dec_self_attn / cst_dec_embed against plain torch fp32 restatements, with a shuffled ancestry table;
@@ -99,6 +99,38 @@ def test_beam_step_matches_oracle_search(KL, beam, V, dtype):
             assert len(hyps[r][1]) == len(ref[b][r]["tokens"])
             assert abs(hyps[r][0] - ref[b][r]["score"]) < 2e-5 * max(1.0, abs(ref[b][r]["score"]))
             assert float((hyps[r][2] - ref[b][r]["positional_scores"]).abs().max()) < 1e-4
+
+
+@pytest.mark.parametrize("dtype,V", [(torch.float32, 60), (torch.float32, 10248), (torch.bfloat16, 20488)], ids=["fp32-NV1", "fp32-wide", "bf16-wide"])
+def test_beam_step_row_with_minus_inf_logits(KL, dtype, V):
+    """Rows whose tokens 4 .. min(V, 512) - 1 are -inf: in the wide row kernel the first element of almost every thread's strided
+    statistics loop is then -inf while the thread's running maximum is still -inf.  torch.log_softmax handles such rows, so after one
+    step the next rows of each sentence hold the top `beam` tokens of log_softmax of the sentence's first row (pad and eos masked:
+    step 0 < min_len), ids exact, scores to 1e-5 (the bar decode_constraints_util states for cumulative scores)."""
+    k, L = KL
+    bsz, beam, max_len, min_len = 2, 2, 3, 1
+    g = torch.Generator().manual_seed(1)
+    x = (2.0 * torch.randn(bsz * beam, V, generator=g)).to(dtype)
+    x[:, 4:min(V, 512)] = -math.inf
+    ref = torch.log_softmax(x.float(), dim=-1)[::beam]  # the first row of every sentence
+    ref[:, 1] = -math.inf  # pad
+    ref[:, 2] = -math.inf  # eos
+    want_val, want_tok = ref.sort(dim=-1, descending=True, stable=True)
+    gap = float((want_val[:, beam - 1] - want_val[:, beam]).min())
+    assert gap > 1e-4, gap  # the ids are decidable
+    logits = torch.zeros(bsz * beam, (V + 7) // 8 * 8, dtype=dtype, device="cuda")
+    logits[:, :V] = x.cuda()
+    st, d = _beam_state(L, bsz, beam, V, max_len, min_len, dtype, logits)
+    lib = L.load()
+    L.check(lib.cst_beam_init(ctypes.byref(d), L.stream_ptr()), "cst_beam_init")
+    L.check(lib.cst_beam_step(ctypes.byref(d), L.stream_ptr()), "cst_beam_step")
+    assert int(st["step"].item()) == 1
+    got_tok = st["tokens"][1, :, 1].view(bsz, beam).cpu()
+    got_val = st["scores"][1, :, 0].view(bsz, beam).cpu()
+    print("tokens %s (want %s)  max |score - log_softmax| %.2e  gap %.2e" % (
+        got_tok.tolist(), want_tok[:, :beam].tolist(), float((got_val - want_val[:, :beam]).abs().nan_to_num(math.inf).max()), gap))
+    assert torch.equal(got_tok, want_tok[:, :beam])
+    assert float((got_val - want_val[:, :beam]).abs().max()) <= 1e-5
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])

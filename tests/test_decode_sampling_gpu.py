@@ -1,4 +1,4 @@
-"""GPU tests of sampling decode (--sampling, --sampling-topk, --sampling-topp, --nbest; decode.hip cst_beam_step with
+"""GPU tests of sampling decode (--sampling, --sampling-topk, --sampling-topp, --nbest; beam_search.hip cst_beam_step with
 cst_beam_desc.sampling, decode_engine.py, sequence_generator.py Sampling, cli.py):
   * cst_beam_step called directly, every register-resident dispatch family, against the fp64 restatement of decode_sampling_util.py;
   * the frequencies of 10 240 draws against the kept distribution (Pearson);
