@@ -248,6 +248,7 @@ def generate_parser():
     p.add_argument("--diverse-beam-strength", type=float, default=0.5, help="the penalty per earlier choice of a token (diverse beam search)")
     p.add_argument("--diversity-rate", type=float, default=-1.0, help="diverse siblings search: the p-th best continuation of a hypothesis "
                    "loses p times this rate (0 equals beam search; negative = off)")
+    p.add_argument("--score-reference", action="store_true", help="just score the reference translation")
     p.add_argument("--nbest", type=int, default=1, help="hypotheses printed per sentence (at most --beam)")
     p.add_argument("--remove-bpe", "--post-process", nargs="?", const="@@ ", default=None, dest="post_process")
     p.add_argument("--scoring", default="bleu")
@@ -287,6 +288,8 @@ def generate_main(argv=None):
     ds = task.load_dataset(args.gen_subset)
     itr = task.get_batch_iterator(ds, max_tokens=args.max_tokens, max_sentences=args.batch_size,
                                   max_positions=(args.max_source_positions, args.max_target_positions), ignore_invalid_inputs=True)
+    if args.score_reference and any(d.tgt_texts is None for d in getattr(ds, "datasets", [ds])):  # before any batch is decoded
+        raise ValueError("--score-reference needs the references of subset %s: it has no target text" % args.gen_subset)
     gen = task.build_generator(models, args)
     tgt_dict = task.target_dictionary
     if args.results_path:
@@ -318,6 +321,11 @@ def generate_main(argv=None):
             if sample.get("target") is None:
                 raise ValueError("--prefix-size needs the references of the subset (no target in this batch)")
             prefix = sample["target"][:, :args.prefix_size].cuda()
+        if args.score_reference:  # fairseq_cli/generate.py hands the scorer the collater's whole sample
+            if sample.get("target") is None:
+                raise ValueError("--score-reference needs the references of the subset (no target in this batch)")
+            s["net_input"]["prev_output_tokens"] = sample["net_input"]["prev_output_tokens"].cuda()
+            s["target"] = sample["target"].cuda()
         results = task.inference_step(gen, models, s, prefix_tokens=prefix)
         for i, sid in enumerate(sample["id"].tolist()):
             ref = tgt_dict.string(sample["target"][i]) if sample.get("target") is not None else None
@@ -341,7 +349,7 @@ def generate_main(argv=None):
                "sentences_per_s": nsent / max(dt, 1e-9), "tokens_per_s": ntok / max(dt, 1e-9), "beam": args.beam, "models": len(models),
                "sampling": bool(args.sampling), "nbest": args.nbest, "seed": args.seed,
                "diverse_beam_groups": args.diverse_beam_groups, "diverse_beam_strength": args.diverse_beam_strength,
-               "diversity_rate": args.diversity_rate,
+               "diversity_rate": args.diversity_rate, "score_reference": bool(args.score_reference),
                "bleu4_whitespace": corpus_bleu(hyps, refs) if any(refs) else None, "ignored_flags": ignored}
     print(json.dumps(summary), file=out, flush=True)
     if out is not sys.stdout:

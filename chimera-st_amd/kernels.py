@@ -776,6 +776,47 @@ def ls_ce_bwd(logits, target, lse, gscale, eps, pad):
     return d
 
 
+def _score_rows(x):
+    """[B, T, V] -> the 2-D view [B*T, V] (unit column stride, one row stride); a copy only where [B, T] is not one run of rows."""
+    B, T, V = x.shape
+    step = x.stride(1) if T > 1 else x.stride(0)
+    if x.stride(2) == 1 and step >= V and (B == 1 or T == 1 or x.stride(0) == T * step):
+        return x.as_strided((B * T, V), (step, 1))
+    return x.contiguous().view(B * T, V)
+
+
+def score_tokens(logits_list, target, pad):
+    """Scores of given target tokens under one model or an ensemble (cst_score_tokens): logits_list = N <= 8 tensors [B, T, V] of one
+    dtype and shape, target int64 [B, T] -> (pos fp32 [B, T], score fp32 [B], len int32 [B]), views of ONE buffer `packed` (fp32
+    [B*T + 2B], also returned: one transfer brings all three to the host).  The kernel cannot validate device data, so the target ids
+    are checked here: an id outside [0, V) that is not `pad` raises ValueError and nothing is launched."""
+    logits_list = list(logits_list)
+    if not 1 <= len(logits_list) <= 8:
+        raise ValueError("score_tokens takes 1 to 8 ensemble members, got %d" % len(logits_list))
+    B, T, V = logits_list[0].shape
+    if tuple(target.shape) != (B, T) or target.dtype != torch.int64:
+        raise ValueError("score_tokens: target must be int64 [%d, %d], got %s %s" % (B, T, target.dtype, tuple(target.shape)))
+    for x in logits_list:
+        if x.shape != logits_list[0].shape or x.dtype != logits_list[0].dtype:
+            raise ValueError("score_tokens: the members' logits differ in shape or dtype")
+    rows = [_score_rows(x) for x in logits_list]
+    if len({x.stride(0) for x in rows}) > 1:  # one row stride serves all members
+        rows = [x.contiguous() for x in rows]
+    ld = max(rows[0].stride(0), V)  # (a single row has no stride to speak of)
+    target = target.contiguous()
+    live = target[target.ne(pad)]
+    if live.numel():
+        lo, hi = torch.stack([live.min(), live.max()]).tolist()
+        if lo < 0 or hi >= V:
+            raise ValueError("score_tokens: target ids must lie in [0, %d) or be the pad index %d; found %d .. %d" % (V, pad, lo, hi))
+    packed = torch.empty(B * T + 2 * B, dtype=torch.float32, device=target.device)
+    pos, score, length = packed[:B * T].view(B, T), packed[B * T:B * T + B], packed[B * T + B:].view(torch.int32)
+    others = (L.c_p * 7)(*[x.data_ptr() for x in rows[1:]])
+    L.check(L.load().cst_score_tokens(L.ptr(rows[0]), others, len(rows), ld, L.ptr(target), int(pad), L.ptr(pos), L.ptr(score),
+                                      L.ptr(length), B, T, V, L.dtype_code(rows[0].dtype), L.stream_ptr()), "cst_score_tokens")
+    return pos, score, length, packed
+
+
 def sumsq(x, out):
     lib = L.load()
     ws = workspace(lib.cst_sumsq_workspace(), x.device)

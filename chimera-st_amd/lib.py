@@ -9,7 +9,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libcst_hip.so")
-ABI_VERSION = 12  # include/cst.h: CST_ABI_VERSION
+ABI_VERSION = 13  # include/cst.h: CST_ABI_VERSION
 
 F32, BF16 = 0, 1
 ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
@@ -171,6 +171,7 @@ SYMBOLS = [
     ("cst_embed_bwd", c_int, [c_p, c_p, c_p, c_f, c_i64, c_i64, c_i64, c_i64, c_f, ctypes.c_uint32, c_int, c_int, c_p]),
     ("cst_ls_ce_fwd", c_int, [c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_f, c_i64, c_int, c_p]),
     ("cst_ls_ce_bwd", c_int, [c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_f, c_i64, c_int, c_p]),
+    ("cst_score_tokens", c_int, [c_p, ctypes.POINTER(c_p), c_i64, c_i64, c_p, c_i64, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_int, c_p]),
     ("cst_contrastive_fwd", c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_f, c_int, c_p]),
     ("cst_contrastive_bwd", c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_f, c_int, c_p]),
     ("cst_sumsq_workspace", c_i64, []),

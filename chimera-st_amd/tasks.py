@@ -97,11 +97,14 @@ class FairseqTask:
                                     required_batch_size_multiple, seed, num_shards, shard_id, epoch)
 
     def build_generator(self, models, args, seq_gen_cls=None, extra_gen_cls_kwargs=None):
-        """fairseq_task.py:309-412: beam search, Sampling with --sampling (:329-357), DiverseBeamSearch with --diverse-beam-groups
+        """fairseq_task.py:309-412: SequenceScorer with --score-reference (:313-320), else beam search, Sampling with --sampling (:329-357), DiverseBeamSearch with --diverse-beam-groups
         (:358-361), DiverseSiblingsSearch with --diversity-rate (:373-376) — the reference's selection: exclusivity is tested with
         `diversity_rate > 0`, the sibling search is chosen with `diversity_rate > -1` (so rate 0 builds it and equals beam search)."""
         from .sequence_generator import DiverseBeamSearch, DiverseSiblingsSearch, Sampling, SequenceGenerator
 
+        if getattr(args, "score_reference", False):  # (:313-320: before any search strategy is looked at; the search flags go unused)
+            from .sequence_scorer import SequenceScorer
+            return SequenceScorer(self.target_dictionary)
         sampling = getattr(args, "sampling", False)
         sampling_topk = getattr(args, "sampling_topk", -1)
         sampling_topp = getattr(args, "sampling_topp", -1.0)

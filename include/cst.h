@@ -34,9 +34,10 @@ extern "C" {
  * cst_ln_gelu_fwd / _bwd and their workspaces; 9: cst_beam_desc.members / logits_n / lprobs_out — checkpoint ensembles;
  * 10: cst_beam_desc.no_repeat_ngram / prefix_tokens / prefix_len — n-gram blocking and forced prefixes;
  * 11: cst_beam_desc.sampling / sample_topk / sample_topp / sample_key — sampling decode;
- * 12: cst_beam_desc.diverse_groups / diverse_strength / diverse_siblings / sibling_rate — diverse beam groups and diverse siblings).
+ * 12: cst_beam_desc.diverse_groups / diverse_strength / diverse_siblings / sibling_rate — diverse beam groups and diverse siblings;
+ * 13: cst_score_tokens — scores of given target tokens, --score-reference).
  * cst_version() returns the value the library was built with; chimera-st_amd/lib.py refuses a mismatch. */
-#define CST_ABI_VERSION 12
+#define CST_ABI_VERSION 13
 
 typedef enum { CST_F32 = 0, CST_BF16 = 1 } cst_dtype;
 
@@ -470,6 +471,33 @@ int cst_ls_ce_fwd(const void* logits, const int64_t* target, float* out2, float*
 int cst_ls_ce_bwd(const void* logits, const int64_t* target, const float* lse, const float* gscale,
                   void* dlogits, int64_t rows, int64_t V, float eps, int64_t pad_idx, int dtype,
                   cst_stream stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Scores of GIVEN target tokens (ABI 13; fairseq-generate --score-reference) — replaces, in fairseq/sequence_scorer.py, the fp32
+ * (log-)softmax of every ensemble member's [B, T, V] decoder output (:77-79 -> models/fairseq_decoder.py:58-79 -> utils.py:469-473),
+ * the gather of the target column (:54-59, :81), the average over the members (:96-111) and the per-sentence mean (:118-127).  The
+ * float32 [B, T, V] probability tensor the reference builds per member is never materialised.
+ *   logits / logits_n: N = `members` matrices (1 <= N <= 8), member 0 in `logits`, members 1 .. N-1 in the HOST array logits_n[0 ..
+ *     N-2] (it travels in the kernel arguments, as cst_beam_desc.logits_n does; NULL when N = 1).  Each is [rows = B*T, V] in `dtype`
+ *     with the common row stride ld >= V (elements); any V, any ld, any element-aligned base: 16-byte loads are used on the part of a
+ *     row between its first and last 16-byte boundary, scalar loads in front and behind.
+ *   target int64 [B, T] with 0 <= id < V or id == pad (the kernel cannot validate device data: the caller checks — kernels.score_tokens
+ *     does so on the host; an id outside the vocabulary yields NaN and reads nothing).
+ *   pos fp32 [B, T], score fp32 [B], len int32 [B]: all overwritten.
+ * All in fp32.  Per non-pad position and member m, with mx_m the row's maximum (taken out before the exponentials):
+ *     lse_m = mx_m + log(sum_v exp(x_v - mx_m)),   l_m = x_target - lse_m;
+ *     N = 1: pos = l_1;      N > 1: pos = logsumexp_m(l_m) - log N  (the members' maximum taken out likewise);
+ *   pos = 0 at pad positions, whose logits are NOT read;  len[b] = the non-pad targets of sentence b;
+ *   score[b] = (sum of the non-pad pos[b, :]) / len[b], added in a fixed order without atomics (bit-reproducible); a sentence without
+ *   targets gives the reference's 0 / 0 = NaN.
+ * DIFFERENCE to the reference: for N > 1 it averages the members' PROBABILITIES in fp32 and takes the log (:96-111); the log-domain
+ * form here is the same number wherever the reference's is finite, and stays finite where every member's probability underflows fp32
+ * (the reference then returns log 0 = -inf).
+ * Bad scalar arguments (null operand, dtype, B / T / V < 1, ld < V, members outside 1 .. 8, a missing member): CST_ERR_BAD_ARG, nothing
+ * is launched.
+ * ------------------------------------------------------------------------------------------ */
+int cst_score_tokens(const void* logits, const void* const* logits_n, int64_t members, int64_t ld, const int64_t* target, int64_t pad,
+                     float* pos, float* score, int32_t* len, int64_t B, int64_t T, int64_t V, int dtype, cst_stream stream);
 
 /* ------------------------------------------------------------------------------------------
  * Contrastive term of TripletSTMTContrastiveCriterion.compute_contrastive
