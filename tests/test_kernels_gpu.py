@@ -196,7 +196,9 @@ def test_layernorm(K, dt, rows, cols):
     y, s, mean, rstd = k.layernorm_fwd(x, res, g, b, 1e-5, want_sum=True)
     sr = (x.float() + res.float())
     check(s, sr, dt, "ln sum")
-    sref = s.float().detach().requires_grad_(True)  # the kernel normalises the rounded sum it wrote
+    # (the kernel takes mean / rstd and y from the UNROUNDED fp32 x + res and only stores the rounded sum; this reference normalises
+    #  the stored sum instead, and the tolerance of check() cannot tell the two apart — test_norm_gpu.py pins the statistics)
+    sref = s.float().detach().requires_grad_(True)
     gr, br = g.float().requires_grad_(True), b.float().requires_grad_(True)
     yr = F.layer_norm(sref, (cols,), gr, br, 1e-5)
     check(y, yr, dt, "ln fwd")
