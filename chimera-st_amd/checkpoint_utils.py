@@ -150,6 +150,37 @@ def load_model_ensemble_and_task(filenames, arg_overrides=None, task=None, stric
     return ensemble, args, task
 
 
+class _DictTask:
+    """What TransformerLanguageModel.build_model asks of a task: the dictionary."""
+
+    def __init__(self, dictionary):
+        self.source_dictionary = self.target_dictionary = dictionary
+
+
+def load_language_model(path, tgt_dict, arg_overrides=None):
+    """The target-side language model of --lm-path (fairseq_cli/generate.py:112-128): built from the checkpoint's args ON the translation
+    task's target dictionary — the reference asks the same of the user: the LM's dictionary must be the target dictionary (it loads
+    the LM with the translation task's data directory).  Returns the model in eval mode."""
+    from . import transformer_lm  # noqa: F401 (registry)
+    state = load_checkpoint_to_cpu(path, arg_overrides)
+    args = state.get("args")
+    if args is None:
+        raise RuntimeError("checkpoint %s has no `args` Namespace (keys: %s)" % (path, list(state.keys())))
+    arch = getattr(args, "arch", "transformer_lm")
+    if registry.ARCH_MODEL_REGISTRY.get(arch) is not registry.MODEL_REGISTRY["transformer_lm"]:
+        raise ValueError("--lm-path %s holds a model of architecture %r: a transformer_lm language model is required" % (path, arch))
+    sd = state["model"]
+    rows = int(sd["decoder.embed_tokens.weight"].shape[0])
+    if rows != len(tgt_dict):
+        raise ValueError("the language model %s has a vocabulary of %d symbols, the target dictionary has %d: the LM's dictionary must "
+                         "be the target dictionary" % (path, rows, len(tgt_dict)))
+    registry.ARCH_CONFIG_REGISTRY[arch](args)
+    model = registry.ARCH_MODEL_REGISTRY[arch].build_model(args, _DictTask(tgt_dict))
+    model.upgrade_state_dict(sd)
+    model.load_state_dict(sd, strict=True)
+    return model.eval()
+
+
 def _require_same_dictionary(first, other, model_state, first_file, other_file):
     """Ensemble members must share the target dictionary: same length, same symbols, and the member's output vocabulary is it."""
     rows = model_state["decoder.embed_tokens.weight"].shape[0] if "decoder.embed_tokens.weight" in model_state else len(other)

@@ -249,6 +249,9 @@ def generate_parser():
     p.add_argument("--diversity-rate", type=float, default=-1.0, help="diverse siblings search: the p-th best continuation of a hypothesis "
                    "loses p times this rate (0 equals beam search; negative = off)")
     p.add_argument("--score-reference", action="store_true", help="just score the reference translation")
+    p.add_argument("--lm-path", default=None, help="a transformer_lm checkpoint over the TARGET dictionary: its next-token log-probabilities "
+                   "are added to the model's at every step (shallow fusion)")
+    p.add_argument("--lm-weight", type=float, default=0.0, help="the weight of the language model's log-probabilities (requires --lm-path)")
     p.add_argument("--nbest", type=int, default=1, help="hypotheses printed per sentence (at most --beam)")
     p.add_argument("--remove-bpe", "--post-process", nargs="?", const="@@ ", default=None, dest="post_process")
     p.add_argument("--scoring", default="bleu")
@@ -272,6 +275,10 @@ def check_generate_args(args):
         raise ValueError("Provided Search parameters are mutually exclusive.")
     if args.diverse_beam_groups > 0 and args.beam % args.diverse_beam_groups != 0:
         raise ValueError("DiverseBeamSearch requires --beam to be divisible by the number of groups")
+    if args.lm_weight != 0.0 and args.lm_path is None:
+        raise ValueError("--lm-weight requires --lm-path")
+    if args.lm_path is not None and args.score_reference:
+        raise ValueError("--lm-path cannot be combined with --score-reference: the scorer has no language model")
     return args
 
 
@@ -290,7 +297,10 @@ def generate_main(argv=None):
                                   max_positions=(args.max_source_positions, args.max_target_positions), ignore_invalid_inputs=True)
     if args.score_reference and any(d.tgt_texts is None for d in getattr(ds, "datasets", [ds])):  # before any batch is decoded
         raise ValueError("--score-reference needs the references of subset %s: it has no target text" % args.gen_subset)
-    gen = task.build_generator(models, args)
+    lm = None
+    if args.lm_path is not None:  # fairseq_cli/generate.py:112-128: one LM over the target dictionary
+        lm = checkpoint_utils.load_language_model(args.lm_path, task.target_dictionary).to("cuda", dtype).eval()
+    gen = task.build_generator(models, args, extra_gen_cls_kwargs={"lm_model": lm, "lm_weight": args.lm_weight})
     tgt_dict = task.target_dictionary
     if args.results_path:
         os.makedirs(args.results_path, exist_ok=True)
@@ -350,6 +360,7 @@ def generate_main(argv=None):
                "sampling": bool(args.sampling), "nbest": args.nbest, "seed": args.seed,
                "diverse_beam_groups": args.diverse_beam_groups, "diverse_beam_strength": args.diverse_beam_strength,
                "diversity_rate": args.diversity_rate, "score_reference": bool(args.score_reference),
+               "lm_path": args.lm_path, "lm_weight": args.lm_weight,
                "bleu4_whitespace": corpus_bleu(hyps, refs) if any(refs) else None, "ignored_flags": ignored}
     print(json.dumps(summary), file=out, flush=True)
     if out is not sys.stdout:

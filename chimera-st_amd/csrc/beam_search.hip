@@ -85,6 +85,22 @@ struct EnsP {
 struct NoEns {};  // what a kernel without ENS takes in EnsP's place: no kernel argument bytes
 template <bool ENS> using EnsArg = std::conditional_t<ENS, EnsP, NoEns>;
 
+// LM (shallow fusion with a target-side language model, sequence_generator.py:318-324): the LM's logits row hs — same rows, vocabulary,
+// ld_logits, dtype and alignment as `logits` — gets its own (max, sum) in the block_lse call of (a) (one more slot, no more barriers), and
+//   lm_lp[v] = x_lm[v] - lse_lm   (NO temperature: the reference normalises the raw LM output),   lp'[v] = fl(lp[v] + fl(w * lm_lp[v]))
+// replaces lp (single or ensemble-combined, after the temperature) before (b): the reference's `probs * w`, then `lprobs += probs`, before
+// any mask.  The LM row is re-read (an L2 hit) where lp' is formed instead of being held in registers next to the model's row.  A NaN LM row
+// or one without a finite entry has no finite lse: every lm_lp is NaN, so is the row, and the first mask of (b) makes it -inf.
+struct LmP {
+  const void* logits;
+  float weight;
+  float* lprobs_out;  // optional [rows][ld_logits] fp32: lp' before the masks of (b)
+};
+struct NoLm {};  // like NoEns
+template <bool LM> using LmArg = std::conditional_t<LM, LmP, NoLm>;
+// lp' of one element (no contraction to an fma: the reference rounds the product)
+__device__ __forceinline__ float lm_fuse(float lp, float w, float x_lm, float lse_lm) { return __fadd_rn(lp, __fmul_rn(w, x_lm - lse_lm)); }
+
 // member n's copy of logits row hs (without ENS: the row itself)
 template <typename T, bool ENS>
 __device__ __forceinline__ const T* member_row(const BeamP& p, const EnsArg<ENS>& e, int n, int hs) {
@@ -490,8 +506,8 @@ __device__ __forceinline__ void beam_row_sample_tail(const BeamP& p, float (&x)[
 // The register-resident body: the row's logits stay in registers (NV 16-byte vectors per thread) between the statistics pass and
 // stage (c); the selection is 2*beam wave-wide arg-max rounds in which only the winning thread rescans its registers (an earlier
 // version kept a sorted top-K list per thread for a whole sentence per workgroup: the divergent insertion chains made it 105 us per step).
-template <typename T, int NV, bool ENS, bool CON, bool SAMP>
-__device__ __forceinline__ void beam_row_regs(const BeamP& p, const EnsArg<ENS>& e, float* cand_val, int32_t* cand_tok) {
+template <typename T, int NV, bool ENS, bool CON, bool SAMP, bool LM>
+__device__ __forceinline__ void beam_row_regs(const BeamP& p, const EnsArg<ENS>& e, const LmArg<LM>& lm, float* cand_val, int32_t* cand_tok) {
   constexpr int VEC = DT<T>::VEC, NTH = 512, NW = NTH / 64;
   RowCtx c;
   if (!row_prologue<CON>(p, c)) return;
@@ -510,7 +526,7 @@ __device__ __forceinline__ void beam_row_regs(const BeamP& p, const EnsArg<ENS>&
       if (v >= 0 && v < V) atomicOr(&ban[v >> 5], 1u << (v & 31));
     });  // (visible after the barriers of the statistics pass below)
   }
-  __shared__ LseSm<ENS ? ENS_MAX : 1, NW> st;
+  __shared__ LseSm<(ENS ? ENS_MAX : 1) + (LM ? 1 : 0), NW> st;
   __shared__ float w_val[NW * KMAX_ALL];
   __shared__ int w_tok[NW * KMAX_ALL];
   static_assert(KMAX_ALL <= 64 && NW <= 64, "the merge keeps one output candidate / one list head per lane of wave 0");
@@ -526,10 +542,28 @@ __device__ __forceinline__ void beam_row_regs(const BeamP& p, const EnsArg<ENS>&
       for (int k = 0; k < VEC; ++k) t[i][k] = (vi < nvec && vi * VEC + k < V) ? temper<ENS>(t[i][k], p, e) : NEG;
     }
   };
+  [[maybe_unused]] auto load_lm_row = [&](float (&t)[NV][VEC]) {  // the LM's row, untempered; -inf behind the vocabulary
+    if constexpr (LM) {
+      const T* ln = reinterpret_cast<const T*>(lm.logits) + (int64_t)hs * p.ld_logits;
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        const int vi = tid + i * NTH;
+        if (vi < nvec) ld_vec<T>(ln + (int64_t)vi * VEC, t[i]);
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) t[i][k] = (vi < nvec && vi * VEC + k < V) ? t[i][k] : NEG;
+      }
+    }
+  };
+  int nmod = 1;  // the model's rows; the LM's statistics take slot nmod
+  if constexpr (ENS) nmod = e.n;
   float lse = 0.0f;
   if constexpr (ENS) {
     float t[NV][VEC];
-    block_lse(e.n, st, [&](int n, float& mx, float& sum) { load_row(n, t); lse_thread(t, mx, sum); });
+    block_lse(nmod + (LM ? 1 : 0), st, [&](int n, float& mx, float& sum) {
+      if (LM && n == nmod) load_lm_row(t);
+      else load_row(n, t);
+      lse_thread(t, mx, sum);
+    });
     const bool bad = ens_bad(st.lse, e.n);
     float acc[NV][VEC];
 #pragma unroll
@@ -555,9 +589,33 @@ __device__ __forceinline__ void beam_row_regs(const BeamP& p, const EnsArg<ENS>&
         for (int k = 0; k < VEC; k += 4) { f32x4 o4 = {x[i][k], x[i][k + 1], x[i][k + 2], x[i][k + 3]}; *reinterpret_cast<f32x4*>(o + k) = o4; }
       }
     }  // x holds log-probabilities already: lse stays 0
+  } else if constexpr (LM) {
+    float t[NV][VEC];
+    block_lse(2, st, [&](int n, float& mx, float& sum) {
+      if (n == 0) { load_row(0, x); lse_thread(x, mx, sum); }
+      else { load_lm_row(t); lse_thread(t, mx, sum); }
+    });
+    lse = st.lse[0];
   } else {
     block_lse(1, st, [&](int, float& mx, float& sum) { load_row(0, x); lse_thread(x, mx, sum); });
     lse = st.lse[0];
+  }
+  if constexpr (LM) {  // x <- lp' (second sweep over the LM row); lse is spent
+    float t[NV][VEC];
+    load_lm_row(t);
+    const float lse_lm = st.lse[nmod];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) x[i][k] = lm_fuse(x[i][k] - lse, lm.weight, t[i][k], lse_lm);
+      const int vi = tid + i * NTH;
+      if (lm.lprobs_out && vi < nvec) {
+        float* o = lm.lprobs_out + (int64_t)h * p.ld_logits + (int64_t)vi * VEC;
+#pragma unroll
+        for (int k = 0; k < VEC; k += 4) { f32x4 o4 = {x[i][k], x[i][k + 1], x[i][k + 2], x[i][k + 3]}; *reinterpret_cast<f32x4*>(o + k) = o4; }
+      }
+    }
+    lse = 0.0f;
   }
   const float prev = row_prev_score(p, c);
   // candidate values replace the logits in the registers
@@ -669,8 +727,8 @@ __device__ __forceinline__ void beam_row_regs(const BeamP& p, const EnsArg<ENS>&
 
 // The generic-width body: rows too long for registers are re-read from memory (L2-resident) on every scan; with ENS every scan
 // recombines the N rows element by element, with CON every scan consults the ban filter.  It only selects.
-template <typename T, bool ENS, bool CON>
-__device__ __forceinline__ void beam_row_wide(const BeamP& p, const EnsArg<ENS>& e, float* cand_val, int32_t* cand_tok) {
+template <typename T, bool ENS, bool CON, bool LM>
+__device__ __forceinline__ void beam_row_wide(const BeamP& p, const EnsArg<ENS>& e, const LmArg<LM>& lm, float* cand_val, int32_t* cand_tok) {
   constexpr int NTH = 512, NW = NTH / 64, BANW = 256;
   RowCtx c;
   if (!row_prologue<CON>(p, c)) return;
@@ -692,17 +750,25 @@ __device__ __forceinline__ void beam_row_wide(const BeamP& p, const EnsArg<ENS>&
     ngram_banned(tk, s, p.ngram, 0, 1, [&](int64_t b) { hit = hit || b == v; });
     return hit;
   };
-  __shared__ LseSm<ENS ? ENS_MAX : 1, NW> st;
+  __shared__ LseSm<(ENS ? ENS_MAX : 1) + (LM ? 1 : 0), NW> st;
   __shared__ float wv[NW];
   __shared__ int wi[NW];
   __shared__ float o_val[KMAX_ALL];
   __shared__ int o_tok[KMAX_ALL];
   int nmem = 1;
   if constexpr (ENS) nmem = e.n;
-  block_lse(nmem, st, [&](int n, float& mx, float& sum) {
-    const T* ln = member_row<T, ENS>(p, e, n, hs);
+  [[maybe_unused]] const T* lmrow = nullptr;  // the LM's row (untempered); its statistics take slot nmem
+  if constexpr (LM) lmrow = reinterpret_cast<const T*>(lm.logits) + (int64_t)hs * p.ld_logits;
+  block_lse(nmem + (LM ? 1 : 0), st, [&](int n, float& mx, float& sum) {
     mx = NEG;
     sum = 0.0f;
+    if constexpr (LM) {
+      if (n == nmem) {
+        for (int v = tid; v < V; v += NTH) lse_push(mx, sum, DT<T>::ld(lmrow + v));  // (a NaN element makes the sum NaN)
+        return;
+      }
+    }
+    const T* ln = member_row<T, ENS>(p, e, n, hs);
     bool nan = false;
     for (int v = tid; v < V; v += NTH) {
       const float xv = temper<ENS>(DT<T>::ld(ln + v), p, e);
@@ -716,8 +782,8 @@ __device__ __forceinline__ void beam_row_wide(const BeamP& p, const EnsArg<ENS>&
   if constexpr (ENS) bad = ens_bad(st.lse, e.n);
   else lse = st.lse[0];
   [[maybe_unused]] const T* lg = member_row<T, ENS>(p, e, 0, hs);
-  // log-probability of token v before the masks
-  auto lprob = [&](int v) -> float {
+  // the model's log-probability of token v
+  auto lprob_model = [&](int v) -> float {
     if constexpr (ENS) {
       float m = NEG, a = 0.0f;
       for (int n = 0; n < e.n; ++n) lse_merge(m, a, temper<ENS>(DT<T>::ld(member_row<T, ENS>(p, e, n, hs) + v), p, e) - st.lse[n], 1.0f);
@@ -726,9 +792,20 @@ __device__ __forceinline__ void beam_row_wide(const BeamP& p, const EnsArg<ENS>&
       return temper<ENS>(DT<T>::ld(lg + v), p, e) - lse;
     }
   };
+  [[maybe_unused]] float lse_lm = 0.0f;
+  if constexpr (LM) lse_lm = st.lse[nmem];
+  // log-probability of token v before the masks (with LM: lp')
+  auto lprob = [&](int v) -> float {
+    if constexpr (LM) return lm_fuse(lprob_model(v), lm.weight, DT<T>::ld(lmrow + v), lse_lm);
+    else return lprob_model(v);
+  };
   if constexpr (ENS) {
     if (e.lprobs_out)
-      for (int v = tid; v < V; v += NTH) e.lprobs_out[(int64_t)h * p.ld_logits + v] = lprob(v);
+      for (int v = tid; v < V; v += NTH) e.lprobs_out[(int64_t)h * p.ld_logits + v] = lprob_model(v);
+  }
+  if constexpr (LM) {
+    if (lm.lprobs_out)
+      for (int v = tid; v < V; v += NTH) lm.lprobs_out[(int64_t)h * p.ld_logits + v] = lprob(v);
   }
   const float prev = row_prev_score(p, c);
   // local best that is strictly worse than (tv, ti) — the thread's previously taken candidate
@@ -764,11 +841,11 @@ __device__ __forceinline__ void beam_row_wide(const BeamP& p, const EnsArg<ENS>&
 }
 
 // NV vectors per thread in registers; NV == 0: the wide body
-template <typename T, int NV, bool ENS, bool CON, bool SAMP>
-__global__ __launch_bounds__(512) void beam_row_kernel(BeamP p, float* cand_val, int32_t* cand_tok, EnsArg<ENS> e) {
+template <typename T, int NV, bool ENS, bool CON, bool SAMP, bool LM>
+__global__ __launch_bounds__(512) void beam_row_kernel(BeamP p, float* cand_val, int32_t* cand_tok, EnsArg<ENS> e, LmArg<LM> lm) {
   static_assert(NV > 0 || !SAMP, "the wide body only selects");
-  if constexpr (NV == 0) beam_row_wide<T, ENS, CON>(p, e, cand_val, cand_tok);
-  else beam_row_regs<T, NV, ENS, CON, SAMP>(p, e, cand_val, cand_tok);
+  if constexpr (NV == 0) beam_row_wide<T, ENS, CON, LM>(p, e, lm, cand_val, cand_tok);
+  else beam_row_regs<T, NV, ENS, CON, SAMP, LM>(p, e, lm, cand_val, cand_tok);
 }
 
 // ---- beam search step, kernel 2 of 2: one workgroup per SENTENCE -------------------------------------------------------------
@@ -1032,7 +1109,9 @@ int64_t cst_beam_workspace(int64_t bsz, int64_t beam) {
   return bsz * beam * 2 * beam * (int64_t)(sizeof(float) + sizeof(int32_t)) + 64;
 }
 
-int cst_beam_step(const cst_beam_desc* d, cst_stream stream) {
+int cst_beam_step(const cst_beam_desc* d, cst_stream stream) { return cst_beam_step_lm(d, nullptr, stream); }
+
+int cst_beam_step_lm(const cst_beam_desc* d, const cst_lm_fusion_desc* f, cst_stream stream) {
   BeamP p;
   const int rc = to_params(d, p);
   if (rc != CST_OK) return rc;
@@ -1099,29 +1178,41 @@ int cst_beam_step(const cst_beam_desc* d, cst_stream stream) {
     CST_REQUIRE(n >= e.n || (e.logits[n] != nullptr && ((uintptr_t)e.logits[n] % 16) == 0),
                 "cst_beam_step: logits of ensemble member %d null or not 16-byte aligned", n);
   }
+  // shallow fusion (an entry point of its own, added at ABI 13): off without f or without f->lm_logits -> the kernels without it
+  const bool lmf = f != nullptr && f->lm_logits != nullptr;
+  LmP lmp{nullptr, 0.0f, nullptr};
+  if (lmf) {
+    CST_REQUIRE(((uintptr_t)f->lm_logits % 16) == 0, "cst_beam_step_lm: lm_logits must be 16-byte aligned (rows laid out like `logits`)");
+    CST_REQUIRE(f->lm_weight - f->lm_weight == 0.0f, "cst_beam_step_lm: lm_weight %g is not finite", (double)f->lm_weight);
+    CST_REQUIRE(f->lprobs_out == nullptr || ((uintptr_t)f->lprobs_out % 16) == 0, "cst_beam_step_lm: lprobs_out must be 16-byte aligned");
+    lmp.logits = f->lm_logits; lmp.weight = f->lm_weight; lmp.lprobs_out = f->lprobs_out;
+  }
   hipStream_t s = (hipStream_t)stream;
   const int64_t rows = (int64_t)p.bsz * p.beam, K = 2 * p.beam;
   int32_t* ticket = reinterpret_cast<int32_t*>(d->workspace);
   float* cand_val = reinterpret_cast<float*>(reinterpret_cast<char*>(d->workspace) + 64);
   int32_t* cand_tok = reinterpret_cast<int32_t*>(cand_val + rows * K);
   {
-    CstProfScope prof(CST_K_ELEMENTWISE, s, 0.0, (double)rows * p.vocab * cst_dtype_size(d->dtype) * (ens ? 2 * e.n : 1));
+    CstProfScope prof(CST_K_ELEMENTWISE, s, 0.0, (double)rows * p.vocab * cst_dtype_size(d->dtype) * ((ens ? 2 * e.n : 1) + (lmf ? 2 : 0)));
     // vectors per thread: the register-resident bodies up to 5, the wide body (NV = 0) beyond.  The constraints, the ensemble and
     // sampling are template flags: a descriptor with all of them off launches the instantiations it always did.
     const int64_t per_thread = cst_ceil_div(cst_ceil_div(d->vocab, vec), 512);
     const int bucket = per_thread <= 1 ? 0 : per_thread <= 3 ? 1 : per_thread <= 5 ? 2 : 3;
     dispatch(
-        [&](auto type, auto nv, auto ens_c, auto con_c, auto samp_c) {
+        [&](auto type, auto nv, auto ens_c, auto con_c, auto samp_c, auto lm_c) {
           using T = typename decltype(type)::type;
           constexpr int NV = decltype(nv)::value;
-          constexpr bool ENS = decltype(ens_c)::value, CON = decltype(con_c)::value, SAMP = decltype(samp_c)::value;
+          constexpr bool ENS = decltype(ens_c)::value, CON = decltype(con_c)::value, SAMP = decltype(samp_c)::value, LM = decltype(lm_c)::value;
           if constexpr (NV > 0 || !SAMP) {  // (sampling with a wide vocabulary was refused above)
             EnsArg<ENS> ea{};
             if constexpr (ENS) ea = e;
-            hipLaunchKernelGGL((beam_row_kernel<T, NV, ENS, CON, SAMP>), dim3((unsigned)rows), dim3(512), 0, s, p, cand_val, cand_tok, ea);
+            LmArg<LM> la{};
+            if constexpr (LM) la = lmp;
+            hipLaunchKernelGGL((beam_row_kernel<T, NV, ENS, CON, SAMP, LM>), dim3((unsigned)rows), dim3(512), 0, s, p, cand_val, cand_tok, ea, la);
           }
         },
-        Choice<Type<float>, Type<bf16_t>>{d->dtype == CST_BF16}, Choice<Int<1>, Int<3>, Int<5>, Int<0>>{bucket}, Bool{ens}, Bool{con}, Bool{samp});
+        Choice<Type<float>, Type<bf16_t>>{d->dtype == CST_BF16}, Choice<Int<1>, Int<3>, Int<5>, Int<0>>{bucket}, Bool{ens}, Bool{con}, Bool{samp},
+        Bool{lmf});
     dispatch(
         [&](auto pfx_c, auto samp_c, auto div_c) {
           constexpr bool PFX = decltype(pfx_c)::value, SAMP = decltype(samp_c)::value;
@@ -1131,7 +1222,7 @@ int cst_beam_step(const cst_beam_desc* d, cst_stream stream) {
         },
         Bool{p.prefix_len > 0}, Bool{samp}, Choice<Int<0>, Int<1>, Int<2>>{groups ? 1 : siblings ? 2 : 0});
   }
-  return cst_check_launch("cst_beam_step");
+  return cst_check_launch(lmf ? "cst_beam_step_lm" : "cst_beam_step");
 }
 
 }  // extern "C"

@@ -30,13 +30,21 @@ from .optim import PARAM_EPOCH
 class BeamDecodeEngine:
     def __init__(self, decoder, tgt_dict, beam_size, max_len, min_len=1, normalize_scores=True, len_penalty=1.0,
                  unk_penalty=0.0, temperature=1.0, use_graph=True, poll=8, cross_kernel=None, lanes=None, no_repeat_ngram_size=0,
-                 sampling=False, topk=0, topp=0.0, diverse_groups=0, diverse_strength=0.0, sibling_rate=None):
+                 sampling=False, topk=0, topp=0.0, diverse_groups=0, diverse_strength=0.0, sibling_rate=None, lm_decoder=None,
+                 lm_weight=0.0):
         # a checkpoint ensemble (--path a.pt:b.pt:c.pt) is a LIST of decoders: every member keeps its own packed weights, K/V caches,
         # encoder K/V and logits buffer; the beam state (tokens / scores / ancestry, step counter, finalized hypotheses) is shared —
         # all members follow the same hypotheses, so one ancestry table serves every member's append-only caches
         self.decs = list(decoder) if isinstance(decoder, (list, tuple)) else [decoder]
         assert 1 <= len(self.decs) <= 8, "cst_beam_step combines at most 8 ensemble members"
         self.dec = self.decs[0]
+        # shallow fusion (--lm-path / --lm-weight, sequence_generator.py:318-324): a target-side language model is one more decoder of
+        # the step — a decoder WITHOUT cross attention (lm_supported) with its own packed weights, caches and logits buffer, following
+        # the same hypotheses through the shared step / tokens / ancestry — and cst_beam_step_lm adds lm_weight x its log-softmax to the
+        # members' combined log-probabilities inside the row kernel
+        self.lm, self.lm_weight = lm_decoder, float(lm_weight)
+        assert self.lm is None or self.lm_supported(self.lm), "the language model's decoder is outside lm_supported()"
+        assert self.lm is None or self.lm.output_projection.weight.shape[0] == len(tgt_dict), "the LM's vocabulary must be the target dictionary"
         self.pad, self.unk, self.eos = tgt_dict.pad(), tgt_dict.unk(), tgt_dict.eos()
         self.vocab = len(tgt_dict)
         self.beam, self.max_len, self.min_len = int(beam_size), int(max_len), int(min_len)
@@ -93,6 +101,20 @@ class BeamDecodeEngine:
             return False
 
     @staticmethod
+    def lm_supported(decoder):
+        """supported() for a language model: the same decoder without encoder attention in any layer."""
+        try:
+            ok = (decoder.embed_positions is not None and decoder.layernorm_embedding is None and decoder.project_in_dim is None
+                  and decoder.project_out_dim is None and decoder.adaptive_softmax is None and len(decoder.layers) > 0)
+            ok = ok and hasattr(decoder.embed_positions, "get_embedding")  # sinusoidal positions
+            for l in decoder.layers:
+                ok = ok and l.normalize_before and l.encoder_attn is None and l.self_attn.head_dim in (32, 64)
+                ok = ok and l.self_attn.q_proj.bias is not None
+            return bool(ok)
+        except AttributeError:
+            return False
+
+    @staticmethod
     def sampling_supported(vocab, dtype):
         """cst_beam_step samples in its register-resident row kernels: at most 5 * 512 16-byte vectors per row (20480 symbols in bf16,
         10240 in fp32).  Beyond that it returns CST_ERR_UNSUPPORTED, so the generator takes the host loop up front."""
@@ -110,12 +132,15 @@ class BeamDecodeEngine:
         copies and graphs to the cyclic collector, which may then run inside a later graph capture)."""
         # weights may have been updated since the last call (training between validations): re-pack and drop the graphs
         # (autograd versions catch load_state_dict / copy_; optim.PARAM_EPOCH catches the fused optimizer's raw-pointer updates)
-        key = (dtype, device, PARAM_EPOCH[0], tuple((p.data_ptr(), p._version) for dec in self.decs for p in dec.parameters()))
+        decs = self.decs + ([self.lm] if self.lm is not None else [])
+        key = (dtype, device, PARAM_EPOCH[0], tuple((p.data_ptr(), p._version) for dec in decs for p in dec.parameters()))
         if self._packed is not None and self._packed[0] == key:
             return self._packed[1]
         self._state.clear()
         members = [self._pack_member(dec, dtype, device) for dec in self.decs]
         members[0]["others"] = members[1:]
+        if self.lm is not None:
+            members[0]["lm"] = self._pack_member(self.lm, dtype, device)
         self._packed = (key, members[0])
         return self._packed[1]
 
@@ -134,8 +159,9 @@ class BeamDecodeEngine:
                 bqkv=torch.cat((sa.q_proj.bias, sa.k_proj.bias, sa.v_proj.bias), 0).detach().contiguous())
             if fuse:  # LayerNorm folded into the projection that follows it (include/cst.h: cst_dec_ln_linear)
                 d["ln_qkv"] = self._fold_ln(l.self_attn_layer_norm, d["wqkv"], d["bqkv"])
-                d["ln_q"] = self._fold_ln(l.encoder_attn_layer_norm, l.encoder_attn.q_proj.weight, l.encoder_attn.q_proj.bias)
-                d["ln_q_frag"] = self.fragment_major(d["ln_q"][0], l.encoder_attn.num_heads)  # cst_dec_ln_q_cross_attn's weight layout
+                if l.encoder_attn is not None:  # (a language model's layers have no cross block)
+                    d["ln_q"] = self._fold_ln(l.encoder_attn_layer_norm, l.encoder_attn.q_proj.weight, l.encoder_attn.q_proj.bias)
+                    d["ln_q_frag"] = self.fragment_major(d["ln_q"][0], l.encoder_attn.num_heads)  # cst_dec_ln_q_cross_attn's weight layout
                 d["ln_fc1"] = self._fold_ln(l.final_layer_norm, l.fc1.weight, l.fc1.bias)
             layers.append(d)
         pos = dec.embed_positions
@@ -151,13 +177,15 @@ class BeamDecodeEngine:
         cross-attention, out, LayerNorm, fc1, fc2 — the three LayerNorms folded into their projections on the bf16 path) + final
         LayerNorm + vocabulary projection + the two beam-search kernels; + the split-K reduce of fc2 where it is split (bf16, <= 256
         hypothesis rows, ffn >= 4096).  An ensemble runs every member's sequence up to its vocabulary projection, then ONE pair of
-        beam-search kernels over the members' logits."""
-        return sum(self._member_nodes(dec, dtype, rows) for dec in self.decs) + 2
+        beam-search kernels over the members' logits.  A language model adds its own sequence without the cross block: per layer
+        (LayerNorm, qkv, self-attention, out, LayerNorm, fc1, fc2), the two LayerNorms folded on the bf16 path."""
+        return sum(self._member_nodes(dec, dtype, rows) for dec in self.decs + ([self.lm] if self.lm is not None else [])) + 2
 
     def _member_nodes(self, dec, dtype, rows):
-        per_layer = 8 if self._fuse_ln(dtype, dec) else 11
+        cross = dec.layers[0].encoder_attn is not None
+        per_layer = (8 if cross else 5) if self._fuse_ln(dtype, dec) else (11 if cross else 7)
         D = dec.layers[0].self_attn.head_dim
-        if self._fuse_ln(dtype, dec) and self._fuse_q_cross(dtype, D, dec.embed_dim, self._cross_mode(dtype, D)):
+        if cross and self._fuse_ln(dtype, dec) and self._fuse_q_cross(dtype, D, dec.embed_dim, self._cross_mode(dtype, D)):
             per_layer -= 1  # the query projection runs inside the cross-attention launch
         F = dec.layers[0].fc1.out_features
         if rows is not None and rows <= 256 and F >= 4096 and dtype == torch.bfloat16 and not os.environ.get("CST_DEC_NO_SPLITK"):
@@ -196,11 +224,18 @@ class BeamDecodeEngine:
 
     # ------------------------------------------------------------------------------------------------------------
     def _alloc_member(self, dec, bsz, S, dtype, device, has_mask):
-        """One member's own buffers: activations, logits, append-only self-attention caches, per-sentence encoder K/V."""
+        """One member's own buffers: activations, logits, append-only self-attention caches, per-sentence encoder K/V (none of the
+        latter for a decoder without cross attention)."""
         beam, L1 = self.beam, self.max_len + 1
         bbsz, C, nl = bsz * beam, dec.embed_dim, len(dec.layers)
         F = dec.layers[0].fc1.out_features
         z = lambda *shape, dt=dtype: torch.zeros(*shape, dtype=dt, device=device)
+        if dec.layers[0].encoder_attn is None:
+            return dict(
+                x=z(bbsz, C), x2=z(bbsz, C), h=z(bbsz, C), qkv=z(bbsz, 3 * C), attn=z(bbsz, C), f=z(bbsz, F),
+                logits=z(bbsz, (self.vocab + 7) // 8 * 8), mean=z(bbsz, dt=torch.float32), rstd=z(bbsz, dt=torch.float32),
+                kc=[z(bbsz, L1, C) for _ in range(nl)], vc=[z(bbsz, L1, C) for _ in range(nl)],
+                gemm_ws=z(8 * bbsz * C * 4 if bbsz <= 256 else 0, dt=torch.uint8))
         return dict(
             x=z(bbsz, C), x2=z(bbsz, C), h=z(bbsz, C), qkv=z(bbsz, 3 * C), q=z(bbsz, C), attn=z(bbsz, C), f=z(bbsz, F),
             logits=z(bbsz, (self.vocab + 7) // 8 * 8),
@@ -217,7 +252,7 @@ class BeamDecodeEngine:
         S = tuple(S) if isinstance(S, (list, tuple)) else (S,) * len(self.decs)
         has_mask = tuple(has_mask) if isinstance(has_mask, (list, tuple)) else (has_mask,) * len(self.decs)
         key = (lane, bsz, S, dtype, device, has_mask, prefix_len, self.no_repeat_ngram_size, self.sampling, self.topk, self.topp,
-               self.diverse_groups, self.diverse_strength, self.sibling_rate)
+               self.diverse_groups, self.diverse_strength, self.sibling_rate, id(self.lm), self.lm_weight)
         st = self._state.get(key)
         if st is not None:
             return st
@@ -237,6 +272,14 @@ class BeamDecodeEngine:
             m = self._alloc_member(dec, bsz, S[i], dtype, device, has_mask[i])
             m.update(step=st["step"], tokens=st["tokens"], anc=st["anc"])
             st["others"].append(m)
+        st["lm"], st["lm_desc"] = None, None
+        if self.lm is not None:
+            m = self._alloc_member(self.lm, bsz, 0, dtype, device, False)
+            m.update(step=st["step"], tokens=st["tokens"], anc=st["anc"])
+            st["lm"] = m
+            f = L.LmFusionDesc()
+            f.lm_logits, f.lm_weight, f.lprobs_out = m["logits"].data_ptr(), self.lm_weight, None
+            st["lm_desc"] = f
         d = L.BeamDesc()
         d.dtype = L.dtype_code(dtype)
         d.bsz, d.beam, d.vocab, d.max_len = bsz, beam, self.vocab, self.max_len
@@ -310,11 +353,15 @@ class BeamDecodeEngine:
 
     def _step(self, st, pk, bsz):
         """One decode step: every launch reads the step counter from device memory.  The members' layer sequences follow one another
-        on the one stream (a linear graph; step graphs on several streams do not overlap on this stack — see `lanes`), then ONE
-        beam step reads all their logits."""
+        on the one stream (a linear graph; step graphs on several streams do not overlap on this stack — see `lanes`), then the
+        language model's, then ONE beam step reads all their logits."""
         for dec, m, mpk in zip(self.decs, self.members(st), self.members(pk)):
             self._step_member(dec, m, mpk, bsz)
-        L.check(L.load().cst_beam_step(ctypes.byref(st["desc"]), L.stream_ptr()), "cst_beam_step")
+        if self.lm is None:
+            L.check(L.load().cst_beam_step(ctypes.byref(st["desc"]), L.stream_ptr()), "cst_beam_step")
+            return
+        self._step_member(self.lm, st["lm"], pk["lm"], bsz)
+        L.check(L.load().cst_beam_step_lm(ctypes.byref(st["desc"]), ctypes.byref(st["lm_desc"]), L.stream_ptr()), "cst_beam_step_lm")
 
     def _step_member(self, dec, st, pk, bsz):
         """One member's decoder up to its vocabulary projection -> st["logits"]."""
@@ -340,39 +387,8 @@ class BeamDecodeEngine:
                                           L.stream_ptr()), "cst_dec_self_attn")
             self._linear(st["attn"], sa.out_proj.weight, sa.out_proj.bias, x2, resid=x)
             x, x2 = x2, x
-            S = st["kx"][li].shape[1]
-            ck = self._cross_mode(st["x"].dtype, D)
-            qfused = fused and p.get("ln_q_frag") is not None and self._fuse_q_cross(st["x"].dtype, D, C, ck)
-            if qfused:
-                pass  # the query projection runs inside the cross-attention launch below
-            elif fused:
-                self._ln_linear(x, p["ln_q"], st["q"])
-            else:
-                self._ln(x, layer.encoder_attn_layer_norm, st["h"], st)
-                self._linear(st["h"], ca.q_proj.weight, ca.q_proj.bias, st["q"])
-            # cross attention: one workgroup per (sentence, head); the sentence's K/V rows serve all of its beam rows
-            if qfused:
-                _, sg, sb, eps = p["ln_q"]
-                L.check(lib.cst_dec_ln_q_cross_attn(L.ptr(x), x.stride(0), L.ptr(p["ln_q_frag"]), L.ptr(sg), L.ptr(sb), eps, L.ptr(st["kx"][li]),
-                                                    L.ptr(st["vx"][li]), L.ptr(st["kpm"]), L.ptr(st["attn"]), L.ptr(st["step"]), self.max_len,
-                                                    bsz, self.beam, H, D, S, float(ca.scaling), dt, L.stream_ptr()), "cst_dec_ln_q_cross_attn")
-            elif ck == "flash_hm":  # the flash kernel over head-major K/V: (b, h, t) strides = (H*S*D, S*D, D)
-                q3, o3 = st["q"].view(bsz, self.beam, C), st["attn"].view(bsz, self.beam, C)
-                d = K.attn_desc(q3, st["kx"][li], st["vx"][li], o3, st["lse"], H, D, st["kpm"], False, float(ca.scaling))
-                d.k_sb = d.v_sb = H * S * D
-                d.k_sh = d.v_sh = S * D
-                d.k_st = d.v_st = D
-                K.attn_fwd_desc(d)
-            elif ck == "shared":
-                L.check(lib.cst_dec_cross_attn(L.ptr(st["q"]), L.ptr(st["kx"][li]), L.ptr(st["vx"][li]), L.ptr(st["kpm"]), L.ptr(st["attn"]),
-                                               L.ptr(st["step"]), self.max_len, bsz, self.beam, H, D, S, float(ca.scaling), dt,
-                                               L.stream_ptr()), "cst_dec_cross_attn")
-            else:  # very long sources: the flash kernel with batch = sentence, query "time" axis = the beam rows
-                q3, o3 = st["q"].view(bsz, self.beam, C), st["attn"].view(bsz, self.beam, C)
-                d = K.attn_desc(q3, st["kx"][li], st["vx"][li], o3, st["lse"], H, D, st["kpm"], False, float(ca.scaling))
-                K.attn_fwd_desc(d)
-            self._linear(st["attn"], ca.out_proj.weight, ca.out_proj.bias, x2, resid=x)
-            x, x2 = x2, x
+            if ca is not None:
+                x, x2 = self._step_cross(layer, li, st, p, x, x2, bsz, fused)
             act = L.ACT_GELU if layer.activation_fn == "gelu" else L.ACT_RELU
             if fused:
                 self._ln_linear(x, p["ln_fc1"], st["f"], act=act)
@@ -388,8 +404,51 @@ class BeamDecodeEngine:
             feat = x
         w = dec.output_projection.weight
         self._linear(feat, w, None, st["logits"])
-        # an even number of x/x2 swaps per layer (3) x layers may leave the residual stream in x2: the NEXT step's embed always
-        # writes st["x"], and every step performs the same swaps, so the captured sequence is step-invariant.
+        # the x/x2 swaps of a step (3 per layer, 2 without a cross block) may leave the residual stream in x2: the NEXT step's embed
+        # always writes st["x"], and every step performs the same swaps, so the captured sequence is step-invariant.
+
+    def _step_cross(self, layer, li, st, p, x, x2, bsz, fused):
+        """The cross-attention block of one layer (query projection, attention over the sentence's encoder K/V, out-proj + residual);
+        returns the swapped (x, x2)."""
+        lib = L.load()
+        bbsz, C = st["x"].shape
+        dt = L.dtype_code(st["x"].dtype)
+        ca = layer.encoder_attn
+        H = layer.self_attn.num_heads
+        D = C // H
+        S = st["kx"][li].shape[1]
+        ck = self._cross_mode(st["x"].dtype, D)
+        qfused = fused and p.get("ln_q_frag") is not None and self._fuse_q_cross(st["x"].dtype, D, C, ck)
+        if qfused:
+            pass  # the query projection runs inside the cross-attention launch below
+        elif fused:
+            self._ln_linear(x, p["ln_q"], st["q"])
+        else:
+            self._ln(x, layer.encoder_attn_layer_norm, st["h"], st)
+            self._linear(st["h"], ca.q_proj.weight, ca.q_proj.bias, st["q"])
+        # cross attention: one workgroup per (sentence, head); the sentence's K/V rows serve all of its beam rows
+        if qfused:
+            _, sg, sb, eps = p["ln_q"]
+            L.check(lib.cst_dec_ln_q_cross_attn(L.ptr(x), x.stride(0), L.ptr(p["ln_q_frag"]), L.ptr(sg), L.ptr(sb), eps, L.ptr(st["kx"][li]),
+                                                L.ptr(st["vx"][li]), L.ptr(st["kpm"]), L.ptr(st["attn"]), L.ptr(st["step"]), self.max_len,
+                                                bsz, self.beam, H, D, S, float(ca.scaling), dt, L.stream_ptr()), "cst_dec_ln_q_cross_attn")
+        elif ck == "flash_hm":  # the flash kernel over head-major K/V: (b, h, t) strides = (H*S*D, S*D, D)
+            q3, o3 = st["q"].view(bsz, self.beam, C), st["attn"].view(bsz, self.beam, C)
+            d = K.attn_desc(q3, st["kx"][li], st["vx"][li], o3, st["lse"], H, D, st["kpm"], False, float(ca.scaling))
+            d.k_sb = d.v_sb = H * S * D
+            d.k_sh = d.v_sh = S * D
+            d.k_st = d.v_st = D
+            K.attn_fwd_desc(d)
+        elif ck == "shared":
+            L.check(lib.cst_dec_cross_attn(L.ptr(st["q"]), L.ptr(st["kx"][li]), L.ptr(st["vx"][li]), L.ptr(st["kpm"]), L.ptr(st["attn"]),
+                                           L.ptr(st["step"]), self.max_len, bsz, self.beam, H, D, S, float(ca.scaling), dt,
+                                           L.stream_ptr()), "cst_dec_cross_attn")
+        else:  # very long sources: the flash kernel with batch = sentence, query "time" axis = the beam rows
+            q3, o3 = st["q"].view(bsz, self.beam, C), st["attn"].view(bsz, self.beam, C)
+            d = K.attn_desc(q3, st["kx"][li], st["vx"][li], o3, st["lse"], H, D, st["kpm"], False, float(ca.scaling))
+            K.attn_fwd_desc(d)
+        self._linear(st["attn"], ca.out_proj.weight, ca.out_proj.bias, x2, resid=x)
+        return x2, x
 
     # ------------------------------------------------------------------------------------------------------------
     @torch.no_grad()

@@ -98,6 +98,10 @@ class BeamDesc(ctypes.Structure):
     ]
 
 
+class LmFusionDesc(ctypes.Structure):
+    _fields_ = [("lm_logits", c_p), ("lm_weight", c_f), ("lprobs_out", c_p)]
+
+
 class FbankDesc(ctypes.Structure):
     _fields_ = [
         ("B", c_i64), ("S", c_i64), ("T", c_i64),
@@ -180,6 +184,7 @@ SYMBOLS = [
     ("cst_beam_workspace", c_i64, [c_i64, c_i64]),
     ("cst_beam_init", c_int, [ctypes.POINTER(BeamDesc), c_p]),
     ("cst_beam_step", c_int, [ctypes.POINTER(BeamDesc), c_p]),
+    ("cst_beam_step_lm", c_int, [ctypes.POINTER(BeamDesc), ctypes.POINTER(LmFusionDesc), c_p]),
     ("cst_dec_embed", c_int, [c_p, c_p, c_p, c_p, c_f, c_i64, c_p, c_i64, c_i64, c_i64, c_i64, c_int, c_p]),
     ("cst_dec_self_attn", c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_f, c_int, c_p]),
     ("cst_batch_by_size", c_i64, [c_p, c_i64, c_i64, c_i64, ctypes.c_int32, c_p]),

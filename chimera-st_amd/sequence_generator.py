@@ -178,7 +178,7 @@ class DiverseSiblingsSearch:
 class SequenceGenerator:
     def __init__(self, models, tgt_dict, beam_size=1, max_len_a=0, max_len_b=200, min_len=1, normalize_scores=True,
                  len_penalty=1.0, unk_penalty=0.0, temperature=1.0, match_source_len=False, no_repeat_ngram_size=0,
-                 search_strategy=None, eos=None, fused=True, use_graph=True, cross_kernel=None, seed=1):
+                 search_strategy=None, eos=None, fused=True, use_graph=True, cross_kernel=None, seed=1, lm_model=None, lm_weight=1.0):
         self.models = list(models) if isinstance(models, (list, tuple)) else [models]
         self.model = self.models[0]
         self.tgt_dict = tgt_dict
@@ -194,6 +194,17 @@ class SequenceGenerator:
         self.max_len_a, self.max_len_b, self.min_len = max_len_a, max_len_b, min_len
         self.normalize_scores, self.len_penalty, self.unk_penalty = normalize_scores, len_penalty, unk_penalty
         self.temperature = temperature
+        # shallow fusion (sequence_generator.py:36-37, :103-106, :318-324): lm_weight x the LM's next-token log-softmax (no temperature)
+        # is added to the models' log-probabilities at every step, before any mask
+        self.lm_model, self.lm_weight = lm_model, float(lm_weight)
+        if lm_model is not None:
+            n = getattr(getattr(lm_model.decoder, "embed_tokens", None), "num_embeddings", len(tgt_dict))
+            if n != len(tgt_dict):
+                raise ValueError("the language model has a vocabulary of %d symbols, the target dictionary has %d: the LM's dictionary "
+                                 "must be the target dictionary" % (n, len(tgt_dict)))
+            if not math.isfinite(self.lm_weight):
+                raise ValueError("lm_weight must be finite, got %r" % lm_weight)
+            lm_model.eval()
         assert temperature > 0 and not match_source_len
         if no_repeat_ngram_size < 0 or no_repeat_ngram_size == 1:
             raise ValueError("no_repeat_ngram_size must be 0 (off) or at least 2, got %d: with 1 the initial eos of every hypothesis is "
@@ -277,6 +288,13 @@ class SequenceGenerator:
             return log_probs[0]
         return torch.logsumexp(torch.stack(log_probs, dim=0), dim=0) - math.log(len(log_probs))
 
+    def _lm_lprobs(self, tokens, incremental_state):
+        """sequence_generator.py:318-324: lm_weight x the LM's log-softmax at the last position (the reference recomputes the whole
+        prefix at every step; the incremental state gives the same numbers)."""
+        out = self.lm_model.decoder.forward(tokens, incremental_state=incremental_state)
+        probs = self.lm_model.get_normalized_probs((out[0][:, -1:, :], None), log_probs=True)[:, -1, :]
+        return probs * self.lm_weight
+
     def _generate(self, sample, prefix_tokens=None, sample_key=None):
         self.calls += 1
         key = (sample_key_of(self.seed, self.calls) if sample_key is None else int(sample_key) & 0xFFFFFFFF) if self.sampling else 0
@@ -296,6 +314,8 @@ class SequenceGenerator:
         if self.fused:
             from .decode_engine import BeamDecodeEngine
             ok = len(self.models) <= 8 and all(BeamDecodeEngine.supported(m.decoder) for m in self.models)  # else the whole ensemble takes the host loop
+            if self.lm_model is not None:  # (an LM the engine cannot take sends the whole decode to the host loop)
+                ok = ok and BeamDecodeEngine.lm_supported(self.lm_model.decoder)
             if self.sampling:  # (the wide-vocabulary row kernel only selects: such vocabularies are sampled by the host loop)
                 ok = ok and BeamDecodeEngine.sampling_supported(self.vocab_size, encoder_outs[0].encoder_out.dtype)
             if ok:
@@ -309,12 +329,15 @@ class SequenceGenerator:
                                                     topp=self.search.sampling_topp if self.sampling else 0.0,
                                                     diverse_groups=self.search.num_groups if type(self.search) is DiverseBeamSearch else 0,
                                                     diverse_strength=getattr(self.search, "diversity_strength", 0.0),
-                                                    sibling_rate=self.search.diversity_rate if type(self.search) is DiverseSiblingsSearch else None)
+                                                    sibling_rate=self.search.diversity_rate if type(self.search) is DiverseSiblingsSearch else None,
+                                                    lm_decoder=None if self.lm_model is None else self.lm_model.decoder,
+                                                    lm_weight=self.lm_weight)
                 return self._engine.generate(encoder_outs if len(encoder_outs) > 1 else encoder_outs[0], bsz, prefix_tokens=prefix_tokens,
                                              sample_key=key)
         new_order = torch.arange(bsz, device=device).view(-1, 1).repeat(1, beam_size).view(-1)
         encoder_outs = [m.encoder.reorder_encoder_out(e, new_order) for m, e in zip(self.models, encoder_outs)]
         incremental_states: List[Dict[str, Dict[str, Optional[Tensor]]]] = [{} for _ in self.models]
+        lm_state: Dict[str, Dict[str, Optional[Tensor]]] = {}
 
         scores = torch.zeros(bsz * beam_size, max_len + 1, device=device, dtype=torch.float32)
         tokens = torch.full((bsz * beam_size, max_len + 2), self.pad, device=device, dtype=torch.long)
@@ -333,7 +356,11 @@ class SequenceGenerator:
                 for m, inc in zip(self.models, incremental_states):
                     m.decoder.reorder_incremental_state_scripting(inc, reorder_state)
                 encoder_outs = [m.encoder.reorder_encoder_out(e, reorder_state) for m, e in zip(self.models, encoder_outs)]
+                if self.lm_model is not None:
+                    self.lm_model.decoder.reorder_incremental_state_scripting(lm_state, reorder_state)
             lprobs = self._forward_decoder(tokens[:, :step + 1], encoder_outs, incremental_states)
+            if self.lm_model is not None:
+                lprobs = lprobs + self._lm_lprobs(tokens[:, :step + 1], lm_state)
             lprobs[lprobs != lprobs] = -math.inf
             lprobs[:, self.pad] = -math.inf
             lprobs[:, self.unk] -= self.unk_penalty

@@ -102,6 +102,7 @@ class FairseqTask:
         `diversity_rate > 0`, the sibling search is chosen with `diversity_rate > -1` (so rate 0 builds it and equals beam search)."""
         from .sequence_generator import DiverseBeamSearch, DiverseSiblingsSearch, Sampling, SequenceGenerator
 
+        extra = dict(extra_gen_cls_kwargs or {})  # (lm_model / lm_weight of --lm-path, fairseq_cli/generate.py:171)
         if getattr(args, "score_reference", False):  # (:313-320: before any search strategy is looked at; the search flags go unused)
             from .sequence_scorer import SequenceScorer
             return SequenceScorer(self.target_dictionary)
@@ -128,7 +129,7 @@ class FairseqTask:
             max_len_b=getattr(args, "max_len_b", 200), min_len=getattr(args, "min_len", 1),
             normalize_scores=(not getattr(args, "unnormalized", False)), len_penalty=getattr(args, "lenpen", 1),
             unk_penalty=getattr(args, "unkpen", 0), temperature=getattr(args, "temperature", 1.0),
-            no_repeat_ngram_size=getattr(args, "no_repeat_ngram_size", 0), search_strategy=search, seed=getattr(args, "seed", 1))
+            no_repeat_ngram_size=getattr(args, "no_repeat_ngram_size", 0), search_strategy=search, seed=getattr(args, "seed", 1), **extra)
 
 
 def _load_dict(args, default_size):

@@ -35,7 +35,8 @@ extern "C" {
  * 10: cst_beam_desc.no_repeat_ngram / prefix_tokens / prefix_len — n-gram blocking and forced prefixes;
  * 11: cst_beam_desc.sampling / sample_topk / sample_topp / sample_key — sampling decode;
  * 12: cst_beam_desc.diverse_groups / diverse_strength / diverse_siblings / sibling_rate — diverse beam groups and diverse siblings;
- * 13: cst_score_tokens — scores of given target tokens, --score-reference).
+ * 13: cst_score_tokens — scores of given target tokens, --score-reference).  cst_beam_step_lm and cst_lm_fusion_desc were ADDED at 13
+ * without a bump: no existing signature or layout changed, and a library without the symbol fails at symbol lookup.
  * cst_version() returns the value the library was built with; chimera-st_amd/lib.py refuses a mismatch. */
 #define CST_ABI_VERSION 13
 
@@ -636,6 +637,21 @@ typedef struct {
 int64_t cst_beam_workspace(int64_t bsz, int64_t beam);
 int cst_beam_init(const cst_beam_desc* d, cst_stream stream);
 int cst_beam_step(const cst_beam_desc* d, cst_stream stream);
+/* Shallow fusion with a target-side language model (sequence_generator.py:318-324; added at ABI 13): cst_beam_step with one more
+ * logits matrix, fused inside the same row kernel — still two launches.  lm_logits: the LM's next-token logits of the hypothesis rows,
+ * same rows, vocab, ld_logits, dtype and alignment as d->logits.  With lp[v] the model's log-probability (single, or the ensemble's
+ * combination; after the temperature):
+ *     lm_lp[v] = lm_logits[v] - logsumexp_v(lm_logits)        (NO temperature: the reference normalises the raw LM output)
+ *     lp'[v]   = fl(lp[v] + fl(lm_weight * lm_lp[v]))          (the reference's `probs * w`, then `lprobs += probs`)
+ * in fp32, and everything cst_beam_step does from the NaN mask on — pad / unk / max-len / prefix / min-len / n-gram masks, cumulative
+ * score, top-2*beam or the draw, the merge kernel, the diverse strategies — runs on lp'.  An LM row with a NaN or without a finite entry
+ * makes the row NaN -> -inf, as in the reference; where the prefix holds eos the row reads the sentence's first row of lm_logits too.
+ * cst_beam_step(d, s) is cst_beam_step_lm(d, NULL, s); f == NULL or f->lm_logits == NULL: off — the kernels and arguments of
+ * cst_beam_step.  lprobs_out (optional, 16-byte aligned): fp32 [bbsz][ld_logits], receives lp' before the masks for any number of
+ * members (columns >= vocab are undefined); cst_beam_desc.lprobs_out keeps its meaning (the ensemble's lp, without the LM) and its
+ * restriction.  lm_logits or lprobs_out not 16-byte aligned, lm_weight not finite: CST_ERR_BAD_ARG.  Nothing is launched on an error. */
+typedef struct { const void* lm_logits; float lm_weight; float* lprobs_out; } cst_lm_fusion_desc;
+int cst_beam_step_lm(const cst_beam_desc* d, const cst_lm_fusion_desc* f, cst_stream stream);
 /* out[h] = scale * embed[tokens[s&1][h][s]] + pos_table[pad_idx + 1 + s], s = *step (models/transformer.py:744-760,
  * sinusoidal_positional_embedding.py:88-95).  embed/out in `dtype`, pos_table fp32 [pos_rows, C]. */
 int cst_dec_embed(const int64_t* tokens, const int32_t* step, const void* embed, const float* pos_table, float scale,

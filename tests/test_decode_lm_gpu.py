@@ -1,0 +1,461 @@
+"""GPU tests of shallow fusion with a target-side language model (--lm-path / --lm-weight; reference sequence_generator.py:318-324):
+  * cst_beam_step_lm called directly: lp' per element against fp64, the fused search in every dispatch family (plain, constrained,
+    sampling) against the restatement of tests/lm_fusion_util.py, and the error paths;
+  * the engine (an LM member without cross attention) and the host loop against the hypotheses of the REAL reference's
+    SequenceGenerator(lm_model=..., lm_weight=...) (decode_lm_tiny.npz);
+  * engine == host loop on fresh ragged audio, graph replay, weight 0, bf16 at real dimensions, and the command line."""
+import ast
+import ctypes
+import math
+import os
+import shutil
+from argparse import Namespace
+from importlib import import_module
+
+import pytest
+import torch
+
+import decode_sampling_util as S
+import lm_fusion_util as U
+from conftest import GOLDEN, load_golden, load_pkg
+from decode_constraints_util import BEAM, BSZ, EOS, MAX_LEN, PAD, PREFIX, UNK
+from test_decode_engine_gpu import _beam_state, _build_s2t
+from test_ensemble_gpu import fixture_members
+from test_model_gpu import assert_close
+
+pytestmark = pytest.mark.gpu
+SETTINGS = {"beam5": dict(beam_size=5, lm_weight=0.3), "recipe": dict(beam_size=10, len_penalty=1.5, lm_weight=0.5),
+            "temp": dict(beam_size=5, temperature=0.7, lm_weight=0.3), "ngram2": dict(beam_size=5, lm_weight=0.3, no_repeat_ngram_size=2),
+            "ens2": dict(beam_size=5, lm_weight=0.3, members=2)}
+ERR_BAD_ARG = -1  # CST_ERR_BAD_ARG
+
+
+def SG():
+    load_pkg()
+    return import_module("chimera-st_amd.sequence_generator").SequenceGenerator
+
+
+@pytest.fixture(scope="module")
+def L():
+    load_pkg()
+    return import_module("chimera-st_amd.lib")
+
+
+def _fusion(L, lm_buf, w, out=None):
+    f = L.LmFusionDesc()
+    f.lm_logits, f.lm_weight, f.lprobs_out = lm_buf.data_ptr(), w, (None if out is None else out.data_ptr())
+    return f
+
+
+def _members(d, bufs):
+    if len(bufs) > 1:
+        d.members = len(bufs)
+        for n in range(1, len(bufs)):
+            d.logits_n[n - 1] = bufs[n].data_ptr()
+
+
+# ---- 1. the kernel ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("N,T,dt", U.KERNEL_CASES)
+def test_fused_lprobs_kernel(L, N, T, dt):
+    """cst_beam_step_lm with f->lprobs_out: lp'[v] = fl(lp[v] + fl(w * (x_lm[v] - lse_lm))) of one step against the fp64 torch
+    evaluation on the same stored logits — 160 rows, vocabulary 10 000, w = 0.5; row 5 with -inf in member 1 only, row 9 with -inf in
+    all members, LM row 7 with -inf at every 13th token.
+
+    Bound per element: min(4 x the error of the FP32 TORCH evaluation against fp64 on these very inputs, 1e-4 / 13 = 7.69e-6).
+    Measured on the CPU (test_decode_lm_cpu): fp32 torch 2.2e-6 .. 4.3e-6, so the bound in force is the cap in every case (|lp'| reaches
+    33: one fp32 ulp there is 3.8e-6).  The -inf sets are equal, there is no NaN, and the step's winner and score of every row are the
+    fp64 result's."""
+    lib = L.load()
+    dtype = U.tdtype(dt)
+    rows, V = U.ROWS, U.VOCAB
+    x, y = U.model_logits(N, dtype), U.lm_logits(dtype)
+    cpu_err, _ = U.fp32_torch_error(x, y, U.W, T)
+    bound = min(4.0 * cpu_err, U.CAP)
+    ref = U.fused_lprobs(x, y, U.W, T, torch.float64)
+    Vp = (V + 7) // 8 * 8
+    bufs = [torch.zeros(rows, Vp, dtype=dtype, device="cuda") for _ in range(N)]
+    for n in range(N):
+        bufs[n][:, :V] = x[n].cuda()
+    lm_buf = torch.zeros(rows, Vp, dtype=dtype, device="cuda")
+    lm_buf[:, :V] = y.cuda()
+    st, d = _beam_state(L, rows, 1, V, 4, 1, dtype, bufs[0], temperature=T)
+    _members(d, bufs)
+    out = torch.full((rows, Vp), 7.0, dtype=torch.float32, device="cuda")
+    f = _fusion(L, lm_buf, U.W, out)
+    L.check(lib.cst_beam_init(ctypes.byref(d), L.stream_ptr()), "cst_beam_init")
+    L.check(lib.cst_beam_step_lm(ctypes.byref(d), ctypes.byref(f), L.stream_ptr()), "cst_beam_step_lm")
+    got = out[:, :V].cpu().double()
+    fin = torch.isfinite(ref)
+    assert not torch.isnan(got).any()
+    assert torch.equal(torch.isfinite(got), fin), "the -inf sets differ"
+    assert bool((got[~fin] == -math.inf).all()) and int((~fin[7]).sum()) == len(range(0, V, 13))
+    err = float((got - ref)[fin].abs().max())
+    print("N=%d %s T=%g: kernel max |err| %.3e, fp32 torch %.3e, bound %.3e, error / bound %.3f" % (N, dt, T, err, cpu_err, bound, err / bound))
+    assert err <= bound, (err, bound, cpu_err)
+    masked = ref.clone()
+    masked[:, 1] = -math.inf
+    masked[:, 2] = -math.inf
+    assert st["tokens"][1, :, 1].cpu().tolist() == masked.argmax(dim=1).tolist()
+    assert float((st["scores"][1, :, 0].cpu().double() - masked.max(dim=1).values).abs().max()) <= bound
+
+
+def _compare_state(st, ref, s, tol):
+    nxt = (s + 1) & 1
+    assert torch.equal(st["tokens"][nxt, :, :s + 2].cpu(), ref["tokens"][:, :s + 2]), s
+    assert torch.equal(st["anc"][nxt, :, :s + 2].cpu(), ref["anc"][:, :s + 2]), s
+    got, want = st["scores"][nxt, :, :s + 1].cpu().double(), ref["scores"][:, :s + 1]
+    assert torch.equal(torch.isinf(got), torch.isinf(want)), s
+    err = float((got - want).nan_to_num(0.0, 0.0, 0.0).abs().max())
+    fin_err = float((st["fin_score"].cpu().double() - ref["fin_score"]).abs().max())
+    print("step %d  max |scores - fp64| %.2e  fin_score %.2e  bound %.2e" % (s, err, fin_err, tol))
+    assert err <= tol and fin_err <= tol, (s, err, fin_err, tol)
+    for k in ("ignore", "finished", "nfinal", "fin_len"):
+        assert torch.equal(st[k].cpu(), ref[k]), (k, s)
+    assert torch.equal(st["fin_tokens"].cpu(), ref["fin_tokens"]), s
+
+
+def _search_setup(L, dt, V, N, sampling=False):
+    dtype = U.tdtype(dt)
+    bbsz, Vp = BSZ * BEAM, (V + 7) // 8 * 8
+    bufs = [torch.zeros(bbsz, Vp, dtype=dtype, device="cuda") for _ in range(N)]
+    lm_buf = torch.zeros(bbsz, Vp, dtype=dtype, device="cuda")
+    st, d = _beam_state(L, BSZ, BEAM, V, MAX_LEN, 1, dtype, bufs[0], pad=PAD, unk=UNK, eos=EOS)
+    _members(d, bufs)
+    return bufs, lm_buf, st, d
+
+
+def _load_step(bufs, lm_buf, model, lm, V):
+    for buf, x in zip(bufs, model):
+        buf[:, :V] = x.cuda()
+    lm_buf[:, :V] = lm.cuda()
+
+
+@pytest.mark.parametrize("dt,V,N,variant", U.SEARCH_PARAMS)
+def test_fused_search_matches_restatement(L, dt, V, N, variant):
+    """bsz 3 x beam 4, six steps of a max_len 12 search on fresh logits per step, w = 0.5: after EVERY step tokens, ancestry, the
+    bookkeeping and the finalized hypotheses equal the fp64 restatement's exactly, scores within the per-element bound (the cap
+    1e-4 / 13 — see test_fused_lprobs_kernel) times the steps taken.  Every selection gap of the fp64 search exceeds 1e-4
+    (test_decode_lm_cpu), so the ids do not hang on rounding.  "ngram2_prefix": no_repeat_ngram 2 and the ragged prefix with an eos."""
+    lib = L.load()
+    ngram, with_prefix = U.SEARCH_VARIANTS[variant]
+    bufs, lm_buf, st, d = _search_setup(L, dt, V, N)
+    d.no_repeat_ngram = ngram
+    prefix = torch.tensor(PREFIX, dtype=torch.int64) if with_prefix else None
+    prefix_d = prefix.cuda() if with_prefix else None
+    if with_prefix:
+        d.prefix_tokens, d.prefix_len = prefix_d.data_ptr(), prefix.size(1)
+    f = _fusion(L, lm_buf, U.W)
+    L.check(lib.cst_beam_init(ctypes.byref(d), L.stream_ptr()), "cst_beam_init")
+    ref = U.new_state()
+    for s in range(U.STEPS):
+        model, lm = U.search_logits(dt, V, N, s)
+        _load_step(bufs, lm_buf, model, lm, V)
+        L.check(lib.cst_beam_step_lm(ctypes.byref(d), ctypes.byref(f), L.stream_ptr()), "cst_beam_step_lm")
+        U.select_step(ref, U.masked(ref, U.fused_step_lprobs(model, lm, U.W), s, ngram=ngram, prefix=prefix), s)
+        assert int(st["step"].item()) == s + 1
+        _compare_state(st, ref, s, U.CAP * (s + 1))
+    assert ref["min_gap"] > 1e-4 and int(ref["nfinal"].sum()) > 0
+    if with_prefix:  # eos inside the prefix: `beam` identical hypotheses, read from the first row of BOTH matrices
+        assert st["fin_tokens"][1, :, :2].tolist() == [[PREFIX[1][0], EOS]] * BEAM and st["fin_len"][1].tolist() == [2] * BEAM
+
+
+@pytest.mark.parametrize("topk,topp", [(5, 0.0), (0, 0.8)])
+@pytest.mark.parametrize("N", [1, 2])
+@pytest.mark.parametrize("dt,V", [c for c in U.SEARCH_CASES if S.family(*c) != "wide"])
+def test_fused_sampling_matches_restatement(L, dt, V, N, topk, topp):
+    """Sampling (top-k 5 / top-p 0.8) in the register families on lp': decode_sampling_util's comparison — a draw may differ from the
+    fp64 restatement only where the restatement calls it undecidable, and then only to a token of the widened kept set."""
+    lib = L.load()
+    bufs, lm_buf, st, d = _search_setup(L, dt, V, N, sampling=True)
+    key = S.case_key(dt, V, N, "plain") ^ (topk * 77 + int(topp * 1000))
+    kb = torch.tensor([key - (1 << 32) if key >= (1 << 31) else key], dtype=torch.int32, device="cuda")
+    d.sampling, d.sample_topk, d.sample_topp, d.sample_key = 1, topk, topp, kb.data_ptr()
+    f = _fusion(L, lm_buf, U.W)
+    L.check(lib.cst_beam_init(ctypes.byref(d), L.stream_ptr()), "cst_beam_init")
+    ref = S.new_state()
+    draws = forgiven = 0
+    n = BSZ * BEAM * 2 * BEAM
+    for s in range(U.STEPS):
+        model, lm = U.search_logits(dt, V, N, s, sampling=True)
+        _load_step(bufs, lm_buf, model, lm, V)
+        L.check(lib.cst_beam_step_lm(ctypes.byref(d), ctypes.byref(f), L.stream_ptr()), "cst_beam_step_lm")
+        lp = U.masked(ref, U.fused_step_lprobs(model, lm, U.W), s)
+        cands = S.step_draws(ref, lp, s, key, topk, topp, None)
+        dev_val = st["ws"][64:64 + 4 * n].view(torch.float32)[:BSZ * BEAM].cpu()
+        dev_tok = st["ws"][64 + 4 * n:64 + 8 * n].view(torch.int32)[:BSZ * BEAM].cpu()
+        for i, c in enumerate(cands):
+            draws += 1
+            t = int(dev_tok[i])
+            if t != c["tok"]:
+                assert not c["decidable"], ("a decidable draw differs", s, i, t, c["tok"])
+                assert 0 <= t < V and c["wide"][t], ("drawn outside the widened kept set", s, i, t)
+                S.adopt(ref, c, t, s)
+                forgiven += 1
+            if math.isinf(c["score"]):
+                assert float(dev_val[i]) == c["score"], (s, i)
+            else:
+                assert abs(float(dev_val[i]) - c["score"]) <= U.CAP * (s + 1), (s, i)
+        S.bookkeeping(ref, cands, s)
+        _compare_state(st, ref, s, U.CAP * (s + 1))
+    print("%d draws, %d forgiven" % (draws, forgiven))
+    assert forgiven <= 0.02 * draws
+    del kb
+
+
+def test_null_lm_is_todays_step_and_bad_arguments_are_refused(L):
+    lib = L.load()
+    V = 1003
+    model, lm = U.search_logits("fp32", V, 1, 0)
+    states = []
+    for how in ("plain", "null_desc", "null_logits"):
+        bufs, lm_buf, st, d = _search_setup(L, "fp32", V, 1)
+        _load_step(bufs, lm_buf, model, lm, V)
+        L.check(lib.cst_beam_init(ctypes.byref(d), L.stream_ptr()), "cst_beam_init")
+        if how == "plain":
+            L.check(lib.cst_beam_step(ctypes.byref(d), L.stream_ptr()), "cst_beam_step")
+        elif how == "null_desc":
+            L.check(lib.cst_beam_step_lm(ctypes.byref(d), None, L.stream_ptr()), "cst_beam_step_lm")
+        else:
+            f = L.LmFusionDesc()
+            f.lm_logits, f.lm_weight = None, float("nan")  # (not read when off)
+            L.check(lib.cst_beam_step_lm(ctypes.byref(d), ctypes.byref(f), L.stream_ptr()), "cst_beam_step_lm")
+        torch.cuda.synchronize()
+        states.append({k: v.clone() for k, v in st.items()})
+    for other in states[1:]:
+        for k in states[0]:
+            assert torch.equal(states[0][k], other[k]), k
+    # and the LM changes it
+    bufs, lm_buf, st, d = _search_setup(L, "fp32", V, 1)
+    _load_step(bufs, lm_buf, model, lm, V)
+    L.check(lib.cst_beam_init(ctypes.byref(d), L.stream_ptr()), "cst_beam_init")
+    f = _fusion(L, lm_buf, U.W)
+    for bad in (dict(lm_weight=float("nan")), dict(lm_weight=float("inf")), dict(lm_logits=lm_buf.data_ptr() + 4),
+                dict(lprobs_out=lm_buf.data_ptr() + 8)):
+        g = _fusion(L, lm_buf, U.W)
+        for k, v in bad.items():
+            setattr(g, k, v)
+        assert lib.cst_beam_step_lm(ctypes.byref(d), ctypes.byref(g), L.stream_ptr()) == ERR_BAD_ARG, bad
+        assert b"cst_beam_step_lm" in lib.cst_last_error()
+    torch.cuda.synchronize()
+    assert int(st["step"].item()) == 0  # nothing was launched
+    L.check(lib.cst_beam_step_lm(ctypes.byref(d), ctypes.byref(f), L.stream_ptr()), "cst_beam_step_lm")
+    assert int(st["step"].item()) == 1 and not torch.equal(st["scores"], states[0]["scores"])
+
+
+# ---- 2. the fixture of the real reference ---------------------------------------------------------------------------------------------
+def fixture_lm(dtype=torch.float32):
+    load_pkg()
+    TL = import_module("chimera-st_amd.transformer_lm")
+    cu = import_module("chimera-st_amd.checkpoint_utils")
+    Dictionary = import_module("chimera-st_amd.dictionary").Dictionary
+    g = load_golden("decode_lm_tiny.npz")
+    sd = {k[len("lm/param/"):]: torch.from_numpy(v).float() for k, v in g.items() if k.startswith("lm/param/")}
+    args = Namespace(**ast.literal_eval(str(g["meta/lm_args"])))
+    lm = TL.TransformerLanguageModel.build_model(args, cu._DictTask(Dictionary.synthetic(sd["decoder.embed_tokens.weight"].shape[0])))
+    missing, unexpected = lm.load_state_dict(sd, strict=False)
+    assert not unexpected and all("_float_tensor" in k or k == "decoder.version" for k in missing), (missing, unexpected)
+    return lm.to("cuda", dtype).eval(), args, g
+
+
+def _sample(rec, tag):
+    return {"net_input": {"src_tokens": torch.from_numpy(rec["in/%s/src_tokens" % tag]).cuda(),
+                          "src_lengths": torch.from_numpy(rec["in/%s/src_lengths" % tag]).cuda()}}
+
+
+@pytest.mark.parametrize("fused", [True, False])
+@pytest.mark.parametrize("name", sorted(SETTINGS))
+def test_fusion_matches_reference_generator(name, fused):
+    """Every finalized hypothesis of the reference's SequenceGenerator(models, lm_model=lm, lm_weight=w) in its order: token ids exact,
+    scores to 1e-4, positional scores to 1e-3 — from the device engine (which runs an LM member) and from the host loop, fp32."""
+    kw = dict(SETTINGS[name])
+    N = kw.pop("members", 1)
+    models, task, _, _ = fixture_members(N)
+    lm, _, fx = fixture_lm()
+    rec = load_golden("decode_recipe_tiny.npz")
+    gen = SG()(models, task.target_dictionary, max_len_a=0, max_len_b=int(fx["meta/max_len_b"]), min_len=1, fused=fused, lm_model=lm, **kw)
+    for tag in ("a", "b"):
+        hyps = gen.generate(models, _sample(rec, tag))
+        assert (gen._engine is not None) == fused
+        if fused:
+            eng = gen._engine
+            assert eng.lm is lm.decoder and len(eng.decs) == N and eng.lm_weight == kw["lm_weight"]
+            plain = SG()(models, task.target_dictionary, max_len_a=0, max_len_b=int(fx["meta/max_len_b"]), min_len=1,
+                         **{k: v for k, v in kw.items() if k != "lm_weight"})
+            plain.generate(models, _sample(rec, tag))
+            rows = 3 * kw["beam_size"]
+            lm_nodes = 1 + 7 * len(lm.decoder.layers) + 1 + 1  # fp32: embed, per layer (LN, qkv, attn, out, LN, fc1, fc2), final LN, vocabulary
+            assert eng.nodes_per_step(torch.float32, rows) == (plain._engine.nodes_per_step(torch.float32, rows) - 2) + lm_nodes + 2
+        for b in range(len(hyps)):
+            n = int(fx["gen/%s/%s/b%d/n" % (name, tag, b)])
+            assert len(hyps[b]) == n, (tag, b)
+            for k in range(n):
+                key = "gen/%s/%s/b%d/r%d/" % (name, tag, b, k)
+                assert hyps[b][k]["tokens"].tolist() == fx[key + "tokens"].tolist(), key
+                assert abs(float(hyps[b][k]["score"]) - float(fx[key + "score"])) < 1e-4, key
+                assert_close(hyps[b][k]["positional_scores"], fx[key + "pos_scores"], 1e-3, key + "pos_scores")
+
+
+# ---- 3. the engine -------------------------------------------------------------------------------------------------------------------
+def _build_lm(dtype, d=256, heads=4, layers=3, V=500, ffn=None, seed=21, sharpen=4.0):
+    load_pkg()
+    TL = import_module("chimera-st_amd.transformer_lm")
+    cu = import_module("chimera-st_amd.checkpoint_utils")
+    Dictionary = import_module("chimera-st_amd.dictionary").Dictionary
+    torch.manual_seed(seed)
+    args = Namespace(decoder_embed_dim=d, decoder_ffn_embed_dim=ffn or 4 * d, decoder_attention_heads=heads, decoder_layers=layers, dropout=0.0)
+    lm = TL.TransformerLanguageModel.build_model(args, cu._DictTask(Dictionary.synthetic(V)))
+    with torch.no_grad():
+        lm.decoder.output_projection.weight.mul_(sharpen)
+    return lm.to("cuda", dtype).eval()
+
+
+def _ragged(dtype=torch.float32):
+    g = torch.Generator().manual_seed(11)
+    src = torch.randn(5, 97, 80, generator=g).cuda().to(dtype)
+    return {"net_input": {"src_tokens": src, "src_lengths": torch.tensor([97, 80, 64, 33, 20]).cuda()}}
+
+
+def _flat(hyps):
+    return [[(h["tokens"].tolist(), float(h["score"])) for h in hb] for hb in hyps]
+
+
+def test_engine_equals_host_loop_with_a_deeper_lm():
+    """An fp32 ragged s2t batch, a 2-layer model and a 3-layer LM: the device engine (the LM's own caches and logits, one ancestry table)
+    and the host loop (the LM's own incremental state) give the same hypotheses; the LM changes them."""
+    model, task = _build_s2t(torch.float32, layers=2, tied=False)
+    lm = _build_lm(torch.float32, layers=3)
+    sample = _ragged()
+    kw = dict(beam_size=4, max_len_a=0, max_len_b=20, lm_model=lm, lm_weight=0.5)
+    fused, host = SG()([model], task.target_dictionary, **kw), SG()([model], task.target_dictionary, fused=False, **kw)
+    h1, h2 = fused.generate([model], sample), host.generate([model], sample)
+    eng = fused._engine
+    assert eng is not None and host._engine is None and len(eng.lm.layers) == 3 and len(eng.decs[0].layers) == 2
+    st = next(iter(eng._state.values()))
+    assert "kx" not in st["lm"] and "q" not in st["lm"] and len(st["lm"]["kc"]) == 3 and st["lm"]["tokens"] is st["tokens"]
+    assert all("ln_q" not in p for p in eng._packed[1]["lm"]["layers"])
+    for b in range(5):
+        assert len(h1[b]) == len(h2[b]) == 4
+        for r in range(4):
+            assert h1[b][r]["tokens"].tolist() == h2[b][r]["tokens"].tolist(), (b, r)
+            assert abs(float(h1[b][r]["score"]) - float(h2[b][r]["score"])) < 1e-4
+            assert_close(h1[b][r]["positional_scores"], h2[b][r]["positional_scores"].cpu().numpy(), 1e-3, "pos")
+    plain = SG()([model], task.target_dictionary, beam_size=4, max_len_a=0, max_len_b=20).generate([model], sample)
+    assert _flat(plain) != _flat(h1)
+
+
+def test_two_calls_replay_one_graph():
+    models, task, _, _ = fixture_members(1)
+    lm, _, _ = fixture_lm()
+    rec = load_golden("decode_recipe_tiny.npz")
+    gen = SG()(models, task.target_dictionary, beam_size=5, max_len_a=0, max_len_b=12, lm_model=lm, lm_weight=0.3)
+    first = _flat(gen.generate(models, _sample(rec, "b")))
+    graphs = [st["graph"] for st in gen._engine._state.values()]
+    assert len(graphs) == 1 and graphs[0] is not None
+    assert _flat(gen.generate(models, _sample(rec, "b"))) == first
+    assert [st["graph"] for st in gen._engine._state.values()] == graphs  # the same captured graph object: nothing was re-captured
+
+
+def test_weight_zero_decodes_the_unfused_ids():
+    """0 x a finite log-probability is 0: an LM at weight 0 (finite logits) leaves ids and scores alone — while the engine still runs it."""
+    model, task = _build_s2t(torch.float32, layers=2, tied=False)
+    lm = _build_lm(torch.float32, layers=1)
+    sample = _ragged()
+    zero = SG()([model], task.target_dictionary, beam_size=4, max_len_a=0, max_len_b=20, lm_model=lm, lm_weight=0.0)
+    plain = SG()([model], task.target_dictionary, beam_size=4, max_len_a=0, max_len_b=20)
+    h0, hp = zero.generate([model], sample), plain.generate([model], sample)
+    assert zero._engine.lm is lm.decoder
+    assert [[t for t, _ in hb] for hb in _flat(h0)] == [[t for t, _ in hb] for hb in _flat(hp)]
+    assert all(abs(a[1] - b[1]) < 1e-6 for x, y in zip(_flat(h0), _flat(hp)) for a, b in zip(x, y))
+
+
+def test_bf16_real_dimensions():
+    """C 512, 8 heads, F 4096, 2 layers, V 10 000, beam 5 in bf16 — the LayerNorm-folded projections and the split-K fc2 run for a
+    decoder without a cross block: the decode terminates, scores are finite and ordered, first tokens agree with the bf16 host loop in
+    >= 6 of 8 (the standard of test_copies_bf16_large_dims)."""
+    model, task = _build_s2t(torch.bfloat16, d=512, heads=8, layers=2, V=10000)
+    lm = _build_lm(torch.bfloat16, d=512, heads=8, layers=2, V=10000, ffn=4096)
+    g = torch.Generator().manual_seed(5)
+    src = torch.randn(8, 120, 80, generator=g).cuda().to(torch.bfloat16)
+    sample = {"net_input": {"src_tokens": src, "src_lengths": torch.tensor([120, 120, 100, 90, 77, 60, 41, 30]).cuda()}}
+    kw = dict(beam_size=5, max_len_a=0, max_len_b=20, lm_model=lm, lm_weight=0.5)
+    fused = SG()([model], task.target_dictionary, **kw)
+    h1 = fused.generate([model], sample)
+    h2 = SG()([model], task.target_dictionary, fused=False, **kw).generate([model], sample)
+    eng = fused._engine
+    assert eng.lm is lm.decoder and all("ln_qkv" in p and "ln_fc1" in p and "ln_q" not in p for p in eng._packed[1]["lm"]["layers"])
+    assert eng._member_nodes(lm.decoder, torch.bfloat16, 40) == 1 + 6 * 2 + 1 + 1  # folded LayerNorms, fc2 split: 6 nodes per layer
+    agree = 0
+    for b in range(8):
+        sc = [float(h["score"]) for h in h1[b]]
+        assert len(sc) == 5 and all(math.isfinite(s) for s in sc) and sc == sorted(sc, reverse=True)
+        agree += int(h1[b][0]["tokens"][0]) == int(h2[b][0]["tokens"][0])
+    assert agree >= 6
+
+
+def test_unsupported_lm_takes_the_host_loop():
+    """An LM outside lm_supported() (here: without positional embeddings) sends the whole decode to the host loop, which fuses it too."""
+    model, task = _build_s2t(torch.float32, layers=2, tied=False)
+    lm = _build_lm(torch.float32, layers=1)
+    lm.decoder.embed_positions = None
+    kw = dict(beam_size=2, max_len_a=0, max_len_b=6)
+    gen = SG()([model], task.target_dictionary, lm_model=lm, lm_weight=0.5, **kw)
+    hyps = gen.generate([model], _ragged())
+    assert gen._engine is None and len(hyps) == 5
+    assert _flat(hyps) != _flat(SG()([model], task.target_dictionary, **kw).generate([model], _ragged()))
+
+
+# ---- 4. the command line -----------------------------------------------------------------------------------------------------------------
+def test_cli_lm_path_decodes_with_the_language_model(tmp_path, capsys):
+    """fairseq_generate.py --path m.pt --lm-path lm.pt --lm-weight 0.3 on tests/golden/data_tiny (its dictionary padded to the fixture
+    models' 60 symbols): the H- lines are those of SequenceGenerator([m0], lm_model=lm, lm_weight=0.3) called directly on the loaded
+    files, the summary names the LM, and without --lm-path the lines differ."""
+    cli = import_module("chimera-st_amd.cli")
+    cu = import_module("chimera-st_amd.checkpoint_utils")
+    models, task, args, _ = fixture_members(1)
+    lm, lm_args, _ = fixture_lm()
+    data = os.path.join(GOLDEN, "data_tiny")
+    root = tmp_path / "data"
+    root.mkdir()
+    for f in os.listdir(data):
+        if not f.endswith(".wav"):
+            shutil.copy(os.path.join(data, f), root / f)
+    (root / "config_wave.yaml").write_text((root / "config_wave.yaml").read_text().replace("AUDIO_ROOT", data))
+    lines = (root / "dict.txt").read_text().splitlines()
+    V = models[0].decoder.embed_tokens.num_embeddings
+    lines += ["filler%d 1" % i for i in range(V - 4 - len(lines))]
+    (root / "dict.txt").write_text("\n".join(lines) + "\n")
+    a = Namespace(**vars(args))
+    a.arch, a.task, a.no_save_optimizer_state = "s2t_transformer_w2v2_interlingua_base", "triplet", True
+    a.data, a.config_yaml = str(root), "config_wave.yaml"
+    m_path, lm_path = str(tmp_path / "m.pt"), str(tmp_path / "lm.pt")
+    cu.save_state(m_path, a, models[0].state_dict(), None, None, 0)
+    la = Namespace(**vars(lm_args))
+    la.no_save_optimizer_state = True
+    cu.save_state(lm_path, la, lm.state_dict(), None, None, 0)
+    common = [str(root), "--task", "triplet", "--config-yaml", "config_wave.yaml", "--gen-subset", "dev_st", "--max-tokens", "12000",
+              "--beam", "5", "--max-len-b", "12", "--max-source-positions", "2000000", "--path", m_path]
+
+    def run(extra):
+        capsys.readouterr()
+        summary = cli.generate_main(common + extra)
+        out = capsys.readouterr().out.splitlines()
+        return summary, {int(l.split("\t")[0][2:]): l.split("\t")[1:] for l in out if l.startswith("H-")}
+
+    loaded, _, t = cu.load_model_ensemble_and_task([m_path], arg_overrides={"data": str(root), "config_yaml": "config_wave.yaml",
+                                                                           "max_source_positions": 2000000})
+    loaded = [m.to("cuda").eval() for m in loaded]
+    lm2 = cu.load_language_model(lm_path, t.target_dictionary).to("cuda").eval()
+    gen = SG()(loaded, t.target_dictionary, beam_size=5, max_len_a=0, max_len_b=12, lm_model=lm2, lm_weight=0.3)
+    direct = {}
+    itr = t.get_batch_iterator(t.load_dataset("dev_st"), max_tokens=12000, max_positions=(2000000, 1024), ignore_invalid_inputs=True)
+    for s in itr.next_epoch_itr(shuffle=False):
+        ni = s["net_input"]
+        hyps = gen.generate(loaded, {"net_input": {"src_tokens": ni["src_tokens"].cuda(), "src_lengths": ni["src_lengths"].cuda()}})
+        for i, sid in enumerate(s["id"].tolist()):
+            direct[sid] = ["%.6f" % (float(hyps[i][0]["score"]) / math.log(2)), t.target_dictionary.string(hyps[i][0]["tokens"].cpu())]
+    assert gen._engine is not None and gen._engine.lm is lm2.decoder
+    s_lm, h_lm = run(["--lm-path", lm_path, "--lm-weight", "0.3"])
+    assert s_lm["lm_path"] == lm_path and s_lm["lm_weight"] == 0.3 and s_lm["sentences"] == len(h_lm) > 0
+    assert h_lm == direct
+    s_plain, h_plain = run([])
+    assert s_plain["lm_path"] is None and h_plain != h_lm

@@ -5,6 +5,7 @@
   python tools/bench_decode.py [--batch 32] [--frames 3000] [--beam 5] [--max-len 200] [--reps 3] [--mirror] [--ensemble N]
                                [--no-repeat-ngram-size N] [--sampling [--sampling-topk K] [--sampling-topp P]]
                                [--diverse-beam-groups G [--diverse-beam-strength S]] [--diversity-rate R]
+                               [--lm-layers L [--lm-weight W]]
 
 Prints one JSON line: utterances/s and generated tokens/s of the device-resident loop (decode_engine.py: one captured HIP
 graph per step), the per-step time, the encoder time, and — with --mirror — the same numbers for the host-driven
@@ -13,7 +14,9 @@ max_len + 1 steps: the reported rate is the worst case for the configured max_le
 --ensemble N decodes N independently seeded copies of the model as a checkpoint ensemble (every member's encoder and decoder run;
 one beam step over the N logits matrices) and adds "models" and "nodes_per_step" to the line.
 --sampling decodes with the Sampling strategy (every hypothesis an independent sample) on the same engine; --diverse-beam-groups and
---diversity-rate with DiverseBeamSearch / DiverseSiblingsSearch (both inside the beam step's merge kernel)."""
+--diversity-rate with DiverseBeamSearch / DiverseSiblingsSearch (both inside the beam step's merge kernel).
+--lm-layers L adds shallow fusion with a random pre-norm language model of the decoder's width, heads and ffn size, L layers deep
+(weight --lm-weight): the engine runs it as a member without cross attention and fuses it inside the beam step's row kernel."""
 import argparse
 import importlib
 import json
@@ -48,6 +51,8 @@ def main():
     ap.add_argument("--diverse-beam-groups", type=int, default=-1, help="diverse beam search with this many groups (--beam divisible)")
     ap.add_argument("--diverse-beam-strength", type=float, default=0.5)
     ap.add_argument("--diversity-rate", type=float, default=-1.0, help="diverse siblings search with this rate (negative = off)")
+    ap.add_argument("--lm-layers", type=int, default=0, help="fuse a random language model of this depth (0 = off)")
+    ap.add_argument("--lm-weight", type=float, default=0.3)
     ap.add_argument("--profile", action="store_true", help="per-class GPU time of one eager decode loop (hipEvent pairs)")
     args = ap.parse_args()
     if sum((args.sampling, args.diverse_beam_groups > 0, args.diversity_rate > 0)) > 1:
@@ -74,6 +79,16 @@ def main():
     for k in range(1, args.ensemble):
         torch.manual_seed(1 + k)
         models.append(s2t.S2TTransformerModel.build_model(ns, task).to("cuda", dt).eval())
+
+    lm = None
+    if args.lm_layers > 0:
+        tlm = importlib.import_module("chimera-st_amd.transformer_lm")
+        cu = importlib.import_module("chimera-st_amd.checkpoint_utils")
+        torch.manual_seed(101)
+        lm_ns = Namespace(decoder_layers=args.lm_layers, decoder_embed_dim=ns.decoder_embed_dim, decoder_ffn_embed_dim=ns.decoder_ffn_embed_dim,
+                          decoder_attention_heads=ns.decoder_attention_heads, dropout=0.0, share_decoder_input_output_embed=True)
+        lm = tlm.TransformerLanguageModel.build_model(lm_ns, cu._DictTask(task.target_dictionary)).to("cuda", dt).eval()
+    lm_kw = dict(lm_model=lm, lm_weight=args.lm_weight) if lm is not None else {}
 
     g = torch.Generator().manual_seed(1)
     lens = torch.randint(args.frames // 3, args.frames + 1, (args.batch,), generator=g).sort(descending=True)[0]
@@ -111,7 +126,7 @@ def main():
         return None
 
     fused = SG(models, task.target_dictionary, beam_size=args.beam, max_len_a=0, max_len_b=args.max_len, use_graph=not args.no_graph,
-               cross_kernel=args.cross_kernel, no_repeat_ngram_size=args.no_repeat_ngram_size, search_strategy=strategy())
+               cross_kernel=args.cross_kernel, no_repeat_ngram_size=args.no_repeat_ngram_size, search_strategy=strategy(), **lm_kw)
     t_f, ntok = timed(fused)
     steps = args.max_len + 1
     out = {"metric": "decode utterances/sec, s2t_transformer_l beam 5, 1 MI355X", "config": {"arch": args.arch, "batch": args.batch,
@@ -133,9 +148,12 @@ def main():
     if args.ensemble > 1:
         out["models"] = args.ensemble
         out["nodes_per_step"] = fused._engine.nodes_per_step(dt, args.batch * args.beam)
+    if lm is not None:
+        out["config"].update(lm_layers=args.lm_layers, lm_weight=args.lm_weight)
+        out["nodes_per_step"] = fused._engine.nodes_per_step(dt, args.batch * args.beam)
     if args.mirror:
         mirror = SG(models, task.target_dictionary, beam_size=args.beam, max_len_a=0, max_len_b=args.max_len, fused=False,
-                    search_strategy=strategy())
+                    search_strategy=strategy(), **lm_kw)
         t_m, ntok_m = timed(mirror)
         out["mirror_host_loop"] = {"utterances_per_s": args.batch / t_m, "tokens_per_s": ntok_m / t_m, "s_per_batch": t_m,
                                    "ms_per_step": (t_m - enc_s) / steps * 1e3}
