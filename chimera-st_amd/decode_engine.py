@@ -15,10 +15,14 @@ input is a device-side counter:
 The sequence is captured once per (batch, encoder length) in a HIP graph and replayed; the host reads one int32
 (`num_remaining`) every `poll` steps.  Results are the reference's: same candidates, same finalisation order, same
 scores (tests/test_decode_engine_gpu.py checks token ids bit-exactly against the reference's SequenceGenerator fixtures
-and against the module-by-module mirror path)."""
+and against the module-by-module mirror path).
+
+Three records describe an engine: DecodeOptions (what to search for: the options part of the state key and of cst_beam_desc), Switches
+(the CST_DEC_* environment, read once) and, per member and row count, StepPlan (which launches a layer is made of)."""
 import ctypes
+import dataclasses
 import os
-import math
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -27,92 +31,158 @@ from . import lib as L
 from .optim import PARAM_EPOCH
 
 
+@dataclasses.dataclass(frozen=True)
+class DecodeOptions:
+    """The search a BeamDecodeEngine runs.  Every field is a parameter of cst_beam_step baked into the captured step graph (or sizes the
+    state), so the record itself — frozen, hashable — is the options part of the state key, and fill() writes it into a cst_beam_desc."""
+    beam: int
+    max_len: int
+    min_len: int = 1
+    normalize_scores: bool = True
+    len_penalty: float = 1.0
+    unk_penalty: float = 0.0
+    temperature: float = 1.0
+    no_repeat_ngram_size: int = 0         # --no-repeat-ngram-size (0 = off: the row kernels without the constraint code)
+    sampling: bool = False                # --sampling / --sampling-topk / --sampling-topp: one draw per row instead of the top 2 * beam
+    topk: int = 0
+    topp: float = 0.0
+    diverse_groups: int = 0               # --diverse-beam-groups / --diverse-beam-strength (sequence_generator.DiverseBeamSearch)
+    diverse_strength: float = 0.0
+    sibling_rate: Optional[float] = None  # --diversity-rate (DiverseSiblingsSearch); None = off, 0 is a legal rate
+    lm_weight: float = 0.0                # --lm-weight: the factor of the language model's log-softmax (shallow fusion)
+
+    def __post_init__(self):
+        opt = lambda f: lambda v: None if v is None else f(v)
+        floor0 = lambda f: lambda v: max(f(v), f(0))
+        norm = dict(beam=int, max_len=int, min_len=int, normalize_scores=bool, len_penalty=float, unk_penalty=float, temperature=float,
+                    no_repeat_ngram_size=int, sampling=bool, topk=floor0(int), topp=floor0(float), diverse_groups=floor0(int),
+                    diverse_strength=float, sibling_rate=opt(float), lm_weight=float)
+        for name, f in norm.items():
+            object.__setattr__(self, name, f(getattr(self, name)))
+        assert self.no_repeat_ngram_size == 0 or self.no_repeat_ngram_size >= 2, "no_repeat_ngram_size is 0 (off) or at least 2"
+
+    def fill(self, d, members):
+        """Write the options into the cst_beam_desc `d` of a step over `members` models.  A strategy that is off leaves its fields at
+        zero: the step then launches the instantiations without it.  cst_beam_step refuses bad values and combinations."""
+        d.beam, d.max_len, d.min_len = self.beam, self.max_len, self.min_len
+        d.unk_penalty, d.len_penalty, d.temperature = self.unk_penalty, self.len_penalty, self.temperature
+        d.normalize_scores = int(self.normalize_scores)
+        d.members = members if members > 1 else 0  # 0: the single-matrix kernels
+        d.no_repeat_ngram = self.no_repeat_ngram_size
+        if self.sampling:
+            d.sampling, d.sample_topk, d.sample_topp = 1, self.topk, self.topp
+        if self.diverse_groups > 0:
+            d.diverse_groups, d.diverse_strength = self.diverse_groups, self.diverse_strength
+        if self.sibling_rate is not None:
+            d.diverse_siblings, d.sibling_rate = 1, self.sibling_rate
+
+
+class Switches(NamedTuple):
+    """The engine's CST_DEC_* environment switches, read once when an engine is built."""
+    cross_kernel: str
+    lanes: int
+    no_ln_fuse: bool
+    no_splitk: bool
+    no_qcross: bool
+
+    @classmethod
+    def read(cls, cross_kernel=None, lanes=None):
+        """Arguments that are not None win over the environment."""
+        env = os.environ
+        return cls(env.get("CST_DEC_CROSS_KERNEL", "auto") if cross_kernel is None else cross_kernel,
+                   max(1, int(env.get("CST_DEC_LANES", "1") if lanes is None else lanes)),
+                   bool(env.get("CST_DEC_NO_LN_FUSE")), bool(env.get("CST_DEC_NO_SPLITK")), bool(env.get("CST_DEC_NO_QCROSS")))
+
+
+class StepPlan(NamedTuple):
+    """Which launches one layer of a member is made of (BeamDecodeEngine._plan decides, everything else reads)."""
+    cross: bool                # the layers have a cross-attention block (a language model's have none)
+    fuse_ln: bool              # the layer's LayerNorms run inside the projections behind them (cst_dec_ln_linear)
+    cross_mode: Optional[str]  # "flash" | "flash_hm" | "shared"; None without a cross block
+    q_in_cross: bool           # the query projection runs inside the cross-attention launch (cst_dec_ln_q_cross_attn)
+    split_fc2: bool            # fc2 as eight K slices + the reduce launch
+
+    @property
+    def head_major(self):
+        """The encoder K/V are stored head-major [bsz, H, S, D]."""
+        return self.cross_mode in ("shared", "flash_hm")
+
+    @property
+    def layer_nodes(self):
+        """Launches per layer: (LayerNorm, qkv, self-attention, out, LayerNorm, fc1, fc2) + the cross block's (LayerNorm, q, cross
+        attention, out); a folded LayerNorm and a query projection inside the attention launch are no launches, the split-K reduce is."""
+        n = (5 if self.fuse_ln else 7) + self.split_fc2
+        return n + ((3 if self.fuse_ln else 4) - self.q_in_cross if self.cross else 0)
+
+
 class BeamDecodeEngine:
-    def __init__(self, decoder, tgt_dict, beam_size, max_len, min_len=1, normalize_scores=True, len_penalty=1.0,
-                 unk_penalty=0.0, temperature=1.0, use_graph=True, poll=8, cross_kernel=None, lanes=None, no_repeat_ngram_size=0,
-                 sampling=False, topk=0, topp=0.0, diverse_groups=0, diverse_strength=0.0, sibling_rate=None, lm_decoder=None,
-                 lm_weight=0.0):
-        # a checkpoint ensemble (--path a.pt:b.pt:c.pt) is a LIST of decoders: every member keeps its own packed weights, K/V caches,
-        # encoder K/V and logits buffer; the beam state (tokens / scores / ancestry, step counter, finalized hypotheses) is shared —
-        # all members follow the same hypotheses, so one ancestry table serves every member's append-only caches
-        self.decs = list(decoder) if isinstance(decoder, (list, tuple)) else [decoder]
+    def __init__(self, decoders, tgt_dict, options, lm_decoder=None, use_graph=True, poll=8, cross_kernel=None, lanes=None):
+        # `decoders`: the list of models of a checkpoint ensemble (--path a.pt:b.pt:c.pt; one model is a list of one).  A language model
+        # (shallow fusion, --lm-path / --lm-weight, sequence_generator.py:318-324) is one more decoder of the step: a decoder WITHOUT
+        # cross attention (lm_supported) whose log-softmax cst_beam_step_lm adds, x lm_weight, to the models' combined log-probabilities.
+        # MEMBERS = the models in order, then the LM.  Every member keeps its own packed weights, activations, K/V caches, encoder K/V
+        # and logits buffer; the beam state (tokens / scores / ancestry, step counter, finalized hypotheses) is shared — all members
+        # follow the same hypotheses, so one ancestry table serves every member's append-only caches.  Three parallel lists in member
+        # order: self.members (decoders), _pack() (weights), st["members"] (buffers).
+        # INVARIANT: packed weights, states and member dicts hold no reference to the engine, to their state or to each other — no
+        # cycles, so a dropped state is freed by reference counting at once and not by the cyclic collector, which could otherwise run
+        # inside a later graph capture.
+        self.opt = options
+        self.decs, self.lm = list(decoders), lm_decoder
         assert 1 <= len(self.decs) <= 8, "cst_beam_step combines at most 8 ensemble members"
-        self.dec = self.decs[0]
-        # shallow fusion (--lm-path / --lm-weight, sequence_generator.py:318-324): a target-side language model is one more decoder of
-        # the step — a decoder WITHOUT cross attention (lm_supported) with its own packed weights, caches and logits buffer, following
-        # the same hypotheses through the shared step / tokens / ancestry — and cst_beam_step_lm adds lm_weight x its log-softmax to the
-        # members' combined log-probabilities inside the row kernel
-        self.lm, self.lm_weight = lm_decoder, float(lm_weight)
         assert self.lm is None or self.lm_supported(self.lm), "the language model's decoder is outside lm_supported()"
         assert self.lm is None or self.lm.output_projection.weight.shape[0] == len(tgt_dict), "the LM's vocabulary must be the target dictionary"
+        self.members = self.decs + ([self.lm] if self.lm is not None else [])
         self.pad, self.unk, self.eos = tgt_dict.pad(), tgt_dict.unk(), tgt_dict.eos()
         self.vocab = len(tgt_dict)
-        self.beam, self.max_len, self.min_len = int(beam_size), int(max_len), int(min_len)
-        self.normalize_scores, self.len_penalty = bool(normalize_scores), float(len_penalty)
-        self.unk_penalty, self.temperature = float(unk_penalty), float(temperature)
         self.use_graph, self.poll = use_graph, max(1, int(poll))
-        # --no-repeat-ngram-size: a parameter of cst_beam_step's row kernel (0 = off: the kernels without the constraint code)
-        self.no_repeat_ngram_size = int(no_repeat_ngram_size)
-        assert self.no_repeat_ngram_size == 0 or self.no_repeat_ngram_size >= 2, "no_repeat_ngram_size is 0 (off) or at least 2"
-        # --sampling / --sampling-topk / --sampling-topp: cst_beam_step draws one token per row instead of selecting the top 2 * beam
-        # (sequence_generator.Sampling is the readable form).  The key of a call's draws lives in a buffer the state owns.
-        self.sampling, self.topk, self.topp = bool(sampling), max(int(topk), 0), max(float(topp), 0.0)
-        # --diverse-beam-groups / --diverse-beam-strength and --diversity-rate (sibling_rate None = off; 0 is a legal rate): parameters of
-        # cst_beam_step's merge kernel, for every vocabulary width (sequence_generator.DiverseBeamSearch / DiverseSiblingsSearch are the
-        # readable forms).  cst_beam_step refuses bad values and combinations.
-        self.diverse_groups, self.diverse_strength = max(int(diverse_groups), 0), float(diverse_strength)
-        self.sibling_rate = None if sibling_rate is None else float(sibling_rate)
-        # cross attention per step: "flash" = cst_attn_fwd with batch = sentence and the beam rows as the query axis (37 us per
-        # layer at 32 x beam 5 x 750 source positions, bf16); "flash_hm" = the same kernel over head-major K/V (contiguous per-head
-        # streams: no faster, 0.811 vs 0.812 ms per step); "shared" = cst_dec_cross_attn (VALU kernel, one pass with online
+        # cross_kernel — cross attention per step: "flash" = cst_attn_fwd with batch = sentence and the beam rows as the query axis
+        # (37 us per layer at 32 x beam 5 x 750 source positions, bf16); "flash_hm" = the same kernel over head-major K/V (contiguous
+        # per-head streams: no faster, 0.811 vs 0.812 ms per step); "shared" = cst_dec_cross_attn (VALU kernel, one pass with online
         # softmax, K/V rows shared by the beam: ~59 us — the 5 queries' dot products per key cost more than the MFMA tile the
         # flash kernel spends on them; kept selectable, covered by the same tests)
         # "auto" (round 5): "shared" where cst_dec_cross_attn runs its matrix-core kernel (bf16, head dim 64, beam <= 32: the four waves
         # of a (sentence, head) workgroup split the keys, 21.5 us per layer against 26.4 for "flash" on s2t_transformer_l), else "flash"
-        if cross_kernel is None:
-            cross_kernel = os.environ.get("CST_DEC_CROSS_KERNEL", "auto")
-        assert cross_kernel in ("auto", "flash", "flash_hm", "shared")
-        self.cross_kernel = cross_kernel
+        self.sw = Switches.read(cross_kernel, lanes)
+        assert self.sw.cross_kernel in ("auto", "flash", "flash_hm", "shared")
         # lanes: the batch may be cut into groups of sentences, each with its own state, step graph and HIP stream, replayed side by
         # side (sentences never interact in beam search: same hypotheses, tests/test_decode_engine_gpu.py).  Measured on MI355X
         # (32 x beam 5, s2t_transformer_l): 1 lane 0.877 ms per step, 2 lanes 0.910, 3 lanes 1.60, 4 lanes 1.63 — the step graphs of
         # different streams do not overlap on this stack (a half-batch step costs 0.455 ms, two of them 0.91), so the default is 1.
-        self.lanes = max(1, int(os.environ.get("CST_DEC_LANES", "1") if lanes is None else lanes))
-        if self.sampling:
-            self.lanes = 1  # the index of a draw holds the sentence's position in the WHOLE batch
+        # (sampling: the index of a draw holds the sentence's position in the WHOLE batch)
+        self.lanes = 1 if self.opt.sampling else self.sw.lanes
         self._packed = None
         self._state = {}
         self._cfg = None
         self._streams = []
 
+    lm_weight = property(lambda self: self.opt.lm_weight)  # (read-only, next to .decs and .lm)
+
     # ------------------------------------------------------------------------------------------------------------
     @staticmethod
-    def supported(decoder):
-        """The fused loop covers the configuration every Chimera / s2t_transformer arch uses: pre-norm layers, sinusoidal
-        positions, encoder attention in every layer, no layernorm_embedding / project_in / adaptive softmax."""
+    def _supported(decoder, cross):
         try:
             ok = (decoder.embed_positions is not None and decoder.layernorm_embedding is None and decoder.project_in_dim is None
                   and decoder.project_out_dim is None and decoder.adaptive_softmax is None and len(decoder.layers) > 0)
+            if not cross:
+                ok = ok and hasattr(decoder.embed_positions, "get_embedding")  # sinusoidal positions
             for l in decoder.layers:
-                ok = ok and l.normalize_before and l.encoder_attn is not None and l.self_attn.head_dim in (32, 64)
-                ok = ok and l.self_attn.q_proj.bias is not None and l.encoder_attn.head_dim == l.self_attn.head_dim
+                ok = ok and l.normalize_before and (l.encoder_attn is not None) == cross and l.self_attn.head_dim in (32, 64)
+                ok = ok and l.self_attn.q_proj.bias is not None and (not cross or l.encoder_attn.head_dim == l.self_attn.head_dim)
             return bool(ok)
         except AttributeError:
             return False
 
     @staticmethod
+    def supported(decoder):
+        """The fused loop covers the configuration every Chimera / s2t_transformer arch uses: pre-norm layers, sinusoidal
+        positions, encoder attention in every layer, no layernorm_embedding / project_in / adaptive softmax."""
+        return BeamDecodeEngine._supported(decoder, True)
+
+    @staticmethod
     def lm_supported(decoder):
         """supported() for a language model: the same decoder without encoder attention in any layer."""
-        try:
-            ok = (decoder.embed_positions is not None and decoder.layernorm_embedding is None and decoder.project_in_dim is None
-                  and decoder.project_out_dim is None and decoder.adaptive_softmax is None and len(decoder.layers) > 0)
-            ok = ok and hasattr(decoder.embed_positions, "get_embedding")  # sinusoidal positions
-            for l in decoder.layers:
-                ok = ok and l.normalize_before and l.encoder_attn is None and l.self_attn.head_dim in (32, 64)
-                ok = ok and l.self_attn.q_proj.bias is not None
-            return bool(ok)
-        except AttributeError:
-            return False
+        return BeamDecodeEngine._supported(decoder, False)
 
     @staticmethod
     def sampling_supported(vocab, dtype):
@@ -126,75 +196,64 @@ class BeamDecodeEngine:
         self._packed = None
         self._state.clear()
 
+    def _plan(self, dec, dtype, rows=None):
+        """The StepPlan of member `dec` at `rows` hypothesis rows — the ONLY place where these decisions are made.  rows None: what holds
+        for any row count up to 1024 (the weights to pack; nodes_per_step's default): LayerNorms folded where they can be, no split."""
+        bf16, C, l0 = dtype == torch.bfloat16, dec.embed_dim, dec.layers[0]
+        D, cross = l0.self_attn.head_dim, l0.encoder_attn is not None
+        matrix_core = bf16 and D == 64 and self.opt.beam <= 32  # cst_dec_cross_attn's matrix-core kernel
+        fuse_ln = bf16 and C % 512 == 0 and (rows is None or rows <= 1024) and not self.sw.no_ln_fuse
+        mode = None if not cross else self.sw.cross_kernel if self.sw.cross_kernel != "auto" else "shared" if matrix_core else "flash"
+        # fc2 (K = 4096) at <= 256 rows: 48 workgroups would stream 170 KB of weights each through a 48 KB ring — 23.7 us; eight K
+        # slices + the reduce launch: 15.3 us although it is a node more (tools/bench_dec_splitk.py; K = 1024 projections lose with any
+        # split).  bf16 only: the fp32 parity configuration keeps the summation order of the module path it is compared with.
+        split_fc2 = bf16 and rows is not None and rows <= 256 and l0.fc1.out_features >= 4096 and not self.sw.no_splitk
+        return StepPlan(cross, fuse_ln, mode, fuse_ln and mode == "shared" and matrix_core and not self.sw.no_qcross, split_fc2)
+
+    def nodes_per_step(self, dtype, rows=None):
+        """Kernel launches (graph nodes) of one decode step: every member's sequence up to its vocabulary projection, then ONE pair of
+        beam-search kernels over the members' logits."""
+        return sum(self._member_nodes(dec, dtype, rows) for dec in self.members) + 2
+
+    def _member_nodes(self, dec, dtype, rows):
+        """embed + the layers (StepPlan.layer_nodes) + final LayerNorm + vocabulary projection."""
+        return 1 + self._plan(dec, dtype, rows).layer_nodes * len(dec.layers) + (1 if dec.layer_norm is not None else 0) + 1
+
     def _pack(self, dtype, device):
-        """Per member and layer the packed [3C, C] self-attention projection (weights are constants in eval mode).  Returns member
-        0's dict; the other members' dicts are its "others" entry (no reference back to itself: a cycle would leave dropped weight
-        copies and graphs to the cyclic collector, which may then run inside a later graph capture)."""
+        """Per member: per layer the packed [3C, C] self-attention projection and the LayerNorm-folded weights the plan asks for, and the
+        position table (weights are constants in eval mode).  Returns the list in member order."""
         # weights may have been updated since the last call (training between validations): re-pack and drop the graphs
         # (autograd versions catch load_state_dict / copy_; optim.PARAM_EPOCH catches the fused optimizer's raw-pointer updates)
-        decs = self.decs + ([self.lm] if self.lm is not None else [])
-        key = (dtype, device, PARAM_EPOCH[0], tuple((p.data_ptr(), p._version) for dec in decs for p in dec.parameters()))
-        if self._packed is not None and self._packed[0] == key:
-            return self._packed[1]
-        self._state.clear()
-        members = [self._pack_member(dec, dtype, device) for dec in self.decs]
-        members[0]["others"] = members[1:]
-        if self.lm is not None:
-            members[0]["lm"] = self._pack_member(self.lm, dtype, device)
-        self._packed = (key, members[0])
+        key = (dtype, device, PARAM_EPOCH[0], tuple((p.data_ptr(), p._version) for dec in self.members for p in dec.parameters()))
+        if self._packed is None or self._packed[0] != key:
+            self._state.clear()
+            self._packed = (key, [self._pack_member(dec, dtype, device) for dec in self.members])
         return self._packed[1]
-
-    @staticmethod
-    def members(d):
-        """[member 0's dict, member 1's, ...] of a state or packed-weights dict."""
-        return [d] + d.get("others", [])
 
     def _pack_member(self, dec, dtype, device):
         layers = []
-        fuse = self._fuse_ln(dtype, dec)
+        plan = self._plan(dec, dtype)
         for l in dec.layers:
-            sa = l.self_attn
+            sa, ca = l.self_attn, l.encoder_attn
             d = dict(
                 wqkv=torch.cat((sa.q_proj.weight, sa.k_proj.weight, sa.v_proj.weight), 0).detach().contiguous(),
                 bqkv=torch.cat((sa.q_proj.bias, sa.k_proj.bias, sa.v_proj.bias), 0).detach().contiguous())
-            if fuse:  # LayerNorm folded into the projection that follows it (include/cst.h: cst_dec_ln_linear)
+            if plan.fuse_ln:  # LayerNorm folded into the projection that follows it (include/cst.h: cst_dec_ln_linear)
                 d["ln_qkv"] = self._fold_ln(l.self_attn_layer_norm, d["wqkv"], d["bqkv"])
-                if l.encoder_attn is not None:  # (a language model's layers have no cross block)
-                    d["ln_q"] = self._fold_ln(l.encoder_attn_layer_norm, l.encoder_attn.q_proj.weight, l.encoder_attn.q_proj.bias)
-                    d["ln_q_frag"] = self.fragment_major(d["ln_q"][0], l.encoder_attn.num_heads)  # cst_dec_ln_q_cross_attn's weight layout
                 d["ln_fc1"] = self._fold_ln(l.final_layer_norm, l.fc1.weight, l.fc1.bias)
+                if plan.cross:
+                    d["ln_q"] = self._fold_ln(l.encoder_attn_layer_norm, ca.q_proj.weight, ca.q_proj.bias)
+                if plan.q_in_cross:
+                    d["ln_q_frag"] = self.fragment_major(d["ln_q"][0], ca.num_heads)  # cst_dec_ln_q_cross_attn's weight layout
+                    assert d["ln_q_frag"] is not None
             layers.append(d)
         pos = dec.embed_positions
-        need = dec.padding_idx + 2 + self.max_len + 1
+        need = dec.padding_idx + 2 + self.opt.max_len + 1
         table = pos.get_embedding(need, pos.embedding_dim, pos.padding_idx).to(device=device, dtype=torch.float32).contiguous()
         # the module path adds positions converted to the storage dtype (models/transformer.py:756 on a .half()/bf16 model)
         if dtype != torch.float32:
             table = table.to(dtype).float()
         return dict(layers=layers, pos=table)
-
-    def nodes_per_step(self, dtype, rows=None):
-        """Kernel launches (graph nodes) of one decode step: embed + per layer (LayerNorm, qkv, self-attention, out, LayerNorm, q,
-        cross-attention, out, LayerNorm, fc1, fc2 — the three LayerNorms folded into their projections on the bf16 path) + final
-        LayerNorm + vocabulary projection + the two beam-search kernels; + the split-K reduce of fc2 where it is split (bf16, <= 256
-        hypothesis rows, ffn >= 4096).  An ensemble runs every member's sequence up to its vocabulary projection, then ONE pair of
-        beam-search kernels over the members' logits.  A language model adds its own sequence without the cross block: per layer
-        (LayerNorm, qkv, self-attention, out, LayerNorm, fc1, fc2), the two LayerNorms folded on the bf16 path."""
-        return sum(self._member_nodes(dec, dtype, rows) for dec in self.decs + ([self.lm] if self.lm is not None else [])) + 2
-
-    def _member_nodes(self, dec, dtype, rows):
-        cross = dec.layers[0].encoder_attn is not None
-        per_layer = (8 if cross else 5) if self._fuse_ln(dtype, dec) else (11 if cross else 7)
-        D = dec.layers[0].self_attn.head_dim
-        if cross and self._fuse_ln(dtype, dec) and self._fuse_q_cross(dtype, D, dec.embed_dim, self._cross_mode(dtype, D)):
-            per_layer -= 1  # the query projection runs inside the cross-attention launch
-        F = dec.layers[0].fc1.out_features
-        if rows is not None and rows <= 256 and F >= 4096 and dtype == torch.bfloat16 and not os.environ.get("CST_DEC_NO_SPLITK"):
-            per_layer += 1
-        return 1 + per_layer * len(dec.layers) + (1 if dec.layer_norm is not None else 0) + 1
-
-    def _fuse_ln(self, dtype, dec=None):
-        C = (self.dec if dec is None else dec).embed_dim
-        return dtype == torch.bfloat16 and C % 512 == 0 and not os.environ.get("CST_DEC_NO_LINEAR") and not os.environ.get("CST_DEC_NO_LN_FUSE")
 
     @staticmethod
     def _fold_ln(ln, w, b):
@@ -215,48 +274,33 @@ class BeamDecodeEngine:
             return None
         return wg.view(H, 2, 32, K // 16, 2, 8).permute(0, 1, 3, 4, 2, 5).contiguous()
 
-    def _ln_linear(self, x, folded, out, act=L.ACT_NONE):
-        wg, sg, sb, eps = folded
-        M, Kd = x.shape
-        L.check(L.load().cst_dec_ln_linear(L.ptr(x), L.ptr(wg), L.ptr(sg), L.ptr(sb), eps, None, L.ptr(out), M, wg.shape[0], Kd,
-                                           x.stride(0), 0, out.stride(0), act, None, 0, L.dtype_code(x.dtype), L.stream_ptr()),
-                "cst_dec_ln_linear")
-
     # ------------------------------------------------------------------------------------------------------------
     def _alloc_member(self, dec, bsz, S, dtype, device, has_mask):
-        """One member's own buffers: activations, logits, append-only self-attention caches, per-sentence encoder K/V (none of the
-        latter for a decoder without cross attention)."""
-        beam, L1 = self.beam, self.max_len + 1
+        """One member's own buffers and its plan: activations, logits, append-only self-attention caches and — with a cross block — the
+        query, the per-sentence encoder K/V and their padding mask."""
+        beam, L1 = self.opt.beam, self.opt.max_len + 1
         bbsz, C, nl = bsz * beam, dec.embed_dim, len(dec.layers)
-        F = dec.layers[0].fc1.out_features
         z = lambda *shape, dt=dtype: torch.zeros(*shape, dtype=dt, device=device)
-        if dec.layers[0].encoder_attn is None:
-            return dict(
-                x=z(bbsz, C), x2=z(bbsz, C), h=z(bbsz, C), qkv=z(bbsz, 3 * C), attn=z(bbsz, C), f=z(bbsz, F),
-                logits=z(bbsz, (self.vocab + 7) // 8 * 8), mean=z(bbsz, dt=torch.float32), rstd=z(bbsz, dt=torch.float32),
-                kc=[z(bbsz, L1, C) for _ in range(nl)], vc=[z(bbsz, L1, C) for _ in range(nl)],
-                gemm_ws=z(8 * bbsz * C * 4 if bbsz <= 256 else 0, dt=torch.uint8))
-        return dict(
-            x=z(bbsz, C), x2=z(bbsz, C), h=z(bbsz, C), qkv=z(bbsz, 3 * C), q=z(bbsz, C), attn=z(bbsz, C), f=z(bbsz, F),
-            logits=z(bbsz, (self.vocab + 7) // 8 * 8),
-            mean=z(bbsz, dt=torch.float32), rstd=z(bbsz, dt=torch.float32), lse=z(bsz * 64 * beam, dt=torch.float32),
+        plan = self._plan(dec, dtype, bbsz)
+        m = dict(
+            plan=plan, x=z(bbsz, C), x2=z(bbsz, C), h=z(bbsz, C), qkv=z(bbsz, 3 * C), attn=z(bbsz, C), f=z(bbsz, dec.layers[0].fc1.out_features),
+            logits=z(bbsz, (self.vocab + 7) // 8 * 8), mean=z(bbsz, dt=torch.float32), rstd=z(bbsz, dt=torch.float32),
             kc=[z(bbsz, L1, C) for _ in range(nl)], vc=[z(bbsz, L1, C) for _ in range(nl)],
-            kx=[z(bsz, S, C) for _ in range(nl)], vx=[z(bsz, S, C) for _ in range(nl)],
-            proj=z(bsz * S, C), kpm=z(bsz, S, dt=torch.uint8) if has_mask else None,
-            gemm_ws=z(8 * bbsz * C * 4 if bbsz <= 256 else 0, dt=torch.uint8))  # split-K partials of the fc2 projection (own buffer: captured)
+            gemm_ws=z(8 * bbsz * C * 4, dt=torch.uint8) if plan.split_fc2 else None)  # split-K partials of the fc2 projection (own buffer: captured)
+        if plan.cross:
+            m.update(q=z(bbsz, C), lse=z(bsz * 64 * beam, dt=torch.float32), kx=[z(bsz, S, C) for _ in range(nl)],
+                     vx=[z(bsz, S, C) for _ in range(nl)], proj=z(bsz * S, C), kpm=z(bsz, S, dt=torch.uint8) if has_mask else None)
+        return m
 
     def _alloc(self, lane, bsz, S, dtype, device, has_mask, prefix_len=0):
-        """S / has_mask: one value per member (members may differ in encoder output length).  prefix_len and no_repeat_ngram_size are
-        kernel parameters baked into the captured graph, so they are part of the state key; the prefix TOKENS live in a buffer the
-        state owns (st["prefix"]), which every call overwrites: a replayed graph reads the new call's prefix."""
-        S = tuple(S) if isinstance(S, (list, tuple)) else (S,) * len(self.decs)
-        has_mask = tuple(has_mask) if isinstance(has_mask, (list, tuple)) else (has_mask,) * len(self.decs)
-        key = (lane, bsz, S, dtype, device, has_mask, prefix_len, self.no_repeat_ngram_size, self.sampling, self.topk, self.topp,
-               self.diverse_groups, self.diverse_strength, self.sibling_rate, id(self.lm), self.lm_weight)
+        """S / has_mask: one value per model (models may differ in encoder output length).  prefix_len and the options are kernel
+        parameters baked into the captured graph, so they are part of the state key; the prefix TOKENS and the sampling key live in
+        buffers the state owns (st["prefix"], st["sample_key"]), which every call overwrites: a replayed graph reads the new call's."""
+        key = (lane, bsz, S, dtype, device, has_mask, prefix_len, self.opt)
         st = self._state.get(key)
         if st is not None:
             return st
-        beam, L1, LT = self.beam, self.max_len + 1, self.max_len + 2
+        beam, L1, LT = self.opt.beam, self.opt.max_len + 1, self.opt.max_len + 2
         bbsz = bsz * beam
         z = lambda *shape, dt=dtype: torch.zeros(*shape, dtype=dt, device=device)
         st = dict(
@@ -264,211 +308,163 @@ class BeamDecodeEngine:
             tokens=z(2, bbsz, LT, dt=torch.int64), scores=z(2, bbsz, L1, dt=torch.float32), anc=z(2, bbsz, L1, dt=torch.int32),
             ignore=z(bsz, beam, dt=torch.uint8), finished=z(bsz, dt=torch.uint8), nfinal=z(bsz, dt=torch.int32),
             fin_tokens=z(bsz, beam, L1, dt=torch.int64), fin_pos=z(bsz, beam, L1, dt=torch.float32),
-            fin_score=z(bsz, beam, dt=torch.float32), fin_len=z(bsz, beam, dt=torch.int32), graph=None)
-        # st itself carries member 0's buffers (the single-model layout); the other members' dicts share the beam state
-        st.update(self._alloc_member(self.decs[0], bsz, S[0], dtype, device, has_mask[0]))
-        st["others"] = []
-        for i, dec in enumerate(self.decs[1:], 1):
-            m = self._alloc_member(dec, bsz, S[i], dtype, device, has_mask[i])
-            m.update(step=st["step"], tokens=st["tokens"], anc=st["anc"])
-            st["others"].append(m)
-        st["lm"], st["lm_desc"] = None, None
+            fin_score=z(bsz, beam, dt=torch.float32), fin_len=z(bsz, beam, dt=torch.int32), graph=None, lm_desc=None,
+            beam_ws=torch.zeros(L.load().cst_beam_workspace(bsz, beam), dtype=torch.uint8, device=device),
+            prefix=torch.full((bsz, prefix_len), self.pad, dtype=torch.int64, device=device) if prefix_len > 0 else None,
+            sample_key=z(1, dt=torch.int32) if self.opt.sampling else None)  # (the 32 bits of the key; the kernel reads them unsigned)
+        ms = [self._alloc_member(dec, bsz, s, dtype, device, hm) for dec, s, hm in zip(self.decs, S, has_mask)]
         if self.lm is not None:
-            m = self._alloc_member(self.lm, bsz, 0, dtype, device, False)
-            m.update(step=st["step"], tokens=st["tokens"], anc=st["anc"])
-            st["lm"] = m
+            ms.append(self._alloc_member(self.lm, bsz, 0, dtype, device, False))
             f = L.LmFusionDesc()
-            f.lm_logits, f.lm_weight, f.lprobs_out = m["logits"].data_ptr(), self.lm_weight, None
+            f.lm_logits, f.lm_weight, f.lprobs_out = ms[-1]["logits"].data_ptr(), self.opt.lm_weight, None
             st["lm_desc"] = f
+        st["members"] = ms
         d = L.BeamDesc()
+        self.opt.fill(d, len(self.decs))
         d.dtype = L.dtype_code(dtype)
-        d.bsz, d.beam, d.vocab, d.max_len = bsz, beam, self.vocab, self.max_len
-        d.pad, d.unk, d.eos, d.min_len = self.pad, self.unk, self.eos, self.min_len
-        d.unk_penalty, d.len_penalty, d.temperature = self.unk_penalty, self.len_penalty, self.temperature
-        d.normalize_scores = int(self.normalize_scores)
-        d.logits, d.ld_logits = st["logits"].data_ptr(), st["logits"].stride(0)
-        d.members = len(self.decs) if len(self.decs) > 1 else 0  # 0: the single-matrix kernels
-        for i, m in enumerate(st["others"]):
+        d.bsz, d.vocab = bsz, self.vocab
+        d.pad, d.unk, d.eos = self.pad, self.unk, self.eos
+        d.logits, d.ld_logits = ms[0]["logits"].data_ptr(), ms[0]["logits"].stride(0)
+        for i, m in enumerate(ms[1:len(self.decs)]):
             d.logits_n[i] = m["logits"].data_ptr()
         d.step, d.tokens, d.scores, d.anc = (st[k].data_ptr() for k in ("step", "tokens", "scores", "anc"))
         d.cands_to_ignore, d.finished, d.nfinal = st["ignore"].data_ptr(), st["finished"].data_ptr(), st["nfinal"].data_ptr()
         d.num_remaining = st["num_remaining"].data_ptr()
         d.fin_tokens, d.fin_pos, d.fin_score, d.fin_len = (st[k].data_ptr() for k in ("fin_tokens", "fin_pos", "fin_score", "fin_len"))
-        st["beam_ws"] = torch.zeros(L.load().cst_beam_workspace(bsz, beam), dtype=torch.uint8, device=device)
         d.workspace = st["beam_ws"].data_ptr()
-        d.no_repeat_ngram = self.no_repeat_ngram_size
-        st["prefix"] = torch.full((bsz, prefix_len), self.pad, dtype=torch.int64, device=device) if prefix_len > 0 else None
         if prefix_len > 0:
             d.prefix_tokens, d.prefix_len = st["prefix"].data_ptr(), prefix_len
-        st["sample_key"] = z(1, dt=torch.int32) if self.sampling else None  # (the 32 bits of the key; the kernel reads them unsigned)
-        if self.sampling:
-            d.sampling, d.sample_topk, d.sample_topp, d.sample_key = 1, self.topk, self.topp, st["sample_key"].data_ptr()
-        if self.diverse_groups > 0:
-            d.diverse_groups, d.diverse_strength = self.diverse_groups, self.diverse_strength
-        if self.sibling_rate is not None:
-            d.diverse_siblings, d.sibling_rate = 1, self.sibling_rate
+        if self.opt.sampling:
+            d.sample_key = st["sample_key"].data_ptr()
         st["desc"] = d
         self._state[key] = st
         return st
 
     # ------------------------------------------------------------------------------------------------------------
     def _linear(self, x, w, b, out, act=L.ACT_NONE, resid=None, ws=None):
+        """out = act(x w^T + b) + resid.  ws: the split-K scratch — given (by fc2 where the plan splits it), the GEMM is split 8 ways."""
         M, Kd = x.shape
-        N = w.shape[0]
-        if (M <= 1024 and x.dtype == torch.bfloat16 and Kd % 512 == 0 and x.stride(0) % 8 == 0 and w.is_contiguous()
-                and os.environ.get("CST_DEC_LINEAR_ALL")):
-            # (A/B switch.  Without a LayerNorm to fold in, the decode-step kernel is no faster than the general GEMM's 64 x 64
-            #  configuration: both sit at the ~8 us a dependent graph node costs on this stack — tools/bench_dec_linear.py)
-            L.check(L.load().cst_dec_linear(L.ptr(x), L.ptr(w), L.ptr(b) if b is not None else None,
-                                            L.ptr(resid) if resid is not None else None, L.ptr(out), M, N, Kd, x.stride(0),
-                                            0 if resid is None else resid.stride(0), out.stride(0), act, None, 0,
-                                            L.dtype_code(x.dtype), L.stream_ptr()), "cst_dec_linear")
-            return
-        # fc2 (K = 4096) at <= 256 rows: 48 workgroups would stream 170 KB of weights each through a 48 KB ring — 23.7 us; eight K
-        # slices + the reduce launch: 15.3 us although it is a node more (tools/bench_dec_splitk.py; K = 1024 projections lose with any
-        # split).  bf16 only: the fp32 parity configuration keeps the summation order of the module path it is compared with.
-        split = 8 if (ws is not None and M <= 256 and Kd >= 4096 and x.dtype == torch.bfloat16 and not os.environ.get("CST_DEC_NO_SPLITK")) else 1
-        K.gemm(x, w, out, M, N, Kd, a_kmajor=1, b_kmajor=1, lda=Kd, ldb=Kd, ldc=out.stride(0), bias=b, act=act,
-               resid=resid, ld_resid=0 if resid is None else resid.stride(0), split_k=split, ws=ws if split > 1 else None)
+        K.gemm(x, w, out, M, w.shape[0], Kd, a_kmajor=1, b_kmajor=1, lda=Kd, ldb=Kd, ldc=out.stride(0), bias=b, act=act,
+               resid=resid, ld_resid=0 if resid is None else resid.stride(0), split_k=1 if ws is None else 8, ws=ws)
 
-    def _cross_mode(self, dtype, D):
-        if self.cross_kernel != "auto":
-            return self.cross_kernel
-        return "shared" if (dtype == torch.bfloat16 and D == 64 and self.beam <= 32) else "flash"
+    def _ln_linear(self, x, folded, out, act=L.ACT_NONE):
+        wg, sg, sb, eps = folded
+        M, Kd = x.shape
+        L.check(L.load().cst_dec_ln_linear(L.ptr(x), L.ptr(wg), L.ptr(sg), L.ptr(sb), eps, None, L.ptr(out), M, wg.shape[0], Kd,
+                                           x.stride(0), 0, out.stride(0), act, None, 0, L.dtype_code(x.dtype), L.stream_ptr()),
+                "cst_dec_ln_linear")
 
-    def _fuse_q_cross(self, dtype, D, C, ck):
-        """The LayerNorm-folded query projection inside the cross-attention launch (cst_dec_ln_q_cross_attn): one node less per layer."""
-        return (ck == "shared" and dtype == torch.bfloat16 and D == 64 and self.beam <= 32 and C % 256 == 0
-                and not os.environ.get("CST_DEC_NO_QCROSS"))
-
-    def _cross_fits(self, dtype, D):
-        """True: the encoder K/V of this engine are stored head-major [bsz, H, S, D]."""
-        return self._cross_mode(dtype, D) in ("shared", "flash_hm")
-
-    def _ln(self, x, ln, out, st):
-        lib = L.load()
-        L.check(lib.cst_layernorm_fwd(L.ptr(x), None, L.ptr(ln.weight), L.ptr(ln.bias), L.ptr(out), None, L.ptr(st["mean"]),
-                                      L.ptr(st["rstd"]), x.shape[0], x.shape[1], ln.eps, L.dtype_code(x.dtype), L.stream_ptr()),
+    def _ln(self, x, ln, out, m):
+        L.check(L.load().cst_layernorm_fwd(L.ptr(x), None, L.ptr(ln.weight), L.ptr(ln.bias), L.ptr(out), None, L.ptr(m["mean"]),
+                                           L.ptr(m["rstd"]), x.shape[0], x.shape[1], ln.eps, L.dtype_code(x.dtype), L.stream_ptr()),
                 "cst_layernorm_fwd")
 
     def _step(self, st, pk, bsz):
         """One decode step: every launch reads the step counter from device memory.  The members' layer sequences follow one another
-        on the one stream (a linear graph; step graphs on several streams do not overlap on this stack — see `lanes`), then the
-        language model's, then ONE beam step reads all their logits."""
-        for dec, m, mpk in zip(self.decs, self.members(st), self.members(pk)):
-            self._step_member(dec, m, mpk, bsz)
+        on the one stream (a linear graph; step graphs on several streams do not overlap on this stack — see `lanes`), then ONE beam
+        step reads all their logits."""
+        for dec, m, mpk in zip(self.members, st["members"], pk):
+            self._step_member(dec, st, m, mpk, bsz)
         if self.lm is None:
             L.check(L.load().cst_beam_step(ctypes.byref(st["desc"]), L.stream_ptr()), "cst_beam_step")
-            return
-        self._step_member(self.lm, st["lm"], pk["lm"], bsz)
-        L.check(L.load().cst_beam_step_lm(ctypes.byref(st["desc"]), ctypes.byref(st["lm_desc"]), L.stream_ptr()), "cst_beam_step_lm")
+        else:
+            L.check(L.load().cst_beam_step_lm(ctypes.byref(st["desc"]), ctypes.byref(st["lm_desc"]), L.stream_ptr()), "cst_beam_step_lm")
 
-    def _step_member(self, dec, st, pk, bsz):
-        """One member's decoder up to its vocabulary projection -> st["logits"]."""
+    def _step_member(self, dec, st, m, pk, bsz):
+        """One member's decoder up to its vocabulary projection -> m["logits"], following the shared st["tokens" / "step" / "anc"]."""
         lib = L.load()
-        bbsz, C = st["x"].shape
-        dt = L.dtype_code(st["x"].dtype)
+        bbsz, C = m["x"].shape
+        dt = L.dtype_code(m["x"].dtype)
         H = dec.layers[0].self_attn.num_heads
         D = C // H
+        fused = m["plan"].fuse_ln
         L.check(lib.cst_dec_embed(L.ptr(st["tokens"]), L.ptr(st["step"]), L.ptr(dec.embed_tokens.weight), L.ptr(pk["pos"]),
-                                  float(dec.embed_scale), dec.padding_idx, L.ptr(st["x"]), bbsz, C, self.max_len,
+                                  float(dec.embed_scale), dec.padding_idx, L.ptr(m["x"]), bbsz, C, self.opt.max_len,
                                   pk["pos"].shape[0], dt, L.stream_ptr()), "cst_dec_embed")
-        x, x2 = st["x"], st["x2"]
+        x, x2 = m["x"], m["x2"]
         for li, layer in enumerate(dec.layers):
-            sa, ca, p = layer.self_attn, layer.encoder_attn, pk["layers"][li]
-            fused = "ln_qkv" in p and bbsz <= 1024
+            sa, p = layer.self_attn, pk["layers"][li]
             if fused:
-                self._ln_linear(x, p["ln_qkv"], st["qkv"])
+                self._ln_linear(x, p["ln_qkv"], m["qkv"])
             else:
-                self._ln(x, layer.self_attn_layer_norm, st["h"], st)
-                self._linear(st["h"], p["wqkv"], p["bqkv"], st["qkv"])
-            L.check(lib.cst_dec_self_attn(L.ptr(st["qkv"]), L.ptr(st["kc"][li]), L.ptr(st["vc"][li]), L.ptr(st["anc"]),
-                                          L.ptr(st["step"]), L.ptr(st["attn"]), bbsz, H, D, self.max_len, float(sa.scaling), dt,
+                self._ln(x, layer.self_attn_layer_norm, m["h"], m)
+                self._linear(m["h"], p["wqkv"], p["bqkv"], m["qkv"])
+            L.check(lib.cst_dec_self_attn(L.ptr(m["qkv"]), L.ptr(m["kc"][li]), L.ptr(m["vc"][li]), L.ptr(st["anc"]),
+                                          L.ptr(st["step"]), L.ptr(m["attn"]), bbsz, H, D, self.opt.max_len, float(sa.scaling), dt,
                                           L.stream_ptr()), "cst_dec_self_attn")
-            self._linear(st["attn"], sa.out_proj.weight, sa.out_proj.bias, x2, resid=x)
+            self._linear(m["attn"], sa.out_proj.weight, sa.out_proj.bias, x2, resid=x)
             x, x2 = x2, x
-            if ca is not None:
-                x, x2 = self._step_cross(layer, li, st, p, x, x2, bsz, fused)
+            if m["plan"].cross:
+                x, x2 = self._step_cross(layer, li, st, m, p, x, x2, bsz)
             act = L.ACT_GELU if layer.activation_fn == "gelu" else L.ACT_RELU
             if fused:
-                self._ln_linear(x, p["ln_fc1"], st["f"], act=act)
+                self._ln_linear(x, p["ln_fc1"], m["f"], act=act)
             else:
-                self._ln(x, layer.final_layer_norm, st["h"], st)
-                self._linear(st["h"], layer.fc1.weight, layer.fc1.bias, st["f"], act=act)
-            self._linear(st["f"], layer.fc2.weight, layer.fc2.bias, x2, resid=x, ws=st["gemm_ws"])
+                self._ln(x, layer.final_layer_norm, m["h"], m)
+                self._linear(m["h"], layer.fc1.weight, layer.fc1.bias, m["f"], act=act)
+            self._linear(m["f"], layer.fc2.weight, layer.fc2.bias, x2, resid=x, ws=m["gemm_ws"])
             x, x2 = x2, x
         if dec.layer_norm is not None:
-            self._ln(x, dec.layer_norm, st["h"], st)
-            feat = st["h"]
-        else:
-            feat = x
-        w = dec.output_projection.weight
-        self._linear(feat, w, None, st["logits"])
+            self._ln(x, dec.layer_norm, m["h"], m)
+        self._linear(x if dec.layer_norm is None else m["h"], dec.output_projection.weight, None, m["logits"])
         # the x/x2 swaps of a step (3 per layer, 2 without a cross block) may leave the residual stream in x2: the NEXT step's embed
-        # always writes st["x"], and every step performs the same swaps, so the captured sequence is step-invariant.
+        # always writes m["x"], and every step performs the same swaps, so the captured sequence is step-invariant.
 
-    def _step_cross(self, layer, li, st, p, x, x2, bsz, fused):
+    def _step_cross(self, layer, li, st, m, p, x, x2, bsz):
         """The cross-attention block of one layer (query projection, attention over the sentence's encoder K/V, out-proj + residual);
         returns the swapped (x, x2)."""
         lib = L.load()
-        bbsz, C = st["x"].shape
-        dt = L.dtype_code(st["x"].dtype)
-        ca = layer.encoder_attn
+        bbsz, C = m["x"].shape
+        dt = L.dtype_code(m["x"].dtype)
+        ca, plan, beam = layer.encoder_attn, m["plan"], self.opt.beam
         H = layer.self_attn.num_heads
         D = C // H
-        S = st["kx"][li].shape[1]
-        ck = self._cross_mode(st["x"].dtype, D)
-        qfused = fused and p.get("ln_q_frag") is not None and self._fuse_q_cross(st["x"].dtype, D, C, ck)
-        if qfused:
-            pass  # the query projection runs inside the cross-attention launch below
-        elif fused:
-            self._ln_linear(x, p["ln_q"], st["q"])
-        else:
-            self._ln(x, layer.encoder_attn_layer_norm, st["h"], st)
-            self._linear(st["h"], ca.q_proj.weight, ca.q_proj.bias, st["q"])
+        S = m["kx"][li].shape[1]
         # cross attention: one workgroup per (sentence, head); the sentence's K/V rows serve all of its beam rows
-        if qfused:
+        if plan.q_in_cross:  # the query projection runs inside the cross-attention launch
             _, sg, sb, eps = p["ln_q"]
-            L.check(lib.cst_dec_ln_q_cross_attn(L.ptr(x), x.stride(0), L.ptr(p["ln_q_frag"]), L.ptr(sg), L.ptr(sb), eps, L.ptr(st["kx"][li]),
-                                                L.ptr(st["vx"][li]), L.ptr(st["kpm"]), L.ptr(st["attn"]), L.ptr(st["step"]), self.max_len,
-                                                bsz, self.beam, H, D, S, float(ca.scaling), dt, L.stream_ptr()), "cst_dec_ln_q_cross_attn")
-        elif ck == "flash_hm":  # the flash kernel over head-major K/V: (b, h, t) strides = (H*S*D, S*D, D)
-            q3, o3 = st["q"].view(bsz, self.beam, C), st["attn"].view(bsz, self.beam, C)
-            d = K.attn_desc(q3, st["kx"][li], st["vx"][li], o3, st["lse"], H, D, st["kpm"], False, float(ca.scaling))
-            d.k_sb = d.v_sb = H * S * D
-            d.k_sh = d.v_sh = S * D
-            d.k_st = d.v_st = D
-            K.attn_fwd_desc(d)
-        elif ck == "shared":
-            L.check(lib.cst_dec_cross_attn(L.ptr(st["q"]), L.ptr(st["kx"][li]), L.ptr(st["vx"][li]), L.ptr(st["kpm"]), L.ptr(st["attn"]),
-                                           L.ptr(st["step"]), self.max_len, bsz, self.beam, H, D, S, float(ca.scaling), dt,
-                                           L.stream_ptr()), "cst_dec_cross_attn")
-        else:  # very long sources: the flash kernel with batch = sentence, query "time" axis = the beam rows
-            q3, o3 = st["q"].view(bsz, self.beam, C), st["attn"].view(bsz, self.beam, C)
-            d = K.attn_desc(q3, st["kx"][li], st["vx"][li], o3, st["lse"], H, D, st["kpm"], False, float(ca.scaling))
-            K.attn_fwd_desc(d)
-        self._linear(st["attn"], ca.out_proj.weight, ca.out_proj.bias, x2, resid=x)
+            L.check(lib.cst_dec_ln_q_cross_attn(L.ptr(x), x.stride(0), L.ptr(p["ln_q_frag"]), L.ptr(sg), L.ptr(sb), eps, L.ptr(m["kx"][li]),
+                                                L.ptr(m["vx"][li]), L.ptr(m["kpm"]), L.ptr(m["attn"]), L.ptr(st["step"]), self.opt.max_len,
+                                                bsz, beam, H, D, S, float(ca.scaling), dt, L.stream_ptr()), "cst_dec_ln_q_cross_attn")
+        else:
+            if plan.fuse_ln:
+                self._ln_linear(x, p["ln_q"], m["q"])
+            else:
+                self._ln(x, layer.encoder_attn_layer_norm, m["h"], m)
+                self._linear(m["h"], ca.q_proj.weight, ca.q_proj.bias, m["q"])
+            if plan.cross_mode == "shared":
+                L.check(lib.cst_dec_cross_attn(L.ptr(m["q"]), L.ptr(m["kx"][li]), L.ptr(m["vx"][li]), L.ptr(m["kpm"]), L.ptr(m["attn"]),
+                                               L.ptr(st["step"]), self.opt.max_len, bsz, beam, H, D, S, float(ca.scaling), dt,
+                                               L.stream_ptr()), "cst_dec_cross_attn")
+            else:  # the flash kernel with batch = sentence, query "time" axis = the beam rows (very long sources)
+                q3, o3 = m["q"].view(bsz, beam, C), m["attn"].view(bsz, beam, C)
+                d = K.attn_desc(q3, m["kx"][li], m["vx"][li], o3, m["lse"], H, D, m["kpm"], False, float(ca.scaling))
+                if plan.cross_mode == "flash_hm":  # over head-major K/V: (b, h, t) strides = (H*S*D, S*D, D)
+                    d.k_sb = d.v_sb = H * S * D
+                    d.k_sh = d.v_sh = S * D
+                    d.k_st = d.v_st = D
+                K.attn_fwd_desc(d)
+        self._linear(m["attn"], ca.out_proj.weight, ca.out_proj.bias, x2, resid=x)
         return x2, x
 
     # ------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def generate(self, encoder_out, bsz, prefix_tokens=None, sample_key=0):
-        """encoder_out: EncoderOut with encoder_out [S, B, C] (T x B x C view) and encoder_padding_mask [B, S] or None — for an
-        ensemble a list with one EncoderOut per member (each member's own encoder; lengths S and widths may differ).
+    def generate(self, encoder_outs, bsz, prefix_tokens=None, sample_key=0):
+        """encoder_outs: one EncoderOut per model, each with encoder_out [S, B, C] (T x B x C view) and encoder_padding_mask [B, S] or
+        None (each model's own encoder; lengths S and widths may differ).
         prefix_tokens: None or int64 [bsz, K] padded with pad, K <= max_len: the tokens forced at the first K steps (--prefix-size);
         it is copied into the engine's own buffer (the caller's tensor is never captured).
         sample_key: the 32-bit key of this call's draws (sampling only), written into the state's buffer before the first step: the
         captured step graph reads it there, so a replay draws with the key of the call that replays it.
         Returns the reference's `finalized` structure (list over sentences of hypothesis dicts, best first)."""
         prefix_len = 0 if prefix_tokens is None else int(prefix_tokens.shape[1])
-        assert prefix_tokens is None or (prefix_tokens.dim() == 2 and prefix_tokens.shape[0] == bsz and prefix_len <= self.max_len)
-        eouts = [encoder_out] if hasattr(encoder_out, "encoder_out") else list(encoder_out)  # (an EncoderOut is itself a tuple)
-        assert len(eouts) == len(self.decs), "one encoder output per ensemble member"
-        encs = [e.encoder_out for e in eouts]
+        assert prefix_tokens is None or (prefix_tokens.dim() == 2 and prefix_tokens.shape[0] == bsz and prefix_len <= self.opt.max_len)
+        assert len(encoder_outs) == len(self.decs), "one encoder output per ensemble member"
+        encs = [e.encoder_out for e in encoder_outs]
         assert all(e.shape[1] == bsz for e in encs)
         dtype, device = encs[0].dtype, encs[0].device
         assert all(e.dtype == dtype for e in encs), "ensemble members must share the storage dtype"
-        masks = [e.encoder_padding_mask for e in eouts]
+        masks = [e.encoder_padding_mask for e in encoder_outs]
         masks = [m if (m is not None and m.dim() == 2) else None for m in masks]
         S, has_mask = tuple(e.shape[0] for e in encs), tuple(m is not None for m in masks)
         pk = self._pack(dtype, device)
@@ -483,7 +479,7 @@ class BeamDecodeEngine:
             self._streams.append(torch.cuda.Stream(device=device))
         encb = [e.transpose(0, 1) for e in encs]
         encb = [e if e.is_contiguous() else e.contiguous() for e in encb]
-        total = self.max_len + 1
+        total = self.opt.max_len + 1
         runs = []
         for i, (b0, b1) in enumerate(bounds):
             stream = main if lanes == 1 else self._streams[i]
@@ -493,7 +489,7 @@ class BeamDecodeEngine:
                 st = self._alloc(i, b1 - b0, S, dtype, device, has_mask, prefix_len)
                 if prefix_len > 0:  # the lane's sentences' prefixes, into the buffer the (captured) beam step reads
                     st["prefix"].copy_(prefix_tokens[b0:b1].to(device=device, dtype=torch.int64))
-                if self.sampling:
+                if self.opt.sampling:
                     k32 = int(sample_key) & 0xFFFFFFFF
                     st["sample_key"].fill_(k32 - (1 << 32) if k32 >= (1 << 31) else k32)
                 done = self._begin(st, pk, [e[b0:b1] for e in encb], [m[b0:b1] if m is not None else None for m in masks], b1 - b0)
@@ -523,28 +519,28 @@ class BeamDecodeEngine:
                 main.wait_stream(r["stream"])
         return finalized
 
-    def _begin_member(self, dec, st, encb, mask, bsz):
-        """The static cross-attention K/V of one member, projected from ITS encoder's output."""
+    def _begin_member(self, dec, m, encb, mask, bsz):
+        """The static cross-attention K/V of one model, projected from ITS encoder's output."""
         S, Ce = encb.shape[1], encb.shape[2]
         flat = encb.reshape(bsz * S, Ce)
         for li, layer in enumerate(dec.layers):  # static cross-attention K/V, once per sentence (not per beam)
             ca = layer.encoder_attn
-            if self._cross_fits(st["x"].dtype, ca.head_dim):  # head-major [bsz, H, S, D] for cst_dec_cross_attn (one transposing copy per call)
+            if m["plan"].head_major:  # [bsz, H, S, D] (one transposing copy per call)
                 for name, proj in (("kx", ca.k_proj), ("vx", ca.v_proj)):
-                    self._linear(flat, proj.weight, proj.bias, st["proj"])
-                    st[name][li].view(bsz, ca.num_heads, S, ca.head_dim).copy_(
-                        st["proj"].view(bsz, S, ca.num_heads, ca.head_dim).transpose(1, 2))
+                    self._linear(flat, proj.weight, proj.bias, m["proj"])
+                    m[name][li].view(bsz, ca.num_heads, S, ca.head_dim).copy_(
+                        m["proj"].view(bsz, S, ca.num_heads, ca.head_dim).transpose(1, 2))
             else:
-                self._linear(flat, ca.k_proj.weight, ca.k_proj.bias, st["kx"][li].view(bsz * S, -1))
-                self._linear(flat, ca.v_proj.weight, ca.v_proj.bias, st["vx"][li].view(bsz * S, -1))
+                self._linear(flat, ca.k_proj.weight, ca.k_proj.bias, m["kx"][li].view(bsz * S, -1))
+                self._linear(flat, ca.v_proj.weight, ca.v_proj.bias, m["vx"][li].view(bsz * S, -1))
         if mask is not None:
-            st["kpm"].copy_(mask.to(torch.uint8))
+            m["kpm"].copy_(mask.to(torch.uint8))
 
     def _begin(self, st, pk, encb, mask, bsz):
-        """Queues the per-call work of one lane on the current stream: every member's static cross-attention K/V of its sentences, the beam
+        """Queues the per-call work of one lane on the current stream: every model's static cross-attention K/V of its sentences, the beam
         state, and — first call of a configuration — the eager step 0 and the capture of the step graph.  Returns the number of
         decode steps already taken (1 after that eager step, else 0)."""
-        for dec, m, e, mk in zip(self.decs, self.members(st), encb, mask):
+        for dec, m, e, mk in zip(self.decs, st["members"], encb, mask):  # (the LM, last of the members, has no encoder: zip stops before it)
             self._begin_member(dec, m, e, mk, bsz)
         L.check(L.load().cst_beam_init(ctypes.byref(st["desc"]), L.stream_ptr()), "cst_beam_init")
         if self.use_graph and st["graph"] is None:

@@ -16,6 +16,7 @@ step), like the dropout masks of rng.py — so the engine and the host loop belo
 
 Differences that do not change results: finished sentences are masked out instead of being removed from the batch
 (the reference shrinks the batch, :427-463 — an optimisation only; every sentence's search is independent)."""
+import dataclasses
 import math
 from typing import Dict, List, Optional
 
@@ -24,6 +25,7 @@ import torch
 from torch import Tensor
 
 from . import rng
+from .decode_engine import BeamDecodeEngine, DecodeOptions
 
 
 class BeamSearch:
@@ -218,17 +220,25 @@ class SequenceGenerator:
         # DiverseBeamSearch and DiverseSiblingsSearch (exactly those classes: a subclass may select differently), which cst_beam_step
         # runs itself.
         self.sampling = isinstance(self.search, Sampling)  # (the host loop hands key and max_len to any Sampling, a subclass included)
-        on_engine = search_strategy is None or type(self.search) in (Sampling, DiverseBeamSearch, DiverseSiblingsSearch)
-        # (a negative strength or rate is a reward: the reference accepts it, cst_beam_step does not — a reward can lift tokens from
-        #  outside the rows' top 2 * beam lists or unsort them — so such a search takes the host loop)
-        if type(self.search) is DiverseBeamSearch and not self.search.diversity_strength >= 0:
-            on_engine = False
-        if type(self.search) is DiverseSiblingsSearch and not self.search.diversity_rate >= 0:
-            on_engine = False
-        self.fused = bool(fused) and on_engine and (eos is None or eos == tgt_dict.eos())
+        # `strategy`: the strategy as engine options; None = it needs the host loop.  (A negative strength or rate is a reward: the
+        # reference accepts it, cst_beam_step does not — a reward can lift tokens from outside the rows' top 2 * beam lists or unsort
+        # them — so such a search takes the host loop.)
+        kind, s, strategy = type(self.search), self.search, None
+        if search_strategy is None:
+            strategy = {}
+        elif kind is Sampling:
+            strategy = dict(sampling=True, topk=s.sampling_topk, topp=s.sampling_topp)
+        elif kind is DiverseBeamSearch and s.diversity_strength >= 0:
+            strategy = dict(diverse_groups=s.num_groups, diverse_strength=s.diversity_strength)
+        elif kind is DiverseSiblingsSearch and s.diversity_rate >= 0:
+            strategy = dict(sibling_rate=s.diversity_rate)
+        self.fused = bool(fused) and strategy is not None and (eos is None or eos == tgt_dict.eos())
         if isinstance(self.search, DiverseBeamSearch) and self.beam_size % self.search.num_groups != 0:
             raise ValueError("DiverseBeamSearch requires --beam to be divisible by the number of groups (beam %d, %d groups)"
                              % (self.beam_size, self.search.num_groups))
+        # the engine's options but for max_len, which a call's source length decides
+        self.options = DecodeOptions(self.beam_size, 0, min_len, normalize_scores, len_penalty, unk_penalty, temperature,
+                                     self.no_repeat_ngram_size, lm_weight=self.lm_weight, **strategy) if self.fused else None
         # sampling: the key of a call's draws = hash of (seed, the call's ordinal in this generator)
         self.seed, self.calls = int(seed), 0
         self._engine = None
@@ -312,28 +322,18 @@ class SequenceGenerator:
                 prefix_tokens = None
         encoder_outs = [m.encoder.forward_torchscript(net_input) for m in self.models]
         if self.fused:
-            from .decode_engine import BeamDecodeEngine
             ok = len(self.models) <= 8 and all(BeamDecodeEngine.supported(m.decoder) for m in self.models)  # else the whole ensemble takes the host loop
             if self.lm_model is not None:  # (an LM the engine cannot take sends the whole decode to the host loop)
                 ok = ok and BeamDecodeEngine.lm_supported(self.lm_model.decoder)
             if self.sampling:  # (the wide-vocabulary row kernel only selects: such vocabularies are sampled by the host loop)
                 ok = ok and BeamDecodeEngine.sampling_supported(self.vocab_size, encoder_outs[0].encoder_out.dtype)
             if ok:
-                if self._engine is None or self._engine.max_len != max_len:
-                    decs = [m.decoder for m in self.models]
-                    self._engine = BeamDecodeEngine(decs if len(decs) > 1 else decs[0], self.tgt_dict, beam_size, max_len, self.min_len,
-                                                    self.normalize_scores, self.len_penalty, self.unk_penalty, self.temperature,
-                                                    use_graph=self.use_graph, cross_kernel=self.cross_kernel,
-                                                    no_repeat_ngram_size=self.no_repeat_ngram_size, sampling=self.sampling,
-                                                    topk=self.search.sampling_topk if self.sampling else 0,
-                                                    topp=self.search.sampling_topp if self.sampling else 0.0,
-                                                    diverse_groups=self.search.num_groups if type(self.search) is DiverseBeamSearch else 0,
-                                                    diverse_strength=getattr(self.search, "diversity_strength", 0.0),
-                                                    sibling_rate=self.search.diversity_rate if type(self.search) is DiverseSiblingsSearch else None,
+                if self._engine is None or self._engine.opt.max_len != max_len:
+                    self._engine = BeamDecodeEngine([m.decoder for m in self.models], self.tgt_dict,
+                                                    dataclasses.replace(self.options, max_len=max_len),
                                                     lm_decoder=None if self.lm_model is None else self.lm_model.decoder,
-                                                    lm_weight=self.lm_weight)
-                return self._engine.generate(encoder_outs if len(encoder_outs) > 1 else encoder_outs[0], bsz, prefix_tokens=prefix_tokens,
-                                             sample_key=key)
+                                                    use_graph=self.use_graph, cross_kernel=self.cross_kernel)
+                return self._engine.generate(encoder_outs, bsz, prefix_tokens=prefix_tokens, sample_key=key)
         new_order = torch.arange(bsz, device=device).view(-1, 1).repeat(1, beam_size).view(-1)
         encoder_outs = [m.encoder.reorder_encoder_out(e, new_order) for m, e in zip(self.models, encoder_outs)]
         incremental_states: List[Dict[str, Dict[str, Optional[Tensor]]]] = [{} for _ in self.models]

@@ -226,7 +226,7 @@ def test_replayed_graph_reads_the_new_prefix_and_has_no_extra_node():
     rows = 4 * 4
     assert gen._engine.nodes_per_step(torch.float32, rows) == off._engine.nodes_per_step(torch.float32, rows)
     # ... and the count is the captured graph's own: the engine's launch sequence does not depend on the constraints
-    assert gen._engine.no_repeat_ngram_size == 3 and off._engine.no_repeat_ngram_size == 0
+    assert gen._engine.opt.no_repeat_ngram_size == 3 and off._engine.opt.no_repeat_ngram_size == 0
 
 
 # ---- 5. the command line ----------------------------------------------------------------------------------------------------

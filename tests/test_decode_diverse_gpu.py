@@ -205,7 +205,7 @@ def test_engine_equals_host_loop_on_an_ensemble_with_two_groups():
     fused = sg.SequenceGenerator(models, d, search_strategy=sg.DiverseBeamSearch(d, 2, 0.5), **kw)
     mirror = sg.SequenceGenerator(models, d, search_strategy=sg.DiverseBeamSearch(d, 2, 0.5), fused=False, **kw)
     h1, h2 = fused.generate(models, sample), mirror.generate(models, sample)
-    assert fused._engine is not None and len(fused._engine.decs) == 2 and fused._engine.diverse_groups == 2 and mirror._engine is None
+    assert fused._engine is not None and len(fused._engine.decs) == 2 and fused._engine.opt.diverse_groups == 2 and mirror._engine is None
     plain = _flat(sg.SequenceGenerator(models, d, **kw).generate(models, sample))
     for b in range(4):
         assert len(h1[b]) == len(h2[b]) == 4
@@ -230,7 +230,7 @@ def test_step_graph_has_the_same_nodes_with_a_diverse_strategy():
         eng = gen._engine
         states = list(eng._state.values())
         assert len(states) == 1 and states[0]["graph"] is not None
-        assert (eng.diverse_groups, eng.sibling_rate) == {"plain": (0, None), "groups": (2, None), "siblings": (0, 0.5)}[name]
+        assert (eng.opt.diverse_groups, eng.opt.sibling_rate) == {"plain": (0, None), "groups": (2, None), "siblings": (0, 0.5)}[name]
         st, pk = states[0], eng._packed[1]
         lib.check(lib.load().cst_beam_init(ctypes.byref(st["desc"]), lib.stream_ptr()), "cst_beam_init")  # back to step 0
         torch.cuda.synchronize()

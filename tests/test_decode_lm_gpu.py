@@ -331,8 +331,11 @@ def test_engine_equals_host_loop_with_a_deeper_lm():
     eng = fused._engine
     assert eng is not None and host._engine is None and len(eng.lm.layers) == 3 and len(eng.decs[0].layers) == 2
     st = next(iter(eng._state.values()))
-    assert "kx" not in st["lm"] and "q" not in st["lm"] and len(st["lm"]["kc"]) == 3 and st["lm"]["tokens"] is st["tokens"]
-    assert all("ln_q" not in p for p in eng._packed[1]["lm"]["layers"])
+    assert len(st["members"]) == 2 and eng.members[-1] is eng.lm
+    m_lm = st["members"][-1]
+    assert "kx" not in m_lm and "q" not in m_lm and len(m_lm["kc"]) == 3
+    assert all(k in st for k in ("tokens", "step", "anc")) and not any(k in m for m in st["members"] for k in ("tokens", "step", "anc"))
+    assert all("ln_q" not in p for p in eng._packed[1][-1]["layers"])
     for b in range(5):
         assert len(h1[b]) == len(h2[b]) == 4
         for r in range(4):
@@ -382,7 +385,7 @@ def test_bf16_real_dimensions():
     h1 = fused.generate([model], sample)
     h2 = SG()([model], task.target_dictionary, fused=False, **kw).generate([model], sample)
     eng = fused._engine
-    assert eng.lm is lm.decoder and all("ln_qkv" in p and "ln_fc1" in p and "ln_q" not in p for p in eng._packed[1]["lm"]["layers"])
+    assert eng.lm is lm.decoder and all("ln_qkv" in p and "ln_fc1" in p and "ln_q" not in p for p in eng._packed[1][-1]["layers"])
     assert eng._member_nodes(lm.decoder, torch.bfloat16, 40) == 1 + 6 * 2 + 1 + 1  # folded LayerNorms, fc2 split: 6 nodes per layer
     agree = 0
     for b in range(8):

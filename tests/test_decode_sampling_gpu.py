@@ -319,7 +319,7 @@ def test_wide_vocabulary_takes_the_host_loop_and_the_node_count_is_unchanged():
     samp.generate([model], sample)
     off.generate([model], sample)
     rows = 4 * 4
-    assert samp._engine.sampling and not off._engine.sampling
+    assert samp._engine.opt.sampling and not off._engine.opt.sampling
     assert samp._engine.nodes_per_step(torch.float32, rows) == off._engine.nodes_per_step(torch.float32, rows)
 
 

@@ -214,7 +214,7 @@ def test_engine_equals_host_loop_members_of_different_depth_and_source_length():
     eng = fused._engine
     assert eng is not None and host._engine is None and [len(d.layers) for d in eng.decs] == [2, 3]
     st = next(iter(eng._state.values()))
-    ms = eng.members(st)
+    ms = st["members"]
     assert len(ms) == 2 and ms[0]["kx"][0].shape[1] == ms[1]["kx"][0].shape[1] + 5
     seen = set()
     for b in range(4):
