@@ -248,6 +248,11 @@ def generate_parser():
     p.add_argument("--diverse-beam-strength", type=float, default=0.5, help="the penalty per earlier choice of a token (diverse beam search)")
     p.add_argument("--diversity-rate", type=float, default=-1.0, help="diverse siblings search: the p-th best continuation of a hypothesis "
                    "loses p times this rate (0 equals beam search; negative = off)")
+    p.add_argument("--constraints", nargs="?", const="ordered", default=None, choices=["ordered", "unordered"],
+                   help="lexically constrained decoding: the phrases of --constraints-file must appear in the translation, in the given "
+                   "order (ordered, the default) or in any order")
+    p.add_argument("--constraints-file", default=None, help="one line per utterance: id<TAB>phrase<TAB>phrase... (the id of the manifest; "
+                   "phrases are tokenised like target text; utterances without a line are unconstrained)")
     p.add_argument("--score-reference", action="store_true", help="just score the reference translation")
     p.add_argument("--lm-path", default=None, help="a transformer_lm checkpoint over the TARGET dictionary: its next-token log-probabilities "
                    "are added to the model's at every step (shallow fusion)")
@@ -275,11 +280,58 @@ def check_generate_args(args):
         raise ValueError("Provided Search parameters are mutually exclusive.")
     if args.diverse_beam_groups > 0 and args.beam % args.diverse_beam_groups != 0:
         raise ValueError("DiverseBeamSearch requires --beam to be divisible by the number of groups")
+    if (args.constraints is None) != (args.constraints_file is None):
+        raise ValueError("--constraints and --constraints-file go together")
+    if args.constraints is not None:
+        if args.sampling or args.diverse_beam_groups > 0 or args.diversity_rate > -1:
+            raise ValueError("Provided Search parameters are mutually exclusive: --constraints with sampling or a diverse strategy.")
+        if args.prefix_size > 0:
+            raise ValueError("--constraints cannot be combined with --prefix-size")
+        if args.score_reference:
+            raise ValueError("--constraints cannot be combined with --score-reference: nothing is searched")
     if args.lm_weight != 0.0 and args.lm_path is None:
         raise ValueError("--lm-weight requires --lm-path")
     if args.lm_path is not None and args.score_reference:
         raise ValueError("--lm-path cannot be combined with --score-reference: the scorer has no language model")
     return args
+
+
+def read_constraints_file(path):
+    """{utterance id: [phrase, ...]} of a constraints file: one line per utterance, id<TAB>phrase<TAB>phrase... (the tab-separated
+    phrases fairseq-interactive takes after the source, keyed by the manifest's id).  An id with no phrase has no constraints."""
+    table = {}
+    with open(path, encoding="utf-8") as f:
+        for n, line in enumerate(f, 1):
+            line = line.rstrip("\n")
+            if not line.strip():
+                continue
+            uid, *phrases = line.split("\t")
+            if uid in table:
+                raise ValueError("%s:%d: utterance id %r occurs twice" % (path, n, uid))
+            if any(not ph.strip() for ph in phrases):
+                raise ValueError("%s:%d: an empty phrase" % (path, n))
+            table[uid] = [ph.strip() for ph in phrases]
+    return table
+
+
+def encode_constraints(dataset, table, tgt_dict):
+    """Per item of `dataset` (one manifest) its constraints as lists of token ids: every phrase is encoded exactly like target text
+    (tokenize_text(..., "target"), then encode_line without new symbols and without eos).  Ids of the file the manifest does not have
+    are an error."""
+    manifests = getattr(dataset, "datasets", [dataset])
+    if len(manifests) != 1:
+        raise ValueError("--constraints-file names utterances by the id of ONE manifest; the subset has %d" % len(manifests))
+    ds = manifests[0]
+    if getattr(ds, "ids", None) is None:
+        raise ValueError("--constraints-file needs the manifest's id column")
+    unknown = sorted(set(table) - set(ds.ids))
+    if unknown:
+        raise ValueError("--constraints-file: ids that are not in the manifest: %s" % ", ".join(map(repr, unknown[:8])))
+    out = []
+    for uid in ds.ids:
+        out.append([tgt_dict.encode_line(ds.tokenize_text(ph, "target"), add_if_not_exist=False, append_eos=False).long().tolist()
+                    for ph in table.get(uid, [])])
+    return out
 
 
 def generate_main(argv=None):
@@ -302,6 +354,10 @@ def generate_main(argv=None):
         lm = checkpoint_utils.load_language_model(args.lm_path, task.target_dictionary).to("cuda", dtype).eval()
     gen = task.build_generator(models, args, extra_gen_cls_kwargs={"lm_model": lm, "lm_weight": args.lm_weight})
     tgt_dict = task.target_dictionary
+    lexical = None
+    if args.constraints is not None:
+        from .lexical_constraints import pack_constraints
+        lexical = encode_constraints(ds, read_constraints_file(args.constraints_file), tgt_dict)
     if args.results_path:
         os.makedirs(args.results_path, exist_ok=True)
     out = open(os.path.join(args.results_path, "generate-%s.txt" % args.gen_subset), "w") if args.results_path else sys.stdout
@@ -336,11 +392,17 @@ def generate_main(argv=None):
                 raise ValueError("--score-reference needs the references of the subset (no target in this batch)")
             s["net_input"]["prev_output_tokens"] = sample["net_input"]["prev_output_tokens"].cuda()
             s["target"] = sample["target"].cuda()
-        results = task.inference_step(gen, models, s, prefix_tokens=prefix)
+        packed = None
+        if lexical is not None:  # interactive.py:188-197: the batch's constraints, packed
+            packed = pack_constraints([lexical[i] for i in sample["id"].tolist()], pad=tgt_dict.pad(), eos=tgt_dict.eos())
+        results = task.inference_step(gen, models, s, prefix_tokens=prefix, constraints=packed)
         for i, sid in enumerate(sample["id"].tolist()):
             ref = tgt_dict.string(sample["target"][i]) if sample.get("target") is not None else None
             if not args.quiet and ref is not None:
                 print("T-%d\t%s" % (sid, ref), file=out)
+            if not args.quiet and lexical is not None:  # interactive.py:257-260
+                for c in lexical[sid]:
+                    print("C-%d\t%s" % (sid, tgt_dict.string(torch.tensor(c))), file=out)
             for j, hj in enumerate(results[i][:args.nbest]):  # fairseq_cli/generate.py: hypos[i][:args.nbest]
                 hyp_j = tgt_dict.string(hj["tokens"].cpu())
                 if not args.quiet:
@@ -360,7 +422,7 @@ def generate_main(argv=None):
                "sampling": bool(args.sampling), "nbest": args.nbest, "seed": args.seed,
                "diverse_beam_groups": args.diverse_beam_groups, "diverse_beam_strength": args.diverse_beam_strength,
                "diversity_rate": args.diversity_rate, "score_reference": bool(args.score_reference),
-               "lm_path": args.lm_path, "lm_weight": args.lm_weight,
+               "lm_path": args.lm_path, "lm_weight": args.lm_weight, "constraints": args.constraints,
                "bleu4_whitespace": corpus_bleu(hyps, refs) if any(refs) else None, "ignored_flags": ignored}
     print(json.dumps(summary), file=out, flush=True)
     if out is not sys.stdout:

@@ -101,6 +101,188 @@ template <bool LM> using LmArg = std::conditional_t<LM, LmP, NoLm>;
 // lp' of one element (no contraction to an fma: the reference rounds the product)
 __device__ __forceinline__ float lm_fuse(float lp, float w, float x_lm, float lse_lm) { return __fadd_rn(lp, __fmul_rn(w, x_lm - lse_lm)); }
 
+// LEX (lexical constraints, search.py LexicallyConstrainedBeamSearch :210-523 with token_generation_constraints.py; cst_beam_step_lex):
+// every hypothesis row carries a constraint STATE, every sentence a TABLE its states move in, both int32 words in the workspace of
+// cst_lex_desc (cst_lex_init builds the tables and the root states):
+//   table  [LEX_TBL_W]: [0] nd = the sentence's DISTINCT constraint tokens, [1] n, [2] representation, then four arrays of LEX_NODES:
+//          ordered (1): n = constraint tokens in all; A = the concatenated constraints, B = 1 where a constraint ends;
+//          unordered (2): n = trie nodes, node 0 the root; A = the node's token, B = its parent, C = constraints that END at the node
+//          (terminal), D = constraints that end at or below it (num_constraints).  A node's children are found by scanning the <= 32
+//          nodes for (parent, token): the table sits in LDS wherever it is walked.
+//   state  [LEX_SW]: NODE (ordered: the index into A, -1 = root), BANK (constraint tokens generated), FIN, NNEXT and NEXT[16] (the
+//          state's next tokens, ascending and distinct — derived when the state is written, so the row kernel only reads them), NCOMP and,
+//          one byte per node, GEN (passes through the node) and COMP (constraints completed at it) of the unordered representation.
+// States live in a ping-pong pair [2][bsz * beam][LEX_SW] indexed by the step's parity like tokens / scores.
+constexpr int LEX_TOK_MAX = 32, LEX_NODES = LEX_TOK_MAX + 1, LEX_NEXT_MAX = 16, LEX_WIDTH_MAX = 1 + 2 * LEX_TOK_MAX;
+constexpr int LEX_TBL_W = 4 + 4 * LEX_NODES, LEX_SW = 44;
+constexpr int LEX_A = 4, LEX_B = LEX_A + LEX_NODES, LEX_C = LEX_B + LEX_NODES, LEX_D = LEX_C + LEX_NODES;
+constexpr int LS_NODE = 0, LS_BANK = 1, LS_FIN = 2, LS_NNEXT = 3, LS_NCOMP = 4, LS_NEXT = 8, LS_GEN = 24, LS_COMP = 33;
+static_assert(LS_NEXT + LEX_NEXT_MAX <= LS_GEN && LS_GEN * 4 + LEX_NODES <= LS_COMP * 4 && LS_COMP * 4 + LEX_NODES <= LEX_SW * 4, "state layout");
+constexpr int LEX_L_MAX = KMAX_ALL + BEAM_MAX + BEAM_MAX * LEX_NEXT_MAX;  // the candidate list of one sentence
+struct LexP {
+  const int32_t* tbl;   // [bsz][LEX_TBL_W]
+  int32_t* state;       // [2][bsz * beam][LEX_SW]; nullptr: no lexical constraints (the CON row kernels without them)
+  float* nval;          // [bsz * beam][LEX_NEXT_MAX]: the row kernel's values of the row's next tokens
+  int32_t* ntok;        // [bsz * beam][LEX_NEXT_MAX]
+};
+struct NoLex {};  // like NoEns
+template <bool LEX> using LexArg = std::conditional_t<LEX, LexP, NoLex>;
+
+// the node below `node` that token t leads to (unordered; 0 = none: the root is nobody's child)
+__device__ __forceinline__ int lex_child(const int32_t* tbl, int node, int t) {
+  int c = 0;
+  for (int q = 1; q < tbl[1]; ++q) c = (tbl[LEX_B + q] == node && tbl[LEX_A + q] == t) ? q : c;
+  return c;
+}
+// The bank of advance(st, t) (token_generation_constraints.py OrderedConstraintState.advance :463-506, UnorderedConstraintState.advance
+// :298-358).  out != nullptr: a copy of st that becomes the advanced state (NODE, BANK, NCOMP, GEN, COMP; lex_derive does the rest).
+// Ordered: finished -> stay; the next token -> on; at the end of a constraint -> stay (the ROOT reads the reference's endpoints[-1], the
+// last entry, always true: a token that does not start the constraints keeps the root); the first token of all -> state 0; else the root.
+// Unordered: the node's child by t if that edge is open (GEN < num_constraints of the child), else back to the root — onto the root's
+// child by t if open — and the path left behind is settled from the old node upwards: the first node with an unfinished terminal gets
+// one more COMP and the walk ends, every node before it loses one GEN.  All tests read the OLD state.
+__device__ __forceinline__ int lex_advance(const int32_t* tbl, const int32_t* st, int t, int32_t* out) {
+  const int n = tbl[1];
+  if (tbl[2] == 1) {
+    const int idx = st[LS_NODE];
+    int ni;
+    if (idx + 1 >= n) ni = idx;
+    else if (tbl[LEX_A + idx + 1] == t) ni = idx + 1;
+    else if (idx < 0 || tbl[LEX_B + idx] != 0) ni = idx;
+    else if (t == tbl[LEX_A]) ni = 0;
+    else ni = -1;
+    if (out) { out[LS_NODE] = ni; out[LS_BANK] = ni + 1; }
+    return ni + 1;
+  }
+  const uint8_t* gen = reinterpret_cast<const uint8_t*>(st + LS_GEN);
+  const uint8_t* comp = reinterpret_cast<const uint8_t*>(st + LS_COMP);
+  uint8_t* ogen = out ? reinterpret_cast<uint8_t*>(out + LS_GEN) : nullptr;
+  uint8_t* ocomp = out ? reinterpret_cast<uint8_t*>(out + LS_COMP) : nullptr;
+  const int node = st[LS_NODE];
+  int bank = st[LS_BANK];
+  int c = lex_child(tbl, node, t);
+  bool rewind = false;
+  if (!(c != 0 && (int)gen[c] < tbl[LEX_D + c])) {
+    c = lex_child(tbl, 0, t);
+    if (!(c != 0 && (int)gen[c] < tbl[LEX_D + c])) c = 0;
+    rewind = true;
+  }
+  if (c != 0) {
+    ++bank;
+    if (out) ogen[c] = (uint8_t)(gen[c] + 1);
+  }
+  if (out) out[LS_NODE] = c;
+  if (rewind) {
+    int q = node;
+    for (int hop = 0; hop < LEX_NODES && q > 0 && q < n; ++hop) {
+      if (tbl[LEX_C + q] != 0 && (int)comp[q] < tbl[LEX_C + q]) {
+        if (out) { ocomp[q] = (uint8_t)(comp[q] + 1); out[LS_NCOMP] = st[LS_NCOMP] + 1; }
+        break;
+      }
+      --bank;
+      if (out) ogen[q] = (uint8_t)(ogen[q] - 1);  // (ogen, not gen: q may be the node just entered)
+      q = tbl[LEX_B + q];
+    }
+  }
+  if (out) out[LS_BANK] = bank;
+  return bank;
+}
+// FIN, NNEXT and NEXT of a state whose other words are final (finished / next_tokens of the two state classes :271-296, :434-461).
+// Ordered: the first token of all once the state is PAST it (state > 0), and the token that advances.  Unordered: the root's children
+// and the node's.  Ascending, distinct, at most LEX_NEXT_MAX (the caller's host check keeps real lists below that).
+__device__ __forceinline__ void lex_derive(const int32_t* tbl, int32_t* st) {
+  const int n = tbl[1], node = st[LS_NODE];
+  int cnt = 0;
+  auto add = [&](int t) {
+    int pos = 0;
+    while (pos < cnt && st[LS_NEXT + pos] < t) ++pos;
+    if ((pos < cnt && st[LS_NEXT + pos] == t) || cnt == LEX_NEXT_MAX) return;
+    for (int q = cnt; q > pos; --q) st[LS_NEXT + q] = st[LS_NEXT + q - 1];
+    st[LS_NEXT + pos] = t;
+    ++cnt;
+  };
+  if (tbl[2] == 1) {
+    const bool fin = node + 1 >= n;
+    st[LS_FIN] = fin ? 1 : 0;
+    if (node > 0) add(tbl[LEX_A]);
+    if (!fin) add(tbl[LEX_A + node + 1]);
+  } else {
+    const uint8_t* comp = reinterpret_cast<const uint8_t*>(st + LS_COMP);
+    const int pending = (node > 0 && tbl[LEX_C + node] != 0 && (int)comp[node] < tbl[LEX_C + node]) ? 1 : 0;
+    st[LS_FIN] = (tbl[LEX_D] - (st[LS_NCOMP] + pending) == 0) ? 1 : 0;
+    for (int q = 1; q < n; ++q)
+      if (tbl[LEX_B + q] == 0 || tbl[LEX_B + q] == node) add(tbl[LEX_A + q]);
+  }
+  st[LS_NNEXT] = cnt;
+}
+
+// cst_lex_init: one workgroup per sentence turns its packed row [count, tokens of c0, 0, tokens of c1, 0, ...] into the table and sets
+// every row's state to the root in both halves of the ping-pong pair.  Tokens beyond LEX_TOK_MAX are not read (the host refuses them).
+__global__ __launch_bounds__(64) void lex_init_kernel(const int64_t* packed, int width, int rep, int beam, int bbsz, int32_t* tbl_out, int32_t* state) {
+  const int sent = blockIdx.x, tid = threadIdx.x;
+  __shared__ int row[LEX_WIDTH_MAX];
+  __shared__ int32_t tbl[LEX_TBL_W], st[LEX_SW];
+  for (int i = tid; i < LEX_WIDTH_MAX; i += blockDim.x) row[i] = i < width ? (int)packed[(int64_t)sent * width + i] : 0;
+  for (int i = tid; i < LEX_TBL_W; i += blockDim.x) tbl[i] = 0;
+  for (int i = tid; i < LEX_SW; i += blockDim.x) st[i] = 0;
+  __syncthreads();
+  if (tid == 0) {
+    const int W = width < LEX_WIDTH_MAX ? width : LEX_WIDTH_MAX;
+    int count = row[0] < 0 ? 0 : (row[0] > LEX_TOK_MAX ? LEX_TOK_MAX : row[0]);
+    int at = 1, n = rep == 1 ? 0 : 1, ntok = 0;
+    for (int c = 0; c < count && at < W; ++c) {
+      int node = 0, len = 0;
+      for (; at < W && row[at] != 0 && ntok < LEX_TOK_MAX; ++at, ++ntok, ++len) {
+        const int t = row[at];
+        if (rep == 1) {
+          tbl[LEX_A + n] = t;
+          tbl[LEX_B + n] = 0;
+          ++n;
+        } else {
+          tbl[1] = n;  // (lex_child scans the nodes made so far)
+          int ch = lex_child(tbl, node, t);
+          if (ch == 0) {
+            ch = n++;
+            tbl[LEX_A + ch] = t;
+            tbl[LEX_B + ch] = node;
+          }
+          node = ch;
+        }
+      }
+      if (len > 0) {
+        if (rep == 1) tbl[LEX_B + n - 1] = 1;
+        else {
+          tbl[LEX_C + node] += 1;
+          for (int q = node, hop = 0; hop < LEX_NODES; ++hop) {
+            tbl[LEX_D + q] += 1;
+            if (q == 0) break;
+            q = tbl[LEX_B + q];
+          }
+        }
+      }
+      while (at < W && row[at] != 0) ++at;  // (the unread tail of a constraint past the limit)
+      ++at;
+    }
+    tbl[1] = n;
+    tbl[2] = rep;
+    int nd = 0;
+    for (int i = rep == 1 ? 0 : 1; i < n; ++i) {
+      bool seen = false;
+      for (int j = rep == 1 ? 0 : 1; j < i; ++j) seen = seen || tbl[LEX_A + j] == tbl[LEX_A + i];
+      nd += seen ? 0 : 1;
+    }
+    tbl[0] = nd;
+    st[LS_NODE] = rep == 1 ? -1 : 0;
+    lex_derive(tbl, st);
+  }
+  __syncthreads();
+  for (int i = tid; i < LEX_TBL_W; i += blockDim.x) tbl_out[(int64_t)sent * LEX_TBL_W + i] = tbl[i];
+  for (int i = tid; i < 2 * beam * LEX_SW; i += blockDim.x) {
+    const int half = i / (beam * LEX_SW), r = i % (beam * LEX_SW);
+    state[((int64_t)half * bbsz + (int64_t)sent * beam) * LEX_SW + r] = st[r % LEX_SW];
+  }
+}
+
 // member n's copy of logits row hs (without ENS: the row itself)
 template <typename T, bool ENS>
 __device__ __forceinline__ const T* member_row(const BeamP& p, const EnsArg<ENS>& e, int n, int hs) {
@@ -225,6 +407,15 @@ __device__ __forceinline__ const int64_t* row_tokens(const BeamP& p, const RowCt
 __device__ __forceinline__ float row_prev_score(const BeamP& p, const RowCtx& c) {
   const int L1 = p.max_len + 1;
   return c.s > 0 ? (p.scores + (int64_t)(c.s & 1) * p.bsz * p.beam * L1)[(int64_t)c.hs * L1 + c.s - 1] : 0.0f;
+}
+
+// the row's lexical-constraint state at this step (nullptr without LEX: the kernels without CON, or a null state pointer)
+template <bool CON>
+__device__ __forceinline__ const int32_t* lex_row_state(const BeamP& p, const LexArg<CON>& lx, const RowCtx& c) {
+  if constexpr (CON) {
+    if (lx.state != nullptr) return lx.state + ((int64_t)(c.s & 1) * p.bsz * p.beam + c.h) * LEX_SW;
+  }
+  return nullptr;
 }
 
 // n-gram blocking (_no_repeat_ngram :734-767): with last = tk[s+2-n .. s], every i in [0, s+1-n] with tk[i .. i+n-2] == last bans token
@@ -507,7 +698,8 @@ __device__ __forceinline__ void beam_row_sample_tail(const BeamP& p, float (&x)[
 // stage (c); the selection is 2*beam wave-wide arg-max rounds in which only the winning thread rescans its registers (an earlier
 // version kept a sorted top-K list per thread for a whole sentence per workgroup: the divergent insertion chains made it 105 us per step).
 template <typename T, int NV, bool ENS, bool CON, bool SAMP, bool LM>
-__device__ __forceinline__ void beam_row_regs(const BeamP& p, const EnsArg<ENS>& e, const LmArg<LM>& lm, float* cand_val, int32_t* cand_tok) {
+__device__ __forceinline__ void beam_row_regs(const BeamP& p, const EnsArg<ENS>& e, const LmArg<LM>& lm, const LexArg<CON>& lx, float* cand_val,
+                                              int32_t* cand_tok) {
   constexpr int VEC = DT<T>::VEC, NTH = 512, NW = NTH / 64;
   RowCtx c;
   if (!row_prologue<CON>(p, c)) return;
@@ -618,6 +810,8 @@ __device__ __forceinline__ void beam_row_regs(const BeamP& p, const EnsArg<ENS>&
     lse = 0.0f;
   }
   const float prev = row_prev_score(p, c);
+  const int32_t* lex_st = lex_row_state<CON>(p, lx, c);  // the row's constraint state (nullptr: no lexical constraints)
+  const bool lex_no_eos = lex_st != nullptr && s > 0 && lex_st[LS_FIN] == 0;
   // candidate values replace the logits in the registers
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
@@ -628,6 +822,7 @@ __device__ __forceinline__ void beam_row_regs(const BeamP& p, const EnsArg<ENS>&
     for (int k = 0; k < VEC; ++k) {
       const int v = vi * VEC + k;
       float val = mask_lprob<CON>(p, c, v, x[i][k] - lse, [&](float) { return ((bw >> (v & 31)) & 1u) != 0u; });
+      if (lex_no_eos && v == p.eos) val = NEG;             // eos only once the constraints are met      (search.py:308-321)
       if constexpr (!SAMP) {
         if (s > 0) val += prev;                          // search.py:125
       }
@@ -637,6 +832,24 @@ __device__ __forceinline__ void beam_row_regs(const BeamP& p, const EnsArg<ENS>&
   if constexpr (SAMP) {  // x holds the masked log-probabilities WITHOUT the cumulative score: (c) is a draw, not a selection
     beam_row_sample_tail<NV, VEC>(p, x, s, h, prev, cand_val, cand_tok);
     return;
+  }
+  if constexpr (CON) {  // the values of the state's next tokens (search.py:398-410): the thread that holds the token writes it
+    if (lex_st != nullptr) {
+      const int nn = lex_st[LS_NNEXT] < LEX_NEXT_MAX ? lex_st[LS_NNEXT] : LEX_NEXT_MAX;
+      for (int j = 0; j < nn; ++j) {
+        const int t = lex_st[LS_NEXT + j];
+        const bool inside = t >= 0 && t < V;
+        const int vi = inside ? t / VEC : 0;
+        if (tid != (inside ? vi % NTH : 0)) continue;
+        float val = NEG;
+#pragma unroll
+        for (int i = 0; i < NV; ++i)
+#pragma unroll
+          for (int k = 0; k < VEC; ++k) val = (inside && i == vi / NTH && k == t % VEC) ? x[i][k] : val;
+        lx.nval[(int64_t)h * LEX_NEXT_MAX + j] = val;
+        lx.ntok[(int64_t)h * LEX_NEXT_MAX + j] = t;
+      }
+    }
   }
   // local best that is strictly worse than (tv, ti) — the thread's previously taken candidate
   float tv = INFINITY, bv;
@@ -728,7 +941,8 @@ __device__ __forceinline__ void beam_row_regs(const BeamP& p, const EnsArg<ENS>&
 // The generic-width body: rows too long for registers are re-read from memory (L2-resident) on every scan; with ENS every scan
 // recombines the N rows element by element, with CON every scan consults the ban filter.  It only selects.
 template <typename T, bool ENS, bool CON, bool LM>
-__device__ __forceinline__ void beam_row_wide(const BeamP& p, const EnsArg<ENS>& e, const LmArg<LM>& lm, float* cand_val, int32_t* cand_tok) {
+__device__ __forceinline__ void beam_row_wide(const BeamP& p, const EnsArg<ENS>& e, const LmArg<LM>& lm, const LexArg<CON>& lx, float* cand_val,
+                                              int32_t* cand_tok) {
   constexpr int NTH = 512, NW = NTH / 64, BANW = 256;
   RowCtx c;
   if (!row_prologue<CON>(p, c)) return;
@@ -808,14 +1022,34 @@ __device__ __forceinline__ void beam_row_wide(const BeamP& p, const EnsArg<ENS>&
       for (int v = tid; v < V; v += NTH) lm.lprobs_out[(int64_t)h * p.ld_logits + v] = lprob(v);
   }
   const float prev = row_prev_score(p, c);
+  const int32_t* lex_st = lex_row_state<CON>(p, lx, c);  // the row's constraint state (nullptr: no lexical constraints)
+  const bool lex_no_eos = lex_st != nullptr && s > 0 && lex_st[LS_FIN] == 0;
+  // the candidate value of token v
+  auto value = [&](int v) -> float {
+    float val = mask_lprob<CON>(p, c, v, lprob(v), [&](float cur) { return cur != NEG && banned(v); });
+    if (lex_no_eos && v == p.eos) val = NEG;  // eos only once the constraints are met (search.py:308-321)
+    if (s > 0) val += prev;                   // search.py:125
+    return val;
+  };
+  if constexpr (CON) {  // the values of the state's next tokens (search.py:398-410), by the thread whose share of the row holds the token
+    if (lex_st != nullptr) {
+      const int nn = lex_st[LS_NNEXT] < LEX_NEXT_MAX ? lex_st[LS_NNEXT] : LEX_NEXT_MAX;
+      for (int j = 0; j < nn; ++j) {
+        const int t = lex_st[LS_NEXT + j];
+        const bool inside = t >= 0 && t < V;
+        if (tid != (inside ? t % NTH : 0)) continue;
+        lx.nval[(int64_t)h * LEX_NEXT_MAX + j] = inside ? value(t) : NEG;
+        lx.ntok[(int64_t)h * LEX_NEXT_MAX + j] = t;
+      }
+    }
+  }
   // local best that is strictly worse than (tv, ti) — the thread's previously taken candidate
   float tv = INFINITY, bv;
   int ti = -1, bi;
   auto rescan = [&]() {
     bv = NEG; bi = INT_MAX;
     for (int v = tid; v < V; v += NTH) {
-      float val = mask_lprob<CON>(p, c, v, lprob(v), [&](float cur) { return cur != NEG && banned(v); });
-      if (s > 0) val += prev;  // search.py:125
+      const float val = value(v);
       const bool open = val < tv || (val == tv && v > ti);
       if (open && cand_better(val, v, bv, bi)) { bv = val; bi = v; }
     }
@@ -842,10 +1076,10 @@ __device__ __forceinline__ void beam_row_wide(const BeamP& p, const EnsArg<ENS>&
 
 // NV vectors per thread in registers; NV == 0: the wide body
 template <typename T, int NV, bool ENS, bool CON, bool SAMP, bool LM>
-__global__ __launch_bounds__(512) void beam_row_kernel(BeamP p, float* cand_val, int32_t* cand_tok, EnsArg<ENS> e, LmArg<LM> lm) {
+__global__ __launch_bounds__(512) void beam_row_kernel(BeamP p, float* cand_val, int32_t* cand_tok, EnsArg<ENS> e, LmArg<LM> lm, LexArg<CON> lx) {
   static_assert(NV > 0 || !SAMP, "the wide body only selects");
-  if constexpr (NV == 0) beam_row_wide<T, ENS, CON, LM>(p, e, lm, cand_val, cand_tok);
-  else beam_row_regs<T, NV, ENS, CON, SAMP, LM>(p, e, lm, cand_val, cand_tok);
+  if constexpr (NV == 0) beam_row_wide<T, ENS, CON, LM>(p, e, lm, lx, cand_val, cand_tok);
+  else beam_row_regs<T, NV, ENS, CON, SAMP, LM>(p, e, lm, lx, cand_val, cand_tok);
 }
 
 // ---- beam search step, kernel 2 of 2: one workgroup per SENTENCE -------------------------------------------------------------
@@ -877,8 +1111,23 @@ __global__ __launch_bounds__(512) void beam_row_kernel(BeamP p, float* cand_val,
 // DIV = 2 (diverse siblings, search.py DiverseSiblingsSearch.step :765-814): at steps s > 0 the candidate at position p (from 0) of a
 // row's sorted list has the value fl(v - fl((p + 1) * R)), formed where the lists are staged; the lists stay sorted, so the rank loop
 // and its tie rule (smaller row * 2*beam + p) are the plain ones.  Step 0 is plain beam search.
+// DIV = 3 (lexical constraints, search.py LexicallyConstrainedBeamSearch.step / step_sentence :263-523; the tables and states are
+// described at LexP above).  After the plain selection, which yields the sentence's top 2*beam, the list L is staged in LDS:
+//   (1) that top 2*beam; at steps s > 0 every row's own best candidate (the head of its sorted list) in row order; then per row in row
+//       order (only the first row at s = 0) one candidate per next token of the row's state in ascending token order, with the value the
+//       row kernel left in LexP::nval — formed by the same operations as a list entry, so a duplicate is bit-equal to its twin;
+//   (2) one thread per candidate advances its PARENT's state by the candidate's token (lex_advance, nothing stored) for the bank, and
+//       forms the fp32 key  fl(float((nd - bank) * -100) + value);
+//   (3) rank by counting: key descending, stable with respect to L (the order IS that of the fp32 key, as the reference's sort_key);
+//   (4) a candidate whose predecessor in that order — cyclically, the first looks at the last — has the same (parent, token) is dropped;
+//   (5) the j-th survivor of a run of equal banks gets the stripe nd - bank + j * (survivors + 1); a second rank by counting, stripe
+//       ascending and stable, and the first 2*beam are the sentence's candidates (score = value, token, parent).
+// (d) and (e) then run over those; after them thread i < beam re-advances the parent state of candidate act[i] into a staging row,
+// derives its FIN / NEXT words, and the workgroup copies the rows into the other half of the state pair (update_constraints :254-260).
 template <bool PFX, bool SAMP = false, int DIV = 0>
-__global__ __launch_bounds__(256) void beam_merge_kernel(BeamP p, const float* cand_val, const int32_t* cand_tok, int32_t* ticket) {
+__global__ __launch_bounds__(256) void beam_merge_kernel(BeamP p, const float* cand_val, const int32_t* cand_tok, int32_t* ticket,
+                                                         LexArg<DIV == 3> lx) {
+  constexpr bool LEX = DIV == 3;
   const int s = *p.step;
   const int sent = blockIdx.x, tid = threadIdx.x;
   const int beam = p.beam, K = SAMP ? beam : 2 * beam, bbsz = p.bsz * beam;
@@ -898,6 +1147,7 @@ __global__ __launch_bounds__(256) void beam_merge_kernel(BeamP p, const float* c
   __shared__ int c_tok[KMAX_ALL], c_beam[KMAX_ALL], c_em[KMAX_ALL];
   __shared__ int act[BEAM_MAX], rec_k[BEAM_MAX], rec_r[BEAM_MAX], n_rec;
   __shared__ int ign[BEAM_MAX], ign_new[BEAM_MAX];
+  __shared__ int32_t x_tbl[LEX ? LEX_TBL_W : 1], x_st[LEX ? BEAM_MAX * LEX_SW : 1], x_new[LEX ? BEAM_MAX * LEX_SW : 1];
   bool first_row_parent = false;
   if constexpr (PFX) first_row_parent = prefix_step(p, s) && p.prefix_tokens[(int64_t)sent * p.prefix_len + s] == p.eos;
   if (s <= p.max_len) {
@@ -967,6 +1217,84 @@ __global__ __launch_bounds__(256) void beam_merge_kernel(BeamP p, const float* c
       if (rank < K) { c_score[rank] = v; c_tok[rank] = l_tok[i]; c_beam[rank] = first_row_parent ? 0 : r; }
     }
     __syncthreads();
+    if constexpr (LEX) {
+      __shared__ float L_val[LEX_L_MAX], L_key[LEX_L_MAX];
+      __shared__ int L_tok[LEX_L_MAX], L_par[LEX_L_MAX], L_bank[LEX_L_MAX];
+      __shared__ int L_ord[LEX_L_MAX], L_keep[LEX_L_MAX], L_stripe[LEX_L_MAX];  // by position in the key order
+      __shared__ int L_off[BEAM_MAX + 1];
+      const int nthr = blockDim.x;
+      for (int i = tid; i < LEX_TBL_W; i += nthr) x_tbl[i] = lx.tbl[(int64_t)sent * LEX_TBL_W + i];
+      for (int i = tid; i < beam * LEX_SW; i += nthr) x_st[i] = lx.state[((int64_t)cur * bbsz + (int64_t)sent * beam) * LEX_SW + i];
+      __syncthreads();
+      if (tid == 0) {  // where each row's next-token candidates start in L
+        int at = K + (s > 0 ? beam : 0);
+        for (int r = 0; r < rows; ++r) {
+          L_off[r] = at;
+          const int nn = x_st[r * LEX_SW + LS_NNEXT];
+          at += nn < 0 ? 0 : (nn < LEX_NEXT_MAX ? nn : LEX_NEXT_MAX);
+        }
+        L_off[rows] = at;
+      }
+      __syncthreads();
+      const int nL = L_off[rows], nd = x_tbl[0];
+      for (int i = tid; i < nL; i += nthr) {  // (1), (2)
+        float v;
+        int t, par;
+        if (i < K) { v = c_score[i]; t = c_tok[i]; par = c_beam[i]; }
+        else if (i < L_off[0]) { par = i - K; v = l_val[par * K]; t = l_tok[par * K]; }
+        else {
+          par = 0;
+          while (par + 1 < rows && i >= L_off[par + 1]) ++par;
+          const int j = i - L_off[par];
+          v = lx.nval[((int64_t)sent * beam + par) * LEX_NEXT_MAX + j];
+          t = x_st[par * LEX_SW + LS_NEXT + j];
+        }
+        const int bank = lex_advance(x_tbl, x_st + par * LEX_SW, t, nullptr);
+        L_val[i] = v; L_tok[i] = t; L_par[i] = par; L_bank[i] = bank;
+        L_key[i] = __fadd_rn((float)((nd - bank) * -100), v);
+      }
+      __syncthreads();
+      for (int i = tid; i < nL; i += nthr) {  // (3)
+        const float key = L_key[i];
+        int rank = 0;
+        for (int o = 0; o < nL; ++o) {
+          const float ko = L_key[o];
+          rank += (ko > key || (ko == key && o < i)) ? 1 : 0;
+        }
+        L_ord[rank] = i;
+      }
+      if (tid < K) { c_score[tid] = NEG; c_tok[tid] = p.pad; c_beam[tid] = 0; }  // (never left: L holds 2*beam distinct pairs)
+      __syncthreads();
+      for (int q = tid; q < nL; q += nthr) {  // (4)
+        const int i = L_ord[q], o = L_ord[q == 0 ? nL - 1 : q - 1];
+        L_keep[q] = (L_par[i] == L_par[o] && L_tok[i] == L_tok[o]) ? 0 : 1;
+      }
+      __syncthreads();
+      for (int q = tid; q < nL; q += nthr) {  // (5): stripes
+        int len = 0;
+        for (int o = 0; o < nL; ++o) len += L_keep[o];
+        const int bank = L_bank[L_ord[q]];
+        int j = 0;
+        for (int o = q - 1; o >= 0; --o) {
+          if (!L_keep[o]) continue;
+          if (L_bank[L_ord[o]] != bank) break;
+          ++j;
+        }
+        L_stripe[q] = L_keep[q] ? nd - bank + j * (len + 1) : INT_MAX;
+      }
+      __syncthreads();
+      for (int q = tid; q < nL; q += nthr) {  // (5): the first 2*beam by stripe
+        if (!L_keep[q]) continue;
+        const int st = L_stripe[q];
+        int rank = 0;
+        for (int o = 0; o < nL; ++o) rank += (L_keep[o] && (L_stripe[o] < st || (L_stripe[o] == st && o < q))) ? 1 : 0;
+        if (rank < K) {
+          const int i = L_ord[q];
+          c_score[rank] = L_val[i]; c_tok[rank] = L_tok[i]; c_beam[rank] = L_par[i];
+        }
+      }
+      __syncthreads();
+    }
     }
     }
     if (tid == 0) {
@@ -1038,6 +1366,19 @@ __global__ __launch_bounds__(256) void beam_merge_kernel(BeamP p, const float* c
         sc_new[dst * L1 + s] = c_score[k];
         anc_new[dst * L1 + s + 1] = (int32_t)dst;
       }
+      if constexpr (LEX) {  // next row i takes the advanced state of its candidate
+        if (tid < beam) {
+          const int k = act[tid];
+          const int32_t* from = x_st + c_beam[k] * LEX_SW;
+          int32_t* to = x_new + tid * LEX_SW;
+          for (int w = 0; w < LEX_SW; ++w) to[w] = from[w];
+          lex_advance(x_tbl, from, c_tok[k], to);
+          lex_derive(x_tbl, to);
+        }
+        __syncthreads();
+        for (int i = tid; i < beam * LEX_SW; i += blockDim.x)
+          lx.state[((int64_t)nxt * bbsz + (int64_t)sent * beam) * LEX_SW + i] = x_new[i];
+      }
     }
   }
   // the last workgroup to get here advances the step (every workgroup has read *p.step by now)
@@ -1091,9 +1432,54 @@ void dispatch(F&& f, Choice<C0, Cs...> c, Rest... rest) {
   else dispatch(f, Choice<Cs...>{c.i - 1}, rest...);
 }
 
+// what cst_lex_init and cst_beam_step_lex refuse alike; on CST_OK the workspace's four parts are in lp
+int lex_params(const cst_beam_desc* d, const cst_lex_desc* x, LexP& lp) {
+  CST_REQUIRE(x->representation == 1 || x->representation == 2, "cst_lex: representation %lld (1 ordered, 2 unordered)", (long long)x->representation);
+  CST_REQUIRE(x->workspace != nullptr && ((uintptr_t)x->workspace % 16) == 0, "cst_lex: workspace of cst_lex_workspace() bytes required, 16-byte aligned");
+  CST_REQUIRE(x->width >= 1, "cst_lex: width %lld (a packed row holds at least its count)", (long long)x->width);
+  if (x->width > LEX_WIDTH_MAX) {
+    cst_set_error("cst_lex: a packed row of width %lld holds more than %d constraint tokens: decode such sentences with the host loop",
+                  (long long)x->width, LEX_TOK_MAX);
+    return CST_ERR_UNSUPPORTED;
+  }
+  CST_REQUIRE(d->sampling == 0 && d->diverse_groups == 0 && d->diverse_siblings == 0,
+              "cst_lex: sampling, the diverse strategies and lexical constraints are mutually exclusive search strategies");
+  CST_REQUIRE(d->prefix_len == 0, "cst_lex: lexical constraints cannot be combined with forced prefixes (prefix_len %lld)", (long long)d->prefix_len);
+  const int64_t rows = d->bsz * d->beam;
+  int32_t* w = reinterpret_cast<int32_t*>(x->workspace);
+  lp.tbl = w;
+  lp.state = w + d->bsz * LEX_TBL_W;
+  lp.nval = reinterpret_cast<float*>(lp.state + 2 * rows * LEX_SW);
+  lp.ntok = reinterpret_cast<int32_t*>(lp.nval + rows * LEX_NEXT_MAX);
+  return CST_OK;
+}
+
+int beam_step_impl(const cst_beam_desc* d, const cst_lm_fusion_desc* f, const cst_lex_desc* x, cst_stream stream);
+
 }  // namespace
 
 extern "C" {
+int64_t cst_lex_workspace(int64_t bsz, int64_t beam, int64_t width) {
+  // per sentence its table; per row two states and LEX_NEXT_MAX (value, token) next-token candidates.  (width: the packed rows are read
+  // in place, the tables have one size)
+  (void)width;
+  return (bsz * LEX_TBL_W + bsz * beam * (2 * LEX_SW + 2 * LEX_NEXT_MAX)) * (int64_t)sizeof(int32_t);
+}
+
+int cst_lex_init(const cst_beam_desc* d, const cst_lex_desc* x, cst_stream stream) {
+  BeamP p;
+  const int rc = to_params(d, p);
+  if (rc != CST_OK) return rc;
+  CST_REQUIRE(x != nullptr, "cst_lex_init: null descriptor");
+  LexP lp;
+  const int rx = lex_params(d, x, lp);
+  if (rx != CST_OK) return rx;
+  CST_REQUIRE(x->constraints != nullptr, "cst_lex_init: null constraints");
+  hipLaunchKernelGGL(lex_init_kernel, dim3(p.bsz), dim3(64), 0, (hipStream_t)stream, x->constraints, (int)x->width, (int)x->representation, p.beam,
+                     p.bsz * p.beam, const_cast<int32_t*>(lp.tbl), lp.state);
+  return cst_check_launch("cst_lex_init");
+}
+
 int cst_beam_init(const cst_beam_desc* d, cst_stream stream) {
   BeamP p;
   const int rc = to_params(d, p);
@@ -1109,9 +1495,16 @@ int64_t cst_beam_workspace(int64_t bsz, int64_t beam) {
   return bsz * beam * 2 * beam * (int64_t)(sizeof(float) + sizeof(int32_t)) + 64;
 }
 
-int cst_beam_step(const cst_beam_desc* d, cst_stream stream) { return cst_beam_step_lm(d, nullptr, stream); }
+int cst_beam_step(const cst_beam_desc* d, cst_stream stream) { return beam_step_impl(d, nullptr, nullptr, stream); }
+int cst_beam_step_lm(const cst_beam_desc* d, const cst_lm_fusion_desc* f, cst_stream stream) { return beam_step_impl(d, f, nullptr, stream); }
+int cst_beam_step_lex(const cst_beam_desc* d, const cst_lm_fusion_desc* f, const cst_lex_desc* x, cst_stream stream) {
+  return beam_step_impl(d, f, x, stream);
+}
 
-int cst_beam_step_lm(const cst_beam_desc* d, const cst_lm_fusion_desc* f, cst_stream stream) {
+}  // extern "C"
+
+namespace {
+int beam_step_impl(const cst_beam_desc* d, const cst_lm_fusion_desc* f, const cst_lex_desc* x, cst_stream stream) {
   BeamP p;
   const int rc = to_params(d, p);
   if (rc != CST_OK) return rc;
@@ -1187,6 +1580,13 @@ int cst_beam_step_lm(const cst_beam_desc* d, const cst_lm_fusion_desc* f, cst_st
     CST_REQUIRE(f->lprobs_out == nullptr || ((uintptr_t)f->lprobs_out % 16) == 0, "cst_beam_step_lm: lprobs_out must be 16-byte aligned");
     lmp.logits = f->lm_logits; lmp.weight = f->lm_weight; lmp.lprobs_out = f->lprobs_out;
   }
+  // lexical constraints (an entry point of its own, added at ABI 13 like the LM's): off without x -> the kernels and arguments above
+  const bool lex = x != nullptr;
+  LexP lexp{nullptr, nullptr, nullptr, nullptr};
+  if (lex) {
+    const int rx = lex_params(d, x, lexp);
+    if (rx != CST_OK) return rx;
+  }
   hipStream_t s = (hipStream_t)stream;
   const int64_t rows = (int64_t)p.bsz * p.beam, K = 2 * p.beam;
   int32_t* ticket = reinterpret_cast<int32_t*>(d->workspace);
@@ -1208,21 +1608,27 @@ int cst_beam_step_lm(const cst_beam_desc* d, const cst_lm_fusion_desc* f, cst_st
             if constexpr (ENS) ea = e;
             LmArg<LM> la{};
             if constexpr (LM) la = lmp;
-            hipLaunchKernelGGL((beam_row_kernel<T, NV, ENS, CON, SAMP, LM>), dim3((unsigned)rows), dim3(512), 0, s, p, cand_val, cand_tok, ea, la);
+            LexArg<CON> xa{};
+            if constexpr (CON) xa = lexp;  // (a null state pointer without lexical constraints)
+            hipLaunchKernelGGL((beam_row_kernel<T, NV, ENS, CON, SAMP, LM>), dim3((unsigned)rows), dim3(512), 0, s, p, cand_val, cand_tok, ea, la, xa);
           }
         },
-        Choice<Type<float>, Type<bf16_t>>{d->dtype == CST_BF16}, Choice<Int<1>, Int<3>, Int<5>, Int<0>>{bucket}, Bool{ens}, Bool{con}, Bool{samp},
+        Choice<Type<float>, Type<bf16_t>>{d->dtype == CST_BF16}, Choice<Int<1>, Int<3>, Int<5>, Int<0>>{bucket}, Bool{ens}, Bool{con || lex}, Bool{samp},
         Bool{lmf});
     dispatch(
         [&](auto pfx_c, auto samp_c, auto div_c) {
           constexpr bool PFX = decltype(pfx_c)::value, SAMP = decltype(samp_c)::value;
           constexpr int DIV = decltype(div_c)::value;
-          if constexpr (!SAMP || DIV == 0)  // (exclusive strategies, checked above)
-            hipLaunchKernelGGL((beam_merge_kernel<PFX, SAMP, DIV>), dim3(p.bsz), dim3(256), 0, s, p, (const float*)cand_val, (const int32_t*)cand_tok, ticket);
+          if constexpr ((!SAMP || DIV == 0) && !(DIV == 3 && PFX)) {  // (exclusive strategies, checked above; no prefix with lexical constraints)
+            LexArg<DIV == 3> xa{};
+            if constexpr (DIV == 3) xa = lexp;
+            hipLaunchKernelGGL((beam_merge_kernel<PFX, SAMP, DIV>), dim3(p.bsz), dim3(256), 0, s, p, (const float*)cand_val, (const int32_t*)cand_tok,
+                               ticket, xa);
+          }
         },
-        Bool{p.prefix_len > 0}, Bool{samp}, Choice<Int<0>, Int<1>, Int<2>>{groups ? 1 : siblings ? 2 : 0});
+        Bool{p.prefix_len > 0}, Bool{samp}, Choice<Int<0>, Int<1>, Int<2>, Int<3>>{groups ? 1 : siblings ? 2 : lex ? 3 : 0});
   }
-  return cst_check_launch(lmf ? "cst_beam_step_lm" : "cst_beam_step");
+  return cst_check_launch(lex ? "cst_beam_step_lex" : lmf ? "cst_beam_step_lm" : "cst_beam_step");
 }
 
-}  // extern "C"
+}  // namespace

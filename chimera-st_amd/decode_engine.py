@@ -116,7 +116,7 @@ class StepPlan(NamedTuple):
 
 
 class BeamDecodeEngine:
-    def __init__(self, decoders, tgt_dict, options, lm_decoder=None, use_graph=True, poll=8, cross_kernel=None, lanes=None):
+    def __init__(self, decoders, tgt_dict, options, lm_decoder=None, use_graph=True, poll=8, cross_kernel=None, lanes=None, lexical=None):
         # `decoders`: the list of models of a checkpoint ensemble (--path a.pt:b.pt:c.pt; one model is a list of one).  A language model
         # (shallow fusion, --lm-path / --lm-weight, sequence_generator.py:318-324) is one more decoder of the step: a decoder WITHOUT
         # cross attention (lm_supported) whose log-softmax cst_beam_step_lm adds, x lm_weight, to the models' combined log-probabilities.
@@ -127,7 +127,14 @@ class BeamDecodeEngine:
         # INVARIANT: packed weights, states and member dicts hold no reference to the engine, to their state or to each other — no
         # cycles, so a dropped state is freed by reference counting at once and not by the cyclic collector, which could otherwise run
         # inside a later graph capture.
+        # `lexical`: None | "ordered" | "unordered" — the representation of the lexical constraints a generate() call may bring
+        # (sequence_generator.LexicallyConstrainedBeamSearch; cst_lex_init / cst_beam_step_lex).  A call without constraints runs the
+        # engine as if it were None.
         self.opt = options
+        assert lexical in (None, "ordered", "unordered"), lexical
+        assert lexical is None or not (options.sampling or options.diverse_groups > 0 or options.sibling_rate is not None), \
+            "sampling, the diverse strategies and lexical constraints are mutually exclusive search strategies"
+        self.lexical = lexical
         self.decs, self.lm = list(decoders), lm_decoder
         assert 1 <= len(self.decs) <= 8, "cst_beam_step combines at most 8 ensemble members"
         assert self.lm is None or self.lm_supported(self.lm), "the language model's decoder is outside lm_supported()"
@@ -190,6 +197,14 @@ class BeamDecodeEngine:
         10240 in fp32).  Beyond that it returns CST_ERR_UNSUPPORTED, so the generator takes the host loop up front."""
         vec = 8 if dtype == torch.bfloat16 else 4
         return -(-(-(-int(vocab) // vec)) // 512) <= 5
+
+    @staticmethod
+    def lexical_supported(packed, beam):
+        """cst_lex_init holds at most 32 constraint tokens per sentence and lists at most 16 next tokens per state; beyond that, or
+        with packed rows wider than 32 one-token constraints need (65), cst_lex_init returns CST_ERR_UNSUPPORTED, so the generator takes the host loop up
+        front.  packed: the int64 [bsz, W] tensor of lexical_constraints.pack_constraints."""
+        from . import lexical_constraints as LC
+        return beam <= 20 and int(packed.shape[1]) <= L.LEX_WIDTH_MAX and LC.device_limits_ok(packed)
 
     def invalidate(self):
         """Drop the packed / folded weight copies and the captured graphs (call after changing decoder weights by any other route)."""
@@ -292,11 +307,13 @@ class BeamDecodeEngine:
                      vx=[z(bsz, S, C) for _ in range(nl)], proj=z(bsz * S, C), kpm=z(bsz, S, dt=torch.uint8) if has_mask else None)
         return m
 
-    def _alloc(self, lane, bsz, S, dtype, device, has_mask, prefix_len=0):
+    def _alloc(self, lane, bsz, S, dtype, device, has_mask, prefix_len=0, lex=None):
         """S / has_mask: one value per model (models may differ in encoder output length).  prefix_len and the options are kernel
         parameters baked into the captured graph, so they are part of the state key; the prefix TOKENS and the sampling key live in
         buffers the state owns (st["prefix"], st["sample_key"]), which every call overwrites: a replayed graph reads the new call's."""
-        key = (lane, bsz, S, dtype, device, has_mask, prefix_len, self.opt)
+        # lex: None or (representation, width of the packed constraints) — the step then is cst_beam_step_lex over a workspace and a
+        # constraint buffer of the lane's own (st["lex_packed"], refilled by every call like st["prefix"]).
+        key = (lane, bsz, S, dtype, device, has_mask, prefix_len, self.opt, lex)
         st = self._state.get(key)
         if st is not None:
             return st
@@ -337,6 +354,15 @@ class BeamDecodeEngine:
         if self.opt.sampling:
             d.sample_key = st["sample_key"].data_ptr()
         st["desc"] = d
+        st["lex_desc"] = None
+        if lex is not None:
+            from .lexical_constraints import REPRESENTATIONS
+            x = L.LexDesc()
+            st["lex_packed"] = torch.zeros(bsz, lex[1], dtype=torch.int64, device=device)
+            st["lex_ws"] = torch.zeros(L.load().cst_lex_workspace(bsz, beam, lex[1]), dtype=torch.uint8, device=device)
+            x.representation, x.width = REPRESENTATIONS[lex[0]], lex[1]
+            x.constraints, x.workspace = st["lex_packed"].data_ptr(), st["lex_ws"].data_ptr()
+            st["lex_desc"] = x
         self._state[key] = st
         return st
 
@@ -365,7 +391,10 @@ class BeamDecodeEngine:
         step reads all their logits."""
         for dec, m, mpk in zip(self.members, st["members"], pk):
             self._step_member(dec, st, m, mpk, bsz)
-        if self.lm is None:
+        if st["lex_desc"] is not None:
+            f = None if self.lm is None else ctypes.byref(st["lm_desc"])
+            L.check(L.load().cst_beam_step_lex(ctypes.byref(st["desc"]), f, ctypes.byref(st["lex_desc"]), L.stream_ptr()), "cst_beam_step_lex")
+        elif self.lm is None:
             L.check(L.load().cst_beam_step(ctypes.byref(st["desc"]), L.stream_ptr()), "cst_beam_step")
         else:
             L.check(L.load().cst_beam_step_lm(ctypes.byref(st["desc"]), ctypes.byref(st["lm_desc"]), L.stream_ptr()), "cst_beam_step_lm")
@@ -449,17 +478,26 @@ class BeamDecodeEngine:
 
     # ------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def generate(self, encoder_outs, bsz, prefix_tokens=None, sample_key=0):
+    def generate(self, encoder_outs, bsz, prefix_tokens=None, sample_key=0, constraints=None):
         """encoder_outs: one EncoderOut per model, each with encoder_out [S, B, C] (T x B x C view) and encoder_padding_mask [B, S] or
         None (each model's own encoder; lengths S and widths may differ).
         prefix_tokens: None or int64 [bsz, K] padded with pad, K <= max_len: the tokens forced at the first K steps (--prefix-size);
         it is copied into the engine's own buffer (the caller's tensor is never captured).
         sample_key: the 32-bit key of this call's draws (sampling only), written into the state's buffer before the first step: the
         captured step graph reads it there, so a replay draws with the key of the call that replays it.
+        constraints: None or the packed lexical constraints int64 [bsz, W] (lexical_constraints.pack_constraints) of an engine built
+        with lexical=...; each lane copies its sentences' rows into its own buffer and cst_lex_init rebuilds tables and root states.  A
+        sentence whose constraints are not met within max_len finalises nothing: RuntimeError.
         Returns the reference's `finalized` structure (list over sentences of hypothesis dicts, best first)."""
         prefix_len = 0 if prefix_tokens is None else int(prefix_tokens.shape[1])
         assert prefix_tokens is None or (prefix_tokens.dim() == 2 and prefix_tokens.shape[0] == bsz and prefix_len <= self.opt.max_len)
         assert len(encoder_outs) == len(self.decs), "one encoder output per ensemble member"
+        lex = None
+        if constraints is not None:
+            assert self.lexical is not None, "constraints need an engine built with lexical=\"ordered\" | \"unordered\""
+            assert prefix_len == 0, "lexical constraints cannot be combined with prefix_tokens"
+            assert constraints.dim() == 2 and constraints.shape[0] == bsz and self.lexical_supported(constraints, self.opt.beam)
+            lex = (self.lexical, int(constraints.shape[1]))
         encs = [e.encoder_out for e in encoder_outs]
         assert all(e.shape[1] == bsz for e in encs)
         dtype, device = encs[0].dtype, encs[0].device
@@ -470,7 +508,7 @@ class BeamDecodeEngine:
         pk = self._pack(dtype, device)
         lanes = min(self.lanes, bsz)
         bounds = [(bsz * i // lanes, bsz * (i + 1) // lanes) for i in range(lanes)]
-        cfg = (tuple(b1 - b0 for b0, b1 in bounds), S, dtype, device, has_mask, prefix_len)
+        cfg = (tuple(b1 - b0 for b0, b1 in bounds), S, dtype, device, has_mask, prefix_len, lex)
         if cfg != self._cfg:
             self._state.clear()  # one resident configuration (the caches are the large buffers)
             self._cfg = cfg
@@ -486,7 +524,9 @@ class BeamDecodeEngine:
             if stream is not main:
                 stream.wait_stream(main)
             with torch.cuda.stream(stream):
-                st = self._alloc(i, b1 - b0, S, dtype, device, has_mask, prefix_len)
+                st = self._alloc(i, b1 - b0, S, dtype, device, has_mask, prefix_len, lex)
+                if lex is not None:  # the lane's sentences' constraints, into the buffer cst_lex_init reads (in _begin)
+                    st["lex_packed"].copy_(constraints[b0:b1].to(device=device, dtype=torch.int64))
                 if prefix_len > 0:  # the lane's sentences' prefixes, into the buffer the (captured) beam step reads
                     st["prefix"].copy_(prefix_tokens[b0:b1].to(device=device, dtype=torch.int64))
                 if self.opt.sampling:
@@ -510,13 +550,18 @@ class BeamDecodeEngine:
                     r["steps"] += r["n"]
                     with torch.cuda.stream(r["stream"]):
                         r["remaining"] = int(r["st"]["num_remaining"].item())  # the only host sync of the loop (one per lane)
-        assert all(r["remaining"] == 0 for r in runs), "beam search did not terminate within max_len + 1 steps"
+        # (with lexical constraints a sentence that could not meet them is still "remaining": _collect names it)
+        assert lex is not None or all(r["remaining"] == 0 for r in runs), "beam search did not terminate within max_len + 1 steps"
         finalized = []
         for r in runs:
             with torch.cuda.stream(r["stream"]):
                 finalized += self._collect(r["st"], r["bsz"], None if r["stream"] is main else main)
             if r["stream"] is not main:
                 main.wait_stream(r["stream"])
+        if lex is not None:
+            unmet = [b for b, hyps in enumerate(finalized) if not hyps]
+            if unmet:
+                raise RuntimeError("lexical constraints not met within max_len: sentences %s" % unmet)
         return finalized
 
     def _begin_member(self, dec, m, encb, mask, bsz):
@@ -543,6 +588,8 @@ class BeamDecodeEngine:
         for dec, m, e, mk in zip(self.decs, st["members"], encb, mask):  # (the LM, last of the members, has no encoder: zip stops before it)
             self._begin_member(dec, m, e, mk, bsz)
         L.check(L.load().cst_beam_init(ctypes.byref(st["desc"]), L.stream_ptr()), "cst_beam_init")
+        if st["lex_desc"] is not None:  # tables and root states from the call's constraints (outside the captured step)
+            L.check(L.load().cst_lex_init(ctypes.byref(st["desc"]), ctypes.byref(st["lex_desc"]), L.stream_ptr()), "cst_lex_init")
         if self.use_graph and st["graph"] is None:
             self._step(st, pk, bsz)  # eager warm-up step 0 (loads code objects, sizes the GEMM workspace)
             torch.cuda.synchronize()

@@ -102,6 +102,21 @@ class LmFusionDesc(ctypes.Structure):
     _fields_ = [("lm_logits", c_p), ("lm_weight", c_f), ("lprobs_out", c_p)]
 
 
+class LexDesc(ctypes.Structure):
+    _fields_ = [("representation", c_i64), ("constraints", c_p), ("width", c_i64), ("workspace", c_p)]
+
+
+# the int32 words of cst_lex_desc.workspace (csrc/beam_search.hip, LexP): per sentence a table of LEX_TBL_W words, then the state pair
+# [2][bsz * beam][LEX_SW]; a state's words: node (ordered: index, -1 = root), bank, finished, number of next tokens, ..., next tokens at 8
+LEX_TBL_W, LEX_SW, LEX_NEXT_MAX, LEX_WIDTH_MAX = 136, 44, 16, 65
+
+
+def lex_states(workspace, bsz, beam):
+    """View [2, bsz * beam, LEX_SW] int32 of the constraint states inside a cst_lex workspace tensor (uint8)."""
+    words = workspace.view(torch.int32)
+    return words[bsz * LEX_TBL_W:bsz * LEX_TBL_W + 2 * bsz * beam * LEX_SW].view(2, bsz * beam, LEX_SW)
+
+
 class FbankDesc(ctypes.Structure):
     _fields_ = [
         ("B", c_i64), ("S", c_i64), ("T", c_i64),
@@ -185,6 +200,9 @@ SYMBOLS = [
     ("cst_beam_init", c_int, [ctypes.POINTER(BeamDesc), c_p]),
     ("cst_beam_step", c_int, [ctypes.POINTER(BeamDesc), c_p]),
     ("cst_beam_step_lm", c_int, [ctypes.POINTER(BeamDesc), ctypes.POINTER(LmFusionDesc), c_p]),
+    ("cst_lex_workspace", c_i64, [c_i64, c_i64, c_i64]),
+    ("cst_lex_init", c_int, [ctypes.POINTER(BeamDesc), ctypes.POINTER(LexDesc), c_p]),
+    ("cst_beam_step_lex", c_int, [ctypes.POINTER(BeamDesc), ctypes.POINTER(LmFusionDesc), ctypes.POINTER(LexDesc), c_p]),
     ("cst_dec_embed", c_int, [c_p, c_p, c_p, c_p, c_f, c_i64, c_p, c_i64, c_i64, c_i64, c_i64, c_int, c_p]),
     ("cst_dec_self_attn", c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_f, c_int, c_p]),
     ("cst_batch_by_size", c_i64, [c_p, c_i64, c_i64, c_i64, ctypes.c_int32, c_p]),

@@ -14,6 +14,10 @@ step), like the dropout masks of rng.py — so the engine and the host loop belo
 --diversity-rate) are the two diverse strategies; the engine runs both inside the per-sentence merge kernel of cst_beam_step
 (include/cst.h, ABI 12), the classes below are the host loop's form of the same selections.
 
+`LexicallyConstrainedBeamSearch` (search.py:210-523: --constraints [ordered|unordered]) keeps a constraint state per hypothesis
+(lexical_constraints.py) and shapes each sentence's candidate list by them; the engine runs it as the third selection rule of the merge
+kernel (cst_beam_step_lex), the class below is the host loop's form of the same rule.
+
 Differences that do not change results: finished sentences are masked out instead of being removed from the batch
 (the reference shrinks the batch, :427-463 — an optimisation only; every sentence's search is independent)."""
 import dataclasses
@@ -24,6 +28,7 @@ import numpy as np
 import torch
 from torch import Tensor
 
+from . import lexical_constraints as LC
 from . import rng
 from .decode_engine import BeamDecodeEngine, DecodeOptions
 
@@ -177,6 +182,97 @@ class DiverseSiblingsSearch:
         return scores_buf, tok.view(bsz, -1).gather(1, pick), pick // k
 
 
+class LexicallyConstrainedBeamSearch:
+    """search.py:210-523.  Every hypothesis carries a constraint state (lexical_constraints.py).  One step of one sentence:
+      1. eos ban: at step > 0 a row whose state is not finished gets lp[eos] = -inf (after the generator's masks, before the cumulative
+         score is added);
+      2. the list L: the sentence's plain top 2*beam; at step > 0 every row's own best candidate, in row order; per row in row order
+         (only the first row at step 0) one candidate per next token of the row's state, in ascending token order, value lp + score;
+      3. per candidate bank = the bank of its parent's state advanced by its token, and the fp32 key = float((nd - bank) * -100) + value,
+         nd = the sentence's number of distinct constraint tokens; L is sorted by the key, descending, stably;
+      4. a candidate whose predecessor in that order (cyclically: the first looks at the last) has the same (parent, token) is dropped;
+      5. the j-th survivor of a run of equal banks gets the stripe nd - bank + j * (survivors + 1); a stable ascending sort by stripe
+         deals the banks round-robin; the first 2*beam are the sentence's candidates, each with its advanced state.
+    update_constraints(active_hypos) then hands next row i the state of candidate active_hypos[i]."""
+
+    def __init__(self, tgt_dict, representation):
+        self.pad, self.unk, self.eos = tgt_dict.pad(), tgt_dict.unk(), tgt_dict.eos()
+        self.vocab_size = len(tgt_dict)
+        if representation not in LC.REPRESENTATIONS:
+            raise ValueError("constraint representation %r (ordered | unordered)" % (representation,))
+        self.representation = representation
+        self.constraint_states = []
+        self.supports_constraints = True
+
+    def init_constraints(self, batch_constraints, beam_size):
+        """batch_constraints: the packed int64 [bsz, W] (lexical_constraints.pack_constraints)."""
+        self.constraint_states = []
+        for row in batch_constraints.tolist():
+            state = LC.create_state(self.representation, row)
+            self.constraint_states.append([state] * beam_size)  # (states are immutable values)
+
+    def update_constraints(self, active_hypos):
+        for sent, act in enumerate(active_hypos.tolist()):
+            self.constraint_states[sent] = [self.constraint_states[sent][i] for i in act]
+
+    def step(self, step: int, lprobs, scores):
+        bsz, beam_size, V = lprobs.size()
+        K = min(2 * beam_size, beam_size * V - 1)
+        states = self.constraint_states
+        if not states:  # no constraints were given to this call: plain beam search (search.py:341-343)
+            return BeamSearch.step(self, step, lprobs, scores)
+        assert len(states) == bsz, "init_constraints() was given another batch"
+        if step > 0:
+            ban = torch.tensor([[not st.finished for st in sent] for sent in states], device=lprobs.device)
+            lprobs = lprobs.clone()
+            lprobs[:, :, self.eos] = lprobs[:, :, self.eos].masked_fill(ban, -math.inf)
+        if step == 0:
+            lprobs = lprobs[:, ::beam_size, :].contiguous()
+        else:
+            lprobs = lprobs + scores[:, :, step - 1].unsqueeze(-1)
+        flat = lprobs.view(bsz, -1)
+        order = torch.sort(flat, dim=1, descending=True, stable=True)[1][:, :K]  # equal values keep their flat-index order
+        top_val, top_tok, top_par = torch.gather(flat, 1, order).tolist(), (order % V).tolist(), (order // V).tolist()
+        if step > 0:  # every row's best, ties to the smaller token
+            best = lprobs.amax(dim=2, keepdim=True)
+            ids = torch.arange(V, device=lprobs.device).expand_as(lprobs)
+            best_tok = torch.where(lprobs == best, ids, torch.full_like(ids, V)).amin(dim=2).tolist()
+            best_val = best.squeeze(2).tolist()
+        host = lprobs.cpu()
+        out_val, out_tok, out_par = [], [], []
+        for b in range(bsz):
+            cand = list(zip(top_val[b], top_tok[b], top_par[b]))
+            if step > 0:
+                cand += [(best_val[b][r], best_tok[b][r], r) for r in range(beam_size)]
+            for r in range(1 if step == 0 else beam_size):
+                cand += [(float(host[b, r, t]), t, r) for t in states[b][r].next_tokens()]
+            val, tok, par, new_states = self._select(cand, states[b], K)
+            states[b] = new_states
+            out_val.append(val), out_tok.append(tok), out_par.append(par)
+        dev = lprobs.device
+        return (torch.tensor(out_val, dtype=torch.float32, device=dev), torch.tensor(out_tok, dtype=torch.long, device=dev),
+                torch.tensor(out_par, dtype=torch.long, device=dev))
+
+    @staticmethod
+    def _select(cand, states, K):
+        """Rules 3-5 over the list `cand` of (value, token, parent) of one sentence; states: its rows' states."""
+        nd = states[0].num_distinct
+        adv = [states[p].advance(t) for _, t, p in cand]
+        value = np.array([v for v, _, _ in cand], dtype=np.float32)
+        bank = np.array([a.bank for a in adv], dtype=np.int64)
+        with np.errstate(invalid="ignore"):
+            key = ((nd - bank) * -100).astype(np.float32) + value
+        order = sorted(range(len(cand)), key=lambda i: -key[i])  # (sorted() is stable; -(-inf) = inf sorts last)
+        pair = [cand[i][1:] for i in order]
+        keep = [i for q, i in enumerate(order) if pair[q] != pair[q - 1]]  # (q = 0 looks at the last one)
+        stripes, run = [], 0
+        for q, i in enumerate(keep):
+            run = run + 1 if q > 0 and bank[i] == bank[keep[q - 1]] else 0
+            stripes.append(nd - int(bank[i]) + run * (len(keep) + 1))
+        chosen = [keep[q] for q in sorted(range(len(keep)), key=lambda q: stripes[q])][:K]
+        return ([cand[i][0] for i in chosen], [cand[i][1] for i in chosen], [cand[i][2] for i in chosen], [adv[i] for i in chosen])
+
+
 class SequenceGenerator:
     def __init__(self, models, tgt_dict, beam_size=1, max_len_a=0, max_len_b=200, min_len=1, normalize_scores=True,
                  len_penalty=1.0, unk_penalty=0.0, temperature=1.0, match_source_len=False, no_repeat_ngram_size=0,
@@ -232,6 +328,10 @@ class SequenceGenerator:
             strategy = dict(diverse_groups=s.num_groups, diverse_strength=s.diversity_strength)
         elif kind is DiverseSiblingsSearch and s.diversity_rate >= 0:
             strategy = dict(sibling_rate=s.diversity_rate)
+        elif kind is LexicallyConstrainedBeamSearch:  # (not an option of cst_beam_desc: the engine's `lexical` keyword)
+            strategy = {}
+        # lexical constraints: the representation; a call hands the constraints themselves to generate()
+        self.lexical = s.representation if isinstance(s, LexicallyConstrainedBeamSearch) else None
         self.fused = bool(fused) and strategy is not None and (eos is None or eos == tgt_dict.eos())
         if isinstance(self.search, DiverseBeamSearch) and self.beam_size % self.search.num_groups != 0:
             raise ValueError("DiverseBeamSearch requires --beam to be divisible by the number of groups (beam %d, %d groups)"
@@ -247,9 +347,29 @@ class SequenceGenerator:
             m.eval()
 
     @torch.no_grad()
-    def generate(self, models, sample, prefix_tokens=None, sample_key=None, **kwargs):
-        """sample_key: the 32-bit key of this call's draws (sampling only); default: the next key of the generator's own stream."""
-        return self._generate(sample, prefix_tokens=prefix_tokens, sample_key=sample_key)
+    def generate(self, models, sample, prefix_tokens=None, sample_key=None, constraints=None, **kwargs):
+        """sample_key: the 32-bit key of this call's draws (sampling only); default: the next key of the generator's own stream.
+        constraints: the packed lexical constraints of the batch, int64 [bsz, W] (lexical_constraints.pack_constraints); needs a
+        LexicallyConstrainedBeamSearch as the search strategy.  None: the search without them."""
+        return self._generate(sample, prefix_tokens=prefix_tokens, sample_key=sample_key, constraints=constraints)
+
+    def _check_constraints(self, constraints, prefix_tokens, bsz):
+        if self.lexical is None:
+            raise ValueError("constraints need a LexicallyConstrainedBeamSearch as the search strategy (--constraints)")
+        if prefix_tokens is not None:  # (the reference copies the first beam's rows at a prefix eos, but not its constraint states)
+            raise ValueError("lexical constraints cannot be combined with prefix_tokens (--prefix-size)")
+        constraints = torch.as_tensor(constraints).to(device="cpu", dtype=torch.long)
+        if constraints.dim() != 2 or constraints.size(0) != bsz:
+            raise ValueError("constraints must be the packed [batch %d, width] tensor, got %s" % (bsz, tuple(constraints.shape)))
+        for row in constraints.tolist():  # the packed layout itself: 0 terminates, pad and eos cannot be asked for
+            LC.pack_constraints([LC.unpack_constraints(row)], pad=self.pad, eos=self.eos)
+        return constraints
+
+    @staticmethod
+    def _unmet(finalized):
+        missing = [b for b, hyps in enumerate(finalized) if not hyps]
+        if missing:
+            raise RuntimeError("lexical constraints not met within max_len: sentences %s" % missing)
 
     def _check_prefix(self, prefix_tokens, bsz, max_len):
         if prefix_tokens.dim() != 2 or prefix_tokens.size(0) != bsz:
@@ -305,7 +425,7 @@ class SequenceGenerator:
         probs = self.lm_model.get_normalized_probs((out[0][:, -1:, :], None), log_probs=True)[:, -1, :]
         return probs * self.lm_weight
 
-    def _generate(self, sample, prefix_tokens=None, sample_key=None):
+    def _generate(self, sample, prefix_tokens=None, sample_key=None, constraints=None):
         self.calls += 1
         key = (sample_key_of(self.seed, self.calls) if sample_key is None else int(sample_key) & 0xFFFFFFFF) if self.sampling else 0
         net_input = sample["net_input"]
@@ -320,6 +440,8 @@ class SequenceGenerator:
             self._check_prefix(prefix_tokens, bsz, max_len)
             if prefix_tokens.size(1) == 0:
                 prefix_tokens = None
+        if constraints is not None:
+            constraints = self._check_constraints(constraints, prefix_tokens, bsz)
         encoder_outs = [m.encoder.forward_torchscript(net_input) for m in self.models]
         if self.fused:
             ok = len(self.models) <= 8 and all(BeamDecodeEngine.supported(m.decoder) for m in self.models)  # else the whole ensemble takes the host loop
@@ -327,13 +449,19 @@ class SequenceGenerator:
                 ok = ok and BeamDecodeEngine.lm_supported(self.lm_model.decoder)
             if self.sampling:  # (the wide-vocabulary row kernel only selects: such vocabularies are sampled by the host loop)
                 ok = ok and BeamDecodeEngine.sampling_supported(self.vocab_size, encoder_outs[0].encoder_out.dtype)
+            if constraints is not None:  # (more constraint tokens or next tokens than cst_lex_init holds: the host loop)
+                ok = ok and BeamDecodeEngine.lexical_supported(constraints, beam_size)
             if ok:
                 if self._engine is None or self._engine.opt.max_len != max_len:
                     self._engine = BeamDecodeEngine([m.decoder for m in self.models], self.tgt_dict,
                                                     dataclasses.replace(self.options, max_len=max_len),
                                                     lm_decoder=None if self.lm_model is None else self.lm_model.decoder,
-                                                    use_graph=self.use_graph, cross_kernel=self.cross_kernel)
-                return self._engine.generate(encoder_outs, bsz, prefix_tokens=prefix_tokens, sample_key=key)
+                                                    use_graph=self.use_graph, cross_kernel=self.cross_kernel, lexical=self.lexical)
+                return self._engine.generate(encoder_outs, bsz, prefix_tokens=prefix_tokens, sample_key=key, constraints=constraints)
+        if self.lexical is not None:  # (sequence_generator.py:216-222; without constraints the strategy steps like BeamSearch)
+            self.search.constraint_states = []
+            if constraints is not None:
+                self.search.init_constraints(constraints, beam_size)
         new_order = torch.arange(bsz, device=device).view(-1, 1).repeat(1, beam_size).view(-1)
         encoder_outs = [m.encoder.reorder_encoder_out(e, new_order) for m, e in zip(self.models, encoder_outs)]
         incremental_states: List[Dict[str, Dict[str, Optional[Tensor]]]] = [{} for _ in self.models]
@@ -407,6 +535,8 @@ class SequenceGenerator:
             active_mask = eos_mask.type_as(cand_offsets) * cand_size + cand_offsets[:eos_mask.size(1)]
             new_cands_to_ignore, active_hypos = torch.topk(active_mask, k=beam_size, dim=1, largest=False)
             cands_to_ignore = new_cands_to_ignore.ge(cand_size)[:, :beam_size]
+            if constraints is not None:  # next row i carries the state of its candidate (:519-520)
+                self.search.update_constraints(active_hypos)
             active_bbsz_idx = torch.gather(cand_bbsz_idx, dim=1, index=active_hypos).view(-1)
             tokens[:, :step + 1] = torch.index_select(tokens[:, :step + 1], dim=0, index=active_bbsz_idx)
             tokens.view(bsz, beam_size, -1)[:, :, step + 1] = torch.gather(cand_indices, dim=1, index=active_hypos)
@@ -415,6 +545,8 @@ class SequenceGenerator:
             scores.view(bsz, beam_size, -1)[:, :, step] = torch.gather(cand_scores, dim=1, index=active_hypos)
             reorder_state = active_bbsz_idx
 
+        if constraints is not None:  # (the reference dies in `assert step < max_len` there)
+            self._unmet(finalized)
         for sent in range(bsz):
             sc = torch.tensor([float(h["score"]) for h in finalized[sent]])
             _, order = torch.sort(sc, descending=True)

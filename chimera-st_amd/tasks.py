@@ -79,7 +79,9 @@ class FairseqTask:
 
     def inference_step(self, generator, models, sample, prefix_tokens=None, constraints=None):
         with torch.no_grad():
-            return generator.generate(models, sample, prefix_tokens=prefix_tokens)
+            if constraints is None:
+                return generator.generate(models, sample, prefix_tokens=prefix_tokens)
+            return generator.generate(models, sample, prefix_tokens=prefix_tokens, constraints=constraints)
 
     # ---- datasets (data.py; tasks/fairseq_task.py:162-275) --------------------------------------------------------
     def dataset(self, split):
@@ -98,9 +100,10 @@ class FairseqTask:
 
     def build_generator(self, models, args, seq_gen_cls=None, extra_gen_cls_kwargs=None):
         """fairseq_task.py:309-412: SequenceScorer with --score-reference (:313-320), else beam search, Sampling with --sampling (:329-357), DiverseBeamSearch with --diverse-beam-groups
-        (:358-361), DiverseSiblingsSearch with --diversity-rate (:373-376) — the reference's selection: exclusivity is tested with
+        (:358-361), DiverseSiblingsSearch with --diversity-rate (:373-376), LexicallyConstrainedBeamSearch with --constraints (:377-380) — the reference's selection: exclusivity is tested with
         `diversity_rate > 0`, the sibling search is chosen with `diversity_rate > -1` (so rate 0 builds it and equals beam search)."""
-        from .sequence_generator import DiverseBeamSearch, DiverseSiblingsSearch, Sampling, SequenceGenerator
+        from .sequence_generator import (DiverseBeamSearch, DiverseSiblingsSearch, LexicallyConstrainedBeamSearch, Sampling,
+                                         SequenceGenerator)
 
         extra = dict(extra_gen_cls_kwargs or {})  # (lm_model / lm_weight of --lm-path, fairseq_cli/generate.py:171)
         if getattr(args, "score_reference", False):  # (:313-320: before any search strategy is looked at; the search flags go unused)
@@ -112,8 +115,14 @@ class FairseqTask:
         diverse_beam_groups = getattr(args, "diverse_beam_groups", -1)
         diverse_beam_strength = getattr(args, "diverse_beam_strength", 0.5)
         diversity_rate = getattr(args, "diversity_rate", -1.0)
+        constrained = getattr(args, "constraints", None) or False  # None | "ordered" | "unordered"
         if sum(int(bool(c)) for c in (sampling, diverse_beam_groups > 0, diversity_rate > 0)) > 1:
             raise ValueError("Provided Search parameters are mutually exclusive.")
+        # (the reference's `elif` chain would silently drop --constraints behind another strategy; here the combination is refused)
+        if constrained and (sampling or diverse_beam_groups > 0 or diversity_rate > -1):
+            raise ValueError("Provided Search parameters are mutually exclusive: --constraints with sampling or a diverse strategy.")
+        if constrained and getattr(args, "prefix_size", 0) > 0:
+            raise ValueError("--constraints cannot be combined with --prefix-size")
         assert sampling_topk < 0 or sampling, "--sampling-topk requires --sampling"
         assert sampling_topp < 0 or sampling, "--sampling-topp requires --sampling"
         if sampling:
@@ -122,6 +131,8 @@ class FairseqTask:
             search = DiverseBeamSearch(self.target_dictionary, diverse_beam_groups, diverse_beam_strength)
         elif diversity_rate > -1:
             search = DiverseSiblingsSearch(self.target_dictionary, diversity_rate)
+        elif constrained:
+            search = LexicallyConstrainedBeamSearch(self.target_dictionary, constrained)
         else:
             search = None
         return SequenceGenerator(

@@ -36,7 +36,8 @@ extern "C" {
  * 11: cst_beam_desc.sampling / sample_topk / sample_topp / sample_key — sampling decode;
  * 12: cst_beam_desc.diverse_groups / diverse_strength / diverse_siblings / sibling_rate — diverse beam groups and diverse siblings;
  * 13: cst_score_tokens — scores of given target tokens, --score-reference).  cst_beam_step_lm and cst_lm_fusion_desc were ADDED at 13
- * without a bump: no existing signature or layout changed, and a library without the symbol fails at symbol lookup.
+ * without a bump: no existing signature or layout changed, and a library without the symbol fails at symbol lookup.  The same holds for
+ * cst_lex_desc, cst_lex_workspace, cst_lex_init and cst_beam_step_lex (lexical constraints), added later at 13.
  * cst_version() returns the value the library was built with; chimera-st_amd/lib.py refuses a mismatch. */
 #define CST_ABI_VERSION 13
 
@@ -652,6 +653,57 @@ int cst_beam_step(const cst_beam_desc* d, cst_stream stream);
  * restriction.  lm_logits or lprobs_out not 16-byte aligned, lm_weight not finite: CST_ERR_BAD_ARG.  Nothing is launched on an error. */
 typedef struct { const void* lm_logits; float lm_weight; float* lprobs_out; } cst_lm_fusion_desc;
 int cst_beam_step_lm(const cst_beam_desc* d, const cst_lm_fusion_desc* f, cst_stream stream);
+/* Lexically constrained beam search (search.py LexicallyConstrainedBeamSearch :210-523 with token_generation_constraints.py; added at
+ * ABI 13): "these phrases must appear".  Every hypothesis row carries a constraint state, every sentence a table; both live in the
+ * workspace of cst_lex_desc.  Still two launches per step: the row kernel rides on the instantiations of no_repeat_ngram / prefix_tokens
+ * behind a pointer, the selection is a third rule of the per-sentence merge kernel beside the two diverse ones.
+ *   constraints: device int64 [bsz][width], the reference's packed layout (pack_constraints :41-91): per sentence
+ *     [count, tokens of constraint 0, 0, tokens of constraint 1, 0, ...], zero-padded.  Read by cst_lex_init only; the caller refills it
+ *     before each call.
+ *   representation 1 (ordered, OrderedConstraintState :387-506): the state is an index into the concatenated constraints, -1 = root.
+ *     advance(t): finished -> stay; t is the next token -> on; the state ends a constraint -> stay, and the ROOT reads endpoints[-1]
+ *     (Python's last entry, always true), so a token that does not start the constraints keeps the root; t is the first token of all ->
+ *     state 0; else the root.  bank = state + 1.  next tokens: the first token of all if state > 0, and the advancing token if not
+ *     finished.  No constraints: finished, bank 0, no next tokens.
+ *   representation 2 (unordered, UnorderedConstraintState :202-358 over the trie ConstraintNode :111-199): the state is a trie node plus,
+ *     per node, `generated` and `completed` counts.  advance(t): the node's child by t if generated[child] < child.num_constraints; else
+ *     back to the root (onto the root's child by t under the same test) and rewind: from the old node upwards, the first node with
+ *     terminal > completed gets completed + 1 and the walk ends, every node before it generated - 1.  bank = sum of generated;
+ *     finished = every constraint completed, counting the node itself when it is an unfinished terminal; next tokens = the root's
+ *     children united with the node's.
+ *   cst_lex_init (after cst_beam_init, on every call, outside a captured step): one workgroup per sentence builds the table — the
+ *     concatenated sequence + endpoints, or the trie's parent / token / terminal / num_constraints, and nd, the number of DISTINCT
+ *     constraint tokens (the reference's len(state.tokens)) — and sets every row's state to the root in both halves of the state pair.
+ *   cst_beam_step_lex(d, f, x): x == NULL is cst_beam_step_lm(d, f): the same kernels and arguments.  Else, at step s, per sentence:
+ *     1. eos ban (:308-321): at s > 0 a row whose state is not finished gets lp[eos] = -inf, after every mask of cst_beam_step (NaN, pad,
+ *        unk, max-len, min-len, n-gram) and before the cumulative score is added; not at step 0.
+ *     2. the list L (:332-357, :398-414): the sentence's plain top 2*beam (value descending, ties to the smaller flat index); at s > 0 each
+ *        row's own best candidate in row order; then per row in row order (only the first row at s = 0) one candidate per next token of
+ *        the row's state in ascending token order, value fl(lp_masked[t] + cumulative score) — formed by the same operations as a list
+ *        entry, so a duplicate is bit-equal to its twin.
+ *     3. (:425-449) bank = the bank of advance(parent's state, token); key = fl(float((nd - bank) * -100) + value) in fp32; L is ordered
+ *        by that fp32 key, descending, stably.  (Not a lexicographic (bank, value) order: scores below -100 and sub-ulp gaps differ.)
+ *     4. (:451-478) a candidate whose predecessor in that order has the same (parent, token) is dropped — cyclically: the first is
+ *        compared with the last; adjacent duplicates only.
+ *     5. (:480-521) the j-th survivor (from 0) of a run of equal banks gets the stripe nd - bank + j * (survivors + 1); a stable ascending
+ *        sort by stripe, the first 2*beam are the sentence's candidates (score = value, token, parent).
+ *     6. the eos / finalize / next-row bookkeeping of cst_beam_step over those; next row i takes the advanced state of its candidate
+ *        (update_constraints :254-260), written into the other half of the state pair.
+ *     A sentence without constraints goes through the same rule and comes out as plain beam search.  A sentence whose constraints cannot
+ *     be met within max_len never finalises anything (all its last-step candidates are -inf): nfinal stays 0, `finished` 0.
+ *   Limits: at most 32 constraint tokens per sentence, i.e. width <= 65 — beyond: CST_ERR_UNSUPPORTED; at most 16 next tokens per state
+ *     (the caller checks both on the host: tokens past the limits are not read).  representation outside {1, 2}, a null or unaligned
+ *     workspace, width < 1, sampling / diverse_groups / diverse_siblings set in d, prefix_len > 0: CST_ERR_BAD_ARG.  Nothing is launched
+ *     on an error.  Composes with members, no_repeat_ngram and f. */
+typedef struct {
+  int64_t representation;            /* 1 ordered, 2 unordered */
+  const int64_t* constraints;        /* device [bsz][width], the packed layout; read by cst_lex_init only */
+  int64_t width;
+  void* workspace;                   /* cst_lex_workspace(bsz, beam, width) bytes, 16-byte aligned: tables, state pair, next-token candidates */
+} cst_lex_desc;
+int64_t cst_lex_workspace(int64_t bsz, int64_t beam, int64_t width);
+int cst_lex_init(const cst_beam_desc* d, const cst_lex_desc* x, cst_stream stream);
+int cst_beam_step_lex(const cst_beam_desc* d, const cst_lm_fusion_desc* f, const cst_lex_desc* x, cst_stream stream);
 /* out[h] = scale * embed[tokens[s&1][h][s]] + pos_table[pad_idx + 1 + s], s = *step (models/transformer.py:744-760,
  * sinusoidal_positional_embedding.py:88-95).  embed/out in `dtype`, pos_table fp32 [pos_rows, C]. */
 int cst_dec_embed(const int64_t* tokens, const int32_t* step, const void* embed, const float* pos_table, float scale,

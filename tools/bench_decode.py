@@ -5,7 +5,7 @@
   python tools/bench_decode.py [--batch 32] [--frames 3000] [--beam 5] [--max-len 200] [--reps 3] [--mirror] [--ensemble N]
                                [--no-repeat-ngram-size N] [--sampling [--sampling-topk K] [--sampling-topp P]]
                                [--diverse-beam-groups G [--diverse-beam-strength S]] [--diversity-rate R]
-                               [--lm-layers L [--lm-weight W]]
+                               [--lm-layers L [--lm-weight W]] [--constraints {ordered,unordered}]
 
 Prints one JSON line: utterances/s and generated tokens/s of the device-resident loop (decode_engine.py: one captured HIP
 graph per step), the per-step time, the encoder time, and — with --mirror — the same numbers for the host-driven
@@ -16,7 +16,10 @@ one beam step over the N logits matrices) and adds "models" and "nodes_per_step"
 --sampling decodes with the Sampling strategy (every hypothesis an independent sample) on the same engine; --diverse-beam-groups and
 --diversity-rate with DiverseBeamSearch / DiverseSiblingsSearch (both inside the beam step's merge kernel).
 --lm-layers L adds shallow fusion with a random pre-norm language model of the decoder's width, heads and ffn size, L layers deep
-(weight --lm-weight): the engine runs it as a member without cross attention and fuses it inside the beam step's row kernel."""
+(weight --lm-weight): the engine runs it as a member without cross attention and fuses it inside the beam step's row kernel.
+--constraints R decodes the batch a second time with LexicallyConstrainedBeamSearch (representation R) and synthetic constraints — two
+one-token phrases and one two-token phrase per sentence — and adds "lexical": its ms_per_step beside the plain-beam figure of the same
+run (same models, batch and step count; the constraint code lives in the two search kernels, so nodes_per_step is the same)."""
 import argparse
 import importlib
 import json
@@ -53,12 +56,16 @@ def main():
     ap.add_argument("--diversity-rate", type=float, default=-1.0, help="diverse siblings search with this rate (negative = off)")
     ap.add_argument("--lm-layers", type=int, default=0, help="fuse a random language model of this depth (0 = off)")
     ap.add_argument("--lm-weight", type=float, default=0.3)
+    ap.add_argument("--constraints", default=None, choices=["ordered", "unordered"],
+                    help="also time lexically constrained beam search with synthetic constraints (three phrases per sentence)")
     ap.add_argument("--profile", action="store_true", help="per-class GPU time of one eager decode loop (hipEvent pairs)")
     args = ap.parse_args()
     if sum((args.sampling, args.diverse_beam_groups > 0, args.diversity_rate > 0)) > 1:
         ap.error("--sampling, --diverse-beam-groups and --diversity-rate are mutually exclusive")
     if args.diverse_beam_groups > 0 and args.beam % args.diverse_beam_groups != 0:
         ap.error("--beam must be divisible by --diverse-beam-groups")
+    if args.constraints and (args.sampling or args.diverse_beam_groups > 0 or args.diversity_rate > -1):
+        ap.error("--constraints times lexically constrained beam search against PLAIN beam search")
 
     importlib.import_module("chimera-st_amd")
     s2t = importlib.import_module("chimera-st_amd.s2t_transformer")
@@ -96,12 +103,12 @@ def main():
     src = torch.randn(args.batch, args.frames, 80, generator=g).to(dt).cuda()
     sample = {"net_input": {"src_tokens": src, "src_lengths": lens.cuda()}}
 
-    def timed(gen):
-        hyps = gen.generate(models, sample)  # warm-up (graph capture, code objects)
+    def timed(gen, **kw):
+        hyps = gen.generate(models, sample, **kw)  # warm-up (graph capture, code objects)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(args.reps):
-            hyps = gen.generate(models, sample)
+            hyps = gen.generate(models, sample, **kw)
         torch.cuda.synchronize()
         dt_ = (time.perf_counter() - t0) / args.reps
         ntok = sum(len(h[0]["tokens"]) for h in hyps)
@@ -150,6 +157,20 @@ def main():
         out["nodes_per_step"] = fused._engine.nodes_per_step(dt, args.batch * args.beam)
     if lm is not None:
         out["config"].update(lm_layers=args.lm_layers, lm_weight=args.lm_weight)
+        out["nodes_per_step"] = fused._engine.nodes_per_step(dt, args.batch * args.beam)
+    if args.constraints:
+        lc = importlib.import_module("chimera-st_amd.lexical_constraints")
+        gc = torch.Generator().manual_seed(7)
+        toks = torch.randint(4, 10000, (args.batch, 4), generator=gc).tolist()  # per sentence: [a], [b], [c d]
+        packed = lc.pack_constraints([[[a], [b], [c, d]] for a, b, c, d in toks], pad=task.target_dictionary.pad(), eos=task.target_dictionary.eos())
+        lex = SG(models, task.target_dictionary, beam_size=args.beam, max_len_a=0, max_len_b=args.max_len, use_graph=not args.no_graph,
+                 cross_kernel=args.cross_kernel, no_repeat_ngram_size=args.no_repeat_ngram_size,
+                 search_strategy=sg_mod.LexicallyConstrainedBeamSearch(task.target_dictionary, args.constraints), **lm_kw)
+        t_x, ntok_x = timed(lex, constraints=packed)
+        assert lex._engine is not None
+        out["lexical"] = {"representation": args.constraints, "phrases_per_sentence": 3, "ms_per_step": (t_x - enc_s) / steps * 1e3,
+                          "utterances_per_s": args.batch / t_x, "best_hyp_tokens": ntok_x,
+                          "nodes_per_step": lex._engine.nodes_per_step(dt, args.batch * args.beam)}
         out["nodes_per_step"] = fused._engine.nodes_per_step(dt, args.batch * args.beam)
     if args.mirror:
         mirror = SG(models, task.target_dictionary, beam_size=args.beam, max_len_a=0, max_len_b=args.max_len, fused=False,
