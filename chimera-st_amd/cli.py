@@ -258,6 +258,8 @@ def generate_parser():
                    "are added to the model's at every step (shallow fusion)")
     p.add_argument("--lm-weight", type=float, default=0.0, help="the weight of the language model's log-probabilities (requires --lm-path)")
     p.add_argument("--nbest", type=int, default=1, help="hypotheses printed per sentence (at most --beam)")
+    p.add_argument("--print-alignment", action="store_true", help="after every hypothesis an A- line: per target token the source position "
+                   "(encoder frame; memory slot for Chimera models) its last-layer cross attention, averaged over the heads, is largest at")
     p.add_argument("--remove-bpe", "--post-process", nargs="?", const="@@ ", default=None, dest="post_process")
     p.add_argument("--scoring", default="bleu")
     p.add_argument("--results-path", default=None)
@@ -291,9 +293,25 @@ def check_generate_args(args):
             raise ValueError("--constraints cannot be combined with --score-reference: nothing is searched")
     if args.lm_weight != 0.0 and args.lm_path is None:
         raise ValueError("--lm-weight requires --lm-path")
+    if args.print_alignment and args.score_reference:
+        raise ValueError("--print-alignment cannot be combined with --score-reference: the scorer returns no attention")
     if args.lm_path is not None and args.score_reference:
         raise ValueError("--lm-path cannot be combined with --score-reference: the scorer has no language model")
     return args
+
+
+def hard_alignment(attention, tokens, pad, eos):
+    """The (source, target) pairs of the A- line of --print-alignment (fairseq_cli/generate.py:296-305 over utils.extract_hard_alignment
+    with the generator's attention): attention [src_len, tgt_len] as a hypothesis carries it, tokens its tgt_len token ids.  Per target
+    position that is neither pad nor eos — the final eos is dropped — the source position with the largest weight, ties to the smallest
+    index; both 0-based.  Padded source positions have weight exactly 0 and so never win."""
+    attention = torch.as_tensor(attention).float().cpu()
+    tokens = torch.as_tensor(tokens).long().cpu()
+    if attention.dim() != 2 or attention.size(1) != tokens.numel():
+        raise ValueError("attention %s does not match %d tokens" % (tuple(attention.shape), tokens.numel()))
+    best = attention.max(dim=0, keepdim=True).values
+    src = torch.where(attention == best, torch.arange(attention.size(0)).unsqueeze(1), torch.full((1, 1), attention.size(0))).amin(dim=0)
+    return [(int(src[t]), t) for t in range(tokens.numel()) if int(tokens[t]) not in (pad, eos)]
 
 
 def read_constraints_file(path):
@@ -409,6 +427,9 @@ def generate_main(argv=None):
                     print("H-%d\t%.6f\t%s" % (sid, float(hj["score"]) / math.log(2), hyp_j), file=out)
                     print("D-%d\t%.6f\t%s" % (sid, float(hj["score"]) / math.log(2), detok(hyp_j)), file=out)
                     print("P-%d\t%s" % (sid, " ".join("%.4f" % (x / math.log(2)) for x in hj["positional_scores"].tolist())), file=out)
+                    if args.print_alignment:
+                        pairs = hard_alignment(hj["attention"], hj["tokens"], tgt_dict.pad(), tgt_dict.eos())
+                        print("A-%d\t%s" % (sid, " ".join("%d-%d" % st for st in pairs)), file=out)
                 if j == 0:  # BLEU and the token count come from the best hypothesis
                     h, hyp = hj, hyp_j
             hyps.append(detok(hyp))
@@ -423,6 +444,7 @@ def generate_main(argv=None):
                "diverse_beam_groups": args.diverse_beam_groups, "diverse_beam_strength": args.diverse_beam_strength,
                "diversity_rate": args.diversity_rate, "score_reference": bool(args.score_reference),
                "lm_path": args.lm_path, "lm_weight": args.lm_weight, "constraints": args.constraints,
+               "print_alignment": bool(args.print_alignment),
                "bleu4_whitespace": corpus_bleu(hyps, refs) if any(refs) else None, "ignored_flags": ignored}
     print(json.dumps(summary), file=out, flush=True)
     if out is not sys.stdout:

@@ -27,6 +27,7 @@ struct BeamP {
   int div_groups;                 // --diverse-beam-groups G (read by the DIV == 1 merge kernels only)
   float div_strength;             // --diverse-beam-strength S >= 0
   float sibling_rate;             // --diversity-rate R >= 0 (read by the DIV == 2 merge kernels only)
+  int32_t* fin_anc;               // optional [bsz][beam][L1]: the ancestry row of every finalised hypothesis
 };
 
 __global__ void beam_init_kernel(BeamP p, int32_t* ticket) {
@@ -1343,6 +1344,7 @@ __global__ __launch_bounds__(256) void beam_merge_kernel(BeamP p, const float* c
         const float cum = j == s ? sc : sc_old[bi * L1 + j];
         const float before = j > 0 ? sc_old[bi * L1 + j - 1] : 0.0f;
         p.fin_pos[slot * L1 + j] = j > 0 ? cum - before : cum;
+        if (p.fin_anc) p.fin_anc[slot * L1 + j] = anc_old[bi * L1 + j];
       }
       if (tid == 0) {
         p.fin_len[slot] = s + 1;
@@ -1414,6 +1416,7 @@ int to_params(const cst_beam_desc* d, BeamP& p) {
   p.ngram = 0; p.prefix_len = 0; p.prefix_tokens = nullptr;  // cst_beam_step sets them
   p.sample_topk = 0; p.sample_topp = 0.0f; p.sample_key = nullptr;
   p.div_groups = 0; p.div_strength = 0.0f; p.sibling_rate = 0.0f;
+  p.fin_anc = d->fin_anc;
   return CST_OK;
 }
 

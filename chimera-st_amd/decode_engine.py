@@ -116,7 +116,7 @@ class StepPlan(NamedTuple):
 
 
 class BeamDecodeEngine:
-    def __init__(self, decoders, tgt_dict, options, lm_decoder=None, use_graph=True, poll=8, cross_kernel=None, lanes=None, lexical=None):
+    def __init__(self, decoders, tgt_dict, options, lm_decoder=None, use_graph=True, poll=8, cross_kernel=None, lanes=None, lexical=None, attention=False):
         # `decoders`: the list of models of a checkpoint ensemble (--path a.pt:b.pt:c.pt; one model is a list of one).  A language model
         # (shallow fusion, --lm-path / --lm-weight, sequence_generator.py:318-324) is one more decoder of the step: a decoder WITHOUT
         # cross attention (lm_supported) whose log-softmax cst_beam_step_lm adds, x lm_weight, to the models' combined log-probabilities.
@@ -130,7 +130,12 @@ class BeamDecodeEngine:
         # `lexical`: None | "ordered" | "unordered" — the representation of the lexical constraints a generate() call may bring
         # (sequence_generator.LexicallyConstrainedBeamSearch; cst_lex_init / cst_beam_step_lex).  A call without constraints runs the
         # engine as if it were None.
+        # `attention` (--print-alignment): keep the last decoder layer's head-averaged cross attention of every step and return it with
+        # the hypotheses.  Like `lexical` it is the engine's, not an option of cst_beam_desc: it sizes the state (the attention history
+        # and the finalised hypotheses' ancestry rows), so an engine is built with it or without it.  Off: every launch, graph node,
+        # buffer and result is what it is without the feature.
         self.opt = options
+        self.attention = bool(attention)
         assert lexical in (None, "ordered", "unordered"), lexical
         assert lexical is None or not (options.sampling or options.diverse_groups > 0 or options.sibling_rate is not None), \
             "sampling, the diverse strategies and lexical constraints are mutually exclusive search strategies"
@@ -227,8 +232,12 @@ class BeamDecodeEngine:
 
     def nodes_per_step(self, dtype, rows=None):
         """Kernel launches (graph nodes) of one decode step: every member's sequence up to its vocabulary projection, then ONE pair of
-        beam-search kernels over the members' logits."""
-        return sum(self._member_nodes(dec, dtype, rows) for dec in self.members) + 2
+        beam-search kernels over the members' logits.  With `attention` every MODEL member's last layer adds cst_attn_avg_probs,
+        and the query projection it reads where the plan otherwise runs that inside the cross-attention launch."""
+        n = sum(self._member_nodes(dec, dtype, rows) for dec in self.members) + 2
+        if self.attention:
+            n += sum(1 + self._plan(dec, dtype, rows).q_in_cross for dec in self.decs)
+        return n
 
     def _member_nodes(self, dec, dtype, rows):
         """embed + the layers (StepPlan.layer_nodes) + final LayerNorm + vocabulary projection."""
@@ -329,6 +338,10 @@ class BeamDecodeEngine:
             beam_ws=torch.zeros(L.load().cst_beam_workspace(bsz, beam), dtype=torch.uint8, device=device),
             prefix=torch.full((bsz, prefix_len), self.pad, dtype=torch.int64, device=device) if prefix_len > 0 else None,
             sample_key=z(1, dt=torch.int32) if self.opt.sampling else None)  # (the 32 bits of the key; the kernel reads them unsigned)
+        if self.attention:
+            # attn_hist[row, s, :]: the head-averaged cross attention row `row` computed at step s (append-only like the K/V caches: a
+            # hypothesis' column j is attn_hist[anc[j], j, :]); fin_anc: the ancestry row of every finalised hypothesis (cst_beam_desc)
+            st.update(attn_hist=z(bbsz, L1, S[0], dt=torch.float32), fin_anc=z(bsz, beam, L1, dt=torch.int32))
         ms = [self._alloc_member(dec, bsz, s, dtype, device, hm) for dec, s, hm in zip(self.decs, S, has_mask)]
         if self.lm is not None:
             ms.append(self._alloc_member(self.lm, bsz, 0, dtype, device, False))
@@ -353,6 +366,8 @@ class BeamDecodeEngine:
             d.prefix_tokens, d.prefix_len = st["prefix"].data_ptr(), prefix_len
         if self.opt.sampling:
             d.sample_key = st["sample_key"].data_ptr()
+        if self.attention:
+            d.fin_anc = st["fin_anc"].data_ptr()
         st["desc"] = d
         st["lex_desc"] = None
         if lex is not None:
@@ -424,7 +439,7 @@ class BeamDecodeEngine:
             self._linear(m["attn"], sa.out_proj.weight, sa.out_proj.bias, x2, resid=x)
             x, x2 = x2, x
             if m["plan"].cross:
-                x, x2 = self._step_cross(layer, li, st, m, p, x, x2, bsz)
+                x, x2 = self._step_cross(layer, li, st, m, p, x, x2, bsz, attn=self.attention and li == len(dec.layers) - 1)
             act = L.ACT_GELU if layer.activation_fn == "gelu" else L.ACT_RELU
             if fused:
                 self._ln_linear(x, p["ln_fc1"], m["f"], act=act)
@@ -439,9 +454,24 @@ class BeamDecodeEngine:
         # the x/x2 swaps of a step (3 per layer, 2 without a cross block) may leave the residual stream in x2: the NEXT step's embed
         # always writes m["x"], and every step performs the same swaps, so the captured sequence is step-invariant.
 
-    def _step_cross(self, layer, li, st, m, p, x, x2, bsz):
+    def _attn_probs(self, ca, st, m, li, bsz):
+        """`attention`, last layer of a model member: this step's head-averaged cross-attention probabilities of m["q"] over the
+        sentence's encoder K (read in place in either layout) -> slot *step of st["attn_hist"]; an ensemble's members add theirs x 1/N
+        one after the other (EnsembleModel.forward_decoder :829-868)."""
+        hist, kx = st["attn_hist"], m["kx"][li]
+        H, D, S = ca.num_heads, ca.head_dim, kx.shape[1]
+        strides = (H * S * D, S * D, D) if m["plan"].head_major else (S * H * D, D, H * D)
+        first = m is st["members"][0]
+        L.check(L.load().cst_attn_avg_probs(L.ptr(m["q"]), m["q"].stride(0), L.ptr(kx), *strides, L.ptr(m["kpm"]), L.ptr(hist), hist.stride(0),
+                                            L.ptr(st["step"]), self.opt.max_len, bsz, self.opt.beam, H, D, S, float(ca.scaling),
+                                            1.0 / len(self.decs), 0 if first else 1, L.dtype_code(m["q"].dtype), L.stream_ptr()),
+                "cst_attn_avg_probs")
+
+    def _step_cross(self, layer, li, st, m, p, x, x2, bsz, attn=False):
         """The cross-attention block of one layer (query projection, attention over the sentence's encoder K/V, out-proj + residual);
-        returns the swapped (x, x2)."""
+        returns the swapped (x, x2).  attn: also record the attention probabilities (_attn_probs) — the launches that feed the residual
+        stream stay what they are, so where the query projection runs inside the cross-attention launch the query is materialised for
+        the probabilities by one more cst_dec_ln_linear (its folded weights are packed anyway)."""
         lib = L.load()
         bbsz, C = m["x"].shape
         dt = L.dtype_code(m["x"].dtype)
@@ -451,6 +481,8 @@ class BeamDecodeEngine:
         S = m["kx"][li].shape[1]
         # cross attention: one workgroup per (sentence, head); the sentence's K/V rows serve all of its beam rows
         if plan.q_in_cross:  # the query projection runs inside the cross-attention launch
+            if attn:
+                self._ln_linear(x, p["ln_q"], m["q"])
             _, sg, sb, eps = p["ln_q"]
             L.check(lib.cst_dec_ln_q_cross_attn(L.ptr(x), x.stride(0), L.ptr(p["ln_q_frag"]), L.ptr(sg), L.ptr(sb), eps, L.ptr(m["kx"][li]),
                                                 L.ptr(m["vx"][li]), L.ptr(m["kpm"]), L.ptr(m["attn"]), L.ptr(st["step"]), self.opt.max_len,
@@ -473,6 +505,8 @@ class BeamDecodeEngine:
                     d.k_sh = d.v_sh = S * D
                     d.k_st = d.v_st = D
                 K.attn_fwd_desc(d)
+        if attn:
+            self._attn_probs(ca, st, m, li, bsz)
         self._linear(m["attn"], ca.out_proj.weight, ca.out_proj.bias, x2, resid=x)
         return x2, x
 
@@ -505,6 +539,8 @@ class BeamDecodeEngine:
         masks = [e.encoder_padding_mask for e in encoder_outs]
         masks = [m if (m is not None and m.dim() == 2) else None for m in masks]
         S, has_mask = tuple(e.shape[0] for e in encs), tuple(m is not None for m in masks)
+        if self.attention and len(set(S)) > 1:  # (the reference's avg_attn.add_ cannot add them either)
+            raise ValueError("attention of an ensemble needs members of one encoder length, got %s" % (S,))
         pk = self._pack(dtype, device)
         lanes = min(self.lanes, bsz)
         bounds = [(bsz * i // lanes, bsz * (i + 1) // lanes) for i in range(lanes)]
@@ -606,14 +642,23 @@ class BeamDecodeEngine:
         if consumer is not None:  # made on a lane's stream, read by the caller on its own
             for t in (d_tokens, d_pos, d_score):
                 t.record_stream(consumer)
+        d_attn = None
+        if self.attention:
+            # column j of hypothesis (b, r) is attn_hist[fin_anc[b, r, j], j, :]: ONE indexed gather over the lane's history (slots past a
+            # hypothesis' length read row 0 of a zero-filled table and are cut off below), then source-major like the reference
+            hist, fa = st["attn_hist"], st["fin_anc"].long()
+            L1 = hist.shape[1]
+            d_attn = hist[fa, torch.arange(L1, device=hist.device).view(1, 1, L1)].transpose(2, 3)  # [bsz, beam, S, L1]
+            if consumer is not None:
+                d_attn.record_stream(consumer)
         fin_score, fin_len, nfinal = d_score.cpu(), st["fin_len"].cpu(), st["nfinal"].cpu()
         finalized = []
         for b in range(bsz):
             hyps = []
             for r in range(int(nfinal[b])):
                 n = int(fin_len[b, r])
-                hyps.append({"tokens": d_tokens[b, r, :n], "score": d_score[b, r], "attention": None, "alignment": None,
-                             "positional_scores": d_pos[b, r, :n]})
+                hyps.append({"tokens": d_tokens[b, r, :n], "score": d_score[b, r], "attention": None if d_attn is None else d_attn[b, r, :, :n],
+                             "alignment": None, "positional_scores": d_pos[b, r, :n]})
             _, order = torch.sort(fin_score[b, :len(hyps)], descending=True)  # sequence_generator.py:529-540
             finalized.append([hyps[i] for i in order.tolist()])
         return finalized

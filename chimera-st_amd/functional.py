@@ -587,6 +587,19 @@ def attention(q, k, v, num_heads, key_padding_mask=None, causal=False, scale=Non
                          *_drop_args(dropout_p))
 
 
+def attention_avg_probs(q, k, num_heads, key_padding_mask=None, scale=None):
+    """The head-averaged attention probabilities fp32 [B, Tq, Tk] of q [B,Tq,C] over k [B,Tk,C] (k may be a channel slice of a packed
+    projection) — what the reference's MultiheadAttention returns as its second value (multihead_attention.py:352-362).  No gradient:
+    inference only (the fused kernels of attention() never materialise the probabilities; this is a kernel of its own)."""
+    if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad):
+        raise NotImplementedError("attention weights are computed under torch.no_grad() only")
+    if scale is None:
+        scale = (q.shape[-1] // num_heads) ** -0.5
+    if key_padding_mask is not None and key_padding_mask.dim() == 0:
+        key_padding_mask = None
+    return K.attn_avg_probs(q, k, num_heads, key_padding_mask, float(scale))
+
+
 class _AttnPackedFn(torch.autograd.Function):
     """Self-attention on a packed projection qkv [B, T, 3C] (q | k | v along channels).  The backward writes dq/dk/dv
     into ONE [B, T, 3C] buffer, so the projection's dX / dW are single GEMMs and x receives a single gradient."""

@@ -817,6 +817,31 @@ def score_tokens(logits_list, target, pad):
     return pos, score, length, packed
 
 
+def attn_avg_probs(q, k, H, kpm, scale, k_strides=None, out=None, out_row_stride=None, step=None, max_len=0, out_scale=1.0,
+                   accumulate=False):
+    """Head-averaged attention probabilities (cst_attn_avg_probs): q [B, Tq, H*D] (unit channel stride, one row stride), k [B, S, H*D]
+    with unit channel stride — or any layout given as k_strides = (k_sb, k_sh, k_st) in elements with k's shape [B, S, ...] only read
+    for B and S — kpm uint8 / bool [B, S] or None -> fp32 [B, Tq, S].  out / out_row_stride / step / max_len / out_scale / accumulate:
+    the kernel's own (include/cst.h); without `out` a fresh tensor is returned."""
+    B, Tq, C = q.shape
+    S, D = k.shape[1], C // H
+    if q.stride(2) != 1 or (B > 1 and q.stride(0) != Tq * q.stride(1)):
+        q = q.contiguous()
+    if k_strides is None:
+        if k.stride(2) != 1:
+            k = k.contiguous()
+        k_strides = (k.stride(0), D, k.stride(1))
+    if kpm is not None:
+        kpm = kpm.to(torch.uint8).contiguous()
+    if out is None:
+        out = torch.empty(B, Tq, S, dtype=torch.float32, device=q.device)
+        out_row_stride = S
+    L.check(L.load().cst_attn_avg_probs(L.ptr(q), q.stride(1), L.ptr(k), *k_strides, L.ptr(kpm), L.ptr(out), out_row_stride, L.ptr(step),
+                                        max_len, B, Tq, H, D, S, float(scale), float(out_scale), int(bool(accumulate)),
+                                        L.dtype_code(q.dtype), L.stream_ptr()), "cst_attn_avg_probs")
+    return out
+
+
 def sumsq(x, out):
     lib = L.load()
     ws = workspace(lib.cst_sumsq_workspace(), x.device)

@@ -95,6 +95,7 @@ class BeamDesc(ctypes.Structure):
         ("no_repeat_ngram", c_i64), ("prefix_tokens", c_p), ("prefix_len", c_i64),
         ("sampling", c_i64), ("sample_topk", c_i64), ("sample_topp", c_f), ("sample_key", c_p),
         ("diverse_groups", c_i64), ("diverse_strength", c_f), ("diverse_siblings", c_i64), ("sibling_rate", c_f),
+        ("fin_anc", c_p),
     ]
 
 
@@ -212,6 +213,8 @@ SYMBOLS = [
     ("cst_fbank_workspace_bytes", c_i64, [c_i64, c_i64]),
     ("cst_fbank", c_int, [ctypes.POINTER(FbankDesc), c_p]),
     ("cst_dec_ln_q_cross_attn", c_int, [c_p, c_i64, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_f, c_int, c_p]),
+    ("cst_attn_avg_probs", c_int, [c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_f, c_f,
+                                   c_int, c_int, c_p]),
 ]
 
 _lib = None

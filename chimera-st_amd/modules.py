@@ -256,14 +256,19 @@ class MultiheadAttention(FairseqIncrementalState, nn.Module):
 
     def forward(self, query, key, value, key_padding_mask=None, incremental_state=None, need_weights=True,
                 static_kv=False, attn_mask=None, before_softmax=False, need_head_weights=False, resid=None, out_dropout_p=0.0, seq=None):
-        """Input shape: Time x Batch x Channel.  Returns (attn [T,B,C], None).
+        """Input shape: Time x Batch x Channel.  Returns (attn [T,B,C], weights).
+        weights: None — except on the cross-attention / incremental branches in eval mode under torch.no_grad() with need_weights:
+        the head-averaged attention probabilities fp32 [B, Tq, Tk] (multihead_attention.py:352-362), by a kernel of their own
+        (cst_attn_avg_probs: the fused attention kernel never materialises them).  Every call site of the package passes
+        need_weights=False but the decoder layer's encoder attention under need_attn.
         `resid` / `out_dropout_p` (extensions): out = resid + dropout(out_proj(attn)) inside out_proj's GEMM epilogue — the
         caller's `residual + self.dropout_module(x)` (transformer_layer.py:139-141) without a separate pass.
         Attention-probability dropout (self.dropout_module, :359) runs inside the attention kernels.
         `seq` (extension): a functional.PackedRows plan — query is [rows, 1, C], the padding-free packing of a right-padded batch;
         every sequence attends to its own real frames (what key_padding_mask expresses for the padded batch)."""
         if need_head_weights or before_softmax:
-            raise NotImplementedError("attention weights never leave the fused kernel (need_weights is ignored)")
+            raise NotImplementedError("per-head / pre-softmax attention weights never leave the fused kernel")
+        want_weights = bool(need_weights) and not self.training and not torch.is_grad_enabled()
         attn_p = self.dropout_module.p if (self.training and self.dropout_module.p > 0) else 0.0
         tgt_len, bsz, embed_dim = query.size()
         assert embed_dim == self.embed_dim
@@ -317,8 +322,10 @@ class MultiheadAttention(FairseqIncrementalState, nn.Module):
                 assert key_padding_mask.size(0) == bsz and key_padding_mask.size(1) == kv.size(1)
             attn = CF.attention_kv(q, kv, self.num_heads, key_padding_mask, self.scaling, dropout_p=attn_p)
             assert not causal
+            weights = (CF.attention_avg_probs(q, kv[..., :embed_dim], self.num_heads, key_padding_mask, self.scaling)
+                       if want_weights else None)
             out = self.out_proj(attn, resid=to_batch_major(resid) if resid is not None else None, dropout_p=out_dropout_p)
-            return to_time_major_view(out), None
+            return to_time_major_view(out), weights
         if self.self_attention:
             k, v = self.k_proj(qb), self.v_proj(qb)
         elif key is not None:
@@ -348,8 +355,12 @@ class MultiheadAttention(FairseqIncrementalState, nn.Module):
             assert key_padding_mask.size(0) == bsz and key_padding_mask.size(1) == k.size(1)
         # q is NOT pre-scaled (reference: q *= scaling, :225); the kernel applies `scale` to QK^T in fp32.
         attn = CF.attention(q, k, v, self.num_heads, key_padding_mask, causal, self.scaling, "bt", "bt", dropout_p=attn_p)
+        weights = None
+        if want_weights:
+            assert not causal, "attention weights are returned for cross attention and single-step decoding"
+            weights = CF.attention_avg_probs(q, k, self.num_heads, key_padding_mask, self.scaling)
         out = self.out_proj(attn, resid=to_batch_major(resid) if resid is not None else None, dropout_p=out_dropout_p)
-        return to_time_major_view(out), None
+        return to_time_major_view(out), weights
 
     @staticmethod
     def _append_prev_key_padding_mask(key_padding_mask, prev_key_padding_mask, batch_size, src_len, static_kv):
@@ -457,7 +468,7 @@ class TransformerEncoderLayer(nn.Module):
         if kv is None:
             # seq: x holds packed rows [rows, 1, C] (functional.PackedRows); every sequence attends to its own rows only
             x, _ = self.self_attn(h, h, h, key_padding_mask=None if seq is not None else encoder_padding_mask, attn_mask=attn_mask,
-                                  resid=residual, out_dropout_p=p_drop, seq=seq)  # residual + dropout(attn)
+                                  need_weights=False, resid=residual, out_dropout_p=p_drop, seq=seq)  # residual + dropout(attn)
         else:
             x, _ = self._cross(h, hk, encoder_padding_mask, residual, p_drop)
         if not self.normalize_before:
@@ -537,6 +548,13 @@ class TransformerDecoderLayer(nn.Module):
     def forward(self, x, encoder_out=None, encoder_padding_mask=None, incremental_state=None, prev_self_attn_state=None,
                 prev_attn_state=None, self_attn_mask=None, self_attn_padding_mask=None, need_attn=False,
                 need_head_weights=False):
+        """need_attn: also return the encoder attention's head-averaged weights fp32 [B, T, S] as the second value
+        (transformer_layer.py:381-382) — in eval mode under torch.no_grad() only."""
+        if need_head_weights:
+            raise NotImplementedError("per-head attention weights never leave the fused kernel")
+        if need_attn and (self.training or torch.is_grad_enabled()):
+            raise NotImplementedError("attention weights (need_attn) are returned in eval mode under torch.no_grad() only")
+        attn = None
         p_drop, p_act = self._drop_ps()
         residual = x
         if self.normalize_before:
@@ -554,9 +572,9 @@ class TransformerDecoderLayer(nn.Module):
                 h, residual = self.encoder_attn_layer_norm.forward_residual(x)
             else:
                 h = x
-            x, _ = self.encoder_attn(query=h, key=encoder_out, value=encoder_out, key_padding_mask=encoder_padding_mask,
-                                     incremental_state=incremental_state, static_kv=True, need_weights=False,
-                                     resid=residual, out_dropout_p=p_drop)
+            x, attn = self.encoder_attn(query=h, key=encoder_out, value=encoder_out, key_padding_mask=encoder_padding_mask,
+                                        incremental_state=incremental_state, static_kv=True, need_weights=bool(need_attn),
+                                        resid=residual, out_dropout_p=p_drop)
             if not self.normalize_before:
                 x = self.encoder_attn_layer_norm(x)
         residual = x
@@ -569,7 +587,7 @@ class TransformerDecoderLayer(nn.Module):
                                       dropout_p=p_drop))
         if not self.normalize_before:
             x = self.final_layer_norm(x)
-        return x, None, None
+        return x, attn, None
 
     def make_generation_fast_(self, need_attn: bool = False, **kwargs):
         self.need_attn = need_attn

@@ -117,18 +117,27 @@ class TransformerDecoder(FairseqIncrementalDecoder):
                 full_context_alignment=False, alignment_layer=None, alignment_heads=None, src_lengths=None,
                 return_all_hiddens=False, **unused):
         x, extra = self.extract_features(prev_output_tokens, encoder_out=encoder_out, incremental_state=incremental_state,
-                                         full_context_alignment=full_context_alignment)
+                                         full_context_alignment=full_context_alignment, alignment_layer=alignment_layer,
+                                         alignment_heads=alignment_heads)
         if not features_only:
             x = self.output_layer(x)
         return x, extra
 
     def extract_features(self, prev_output_tokens, encoder_out=None, incremental_state=None, full_context_alignment=False,
                          alignment_layer=None, alignment_heads=None):
-        return self.extract_features_scriptable(prev_output_tokens, encoder_out, incremental_state, full_context_alignment)
+        return self.extract_features_scriptable(prev_output_tokens, encoder_out, incremental_state, full_context_alignment,
+                                                alignment_layer, alignment_heads)
 
     def extract_features_scriptable(self, prev_output_tokens, encoder_out=None, incremental_state=None,
                                     full_context_alignment=False, alignment_layer=None, alignment_heads=None):
-        """transformer.py:720-828."""
+        """transformer.py:720-828.  alignment_layer = i: extra["attn"] = [the head-averaged cross attention of layer i, fp32 [B, T, S]]
+        (:787-812 with alignment_heads None; eval mode under torch.no_grad()).  DIFFERENCE to the reference: alignment_layer None is
+        "no attention" here (extra["attn"] = [None], as before), not "the last layer" — nothing that does not ask for it pays for it."""
+        if alignment_heads is not None:
+            raise NotImplementedError("alignment_heads: per-head attention weights never leave the fused kernel")
+        if alignment_layer is not None and not 0 <= alignment_layer < self.num_layers:
+            raise ValueError("alignment_layer %r outside the decoder's %d layers" % (alignment_layer, self.num_layers))
+        attn = None
         if incremental_state is None and prev_output_tokens.is_cuda:
             # training / full-sequence path: embed_scale * E[tokens] + sinusoidal positions + dropout in ONE kernel
             # (cst_embed_pos_fwd: make_positions evaluated in-kernel; deterministic table gradient cst_embed_bwd)
@@ -162,14 +171,17 @@ class TransformerDecoder(FairseqIncrementalDecoder):
                 self_attn_mask = self.buffered_future_mask(x)
             else:
                 self_attn_mask = None
-            x, _, _ = layer(x, encoder_out.encoder_out if encoder_out is not None else None,
-                            encoder_out.encoder_padding_mask if encoder_out is not None else None, incremental_state,
-                            self_attn_mask=self_attn_mask, self_attn_padding_mask=self_attn_padding_mask)
+            x, layer_attn, _ = layer(x, encoder_out.encoder_out if encoder_out is not None else None,
+                                     encoder_out.encoder_padding_mask if encoder_out is not None else None, incremental_state,
+                                     self_attn_mask=self_attn_mask, self_attn_padding_mask=self_attn_padding_mask,
+                                     need_attn=idx == alignment_layer)
             inner_states.append(x)
+            if idx == alignment_layer:
+                attn = layer_attn
         if self.layer_norm is not None:
             x = self.layer_norm(x)
         x = x.transpose(0, 1)  # B x T x C (contiguous: batch-major storage)
-        return x, {"attn": [None], "inner_states": inner_states}
+        return x, {"attn": [attn], "inner_states": inner_states}
 
     def output_layer(self, features):
         """transformer.py:830-836 — tied vocabulary projection (cst_gemm, V x C weight k-major)."""
@@ -194,8 +206,9 @@ class TransformerDecoderScriptable(TransformerDecoder):
 
     def extract_features(self, prev_output_tokens, encoder_out=None, incremental_state=None, full_context_alignment=False,
                          alignment_layer=None, alignment_heads=None):
-        x, _ = self.extract_features_scriptable(prev_output_tokens, encoder_out, incremental_state, full_context_alignment)
-        return x, None
+        x, extra = self.extract_features_scriptable(prev_output_tokens, encoder_out, incremental_state, full_context_alignment,
+                                                    alignment_layer, alignment_heads)
+        return x, (None if alignment_layer is None else extra)  # (the reference drops the dict always, s2t_transformer.py:369-389)
 
 
 def build_embedding(dictionary, embed_dim):

@@ -276,7 +276,8 @@ class LexicallyConstrainedBeamSearch:
 class SequenceGenerator:
     def __init__(self, models, tgt_dict, beam_size=1, max_len_a=0, max_len_b=200, min_len=1, normalize_scores=True,
                  len_penalty=1.0, unk_penalty=0.0, temperature=1.0, match_source_len=False, no_repeat_ngram_size=0,
-                 search_strategy=None, eos=None, fused=True, use_graph=True, cross_kernel=None, seed=1, lm_model=None, lm_weight=1.0):
+                 search_strategy=None, eos=None, fused=True, use_graph=True, cross_kernel=None, seed=1, lm_model=None, lm_weight=1.0,
+                 return_attention=False):
         self.models = list(models) if isinstance(models, (list, tuple)) else [models]
         self.model = self.models[0]
         self.tgt_dict = tgt_dict
@@ -292,6 +293,10 @@ class SequenceGenerator:
         self.max_len_a, self.max_len_b, self.min_len = max_len_a, max_len_b, min_len
         self.normalize_scores, self.len_penalty, self.unk_penalty = normalize_scores, len_penalty, unk_penalty
         self.temperature = temperature
+        # return_attention (--print-alignment): every hypothesis' "attention" is the fp32 [src_len, tgt_len] matrix of the reference
+        # (sequence_generator.py:349-355, :523-526, :609-611, :664-674): per emitted token the LAST decoder layer's cross attention,
+        # averaged over the heads and over the members of an ensemble.  Off: "attention" is None and nothing is computed for it.
+        self.return_attention = bool(return_attention)
         # shallow fusion (sequence_generator.py:36-37, :103-106, :318-324): lm_weight x the LM's next-token log-softmax (no temperature)
         # is added to the models' log-probabilities at every step, before any mask
         self.lm_model, self.lm_weight = lm_model, float(lm_weight)
@@ -406,17 +411,26 @@ class SequenceGenerator:
 
     def _forward_decoder(self, tokens, encoder_outs, incremental_states):
         """sequence_generator.py:806-868: per member the last-step logits / temperature -> fp32 log-softmax; an ensemble averages the
-        members' DISTRIBUTIONS: logsumexp over the members - log N (:862-864)."""
-        log_probs = []
+        members' DISTRIBUTIONS: logsumexp over the members - log N (:862-864).  Returns (lprobs, attention): attention is None, or with
+        return_attention the members' last-layer head-averaged cross attention of this step, fp32 [rows, S], summed / N (:829-868)."""
+        log_probs, avg_attn = [], None
         for model, encoder_out, incremental_state in zip(self.models, encoder_outs, incremental_states):
-            logits, _ = model.decoder.forward(tokens, encoder_out=encoder_out, incremental_state=incremental_state)
+            last = len(model.decoder.layers) - 1 if self.return_attention else None
+            logits, extra = model.decoder.forward(tokens, encoder_out=encoder_out, incremental_state=incremental_state, alignment_layer=last)
+            if self.return_attention:
+                a = extra["attn"][0][:, -1, :]
+                if avg_attn is not None and avg_attn.shape != a.shape:
+                    raise ValueError("attention of an ensemble needs members of one encoder length, got %d and %d" % (avg_attn.size(1), a.size(1)))
+                avg_attn = a if avg_attn is None else avg_attn + a
             logits = logits[:, -1:, :]
             if self.temperature != 1.0:
                 logits = logits / self.temperature
             log_probs.append(model.get_normalized_probs((logits, None), log_probs=True)[:, -1, :])
         if len(log_probs) == 1:
-            return log_probs[0]
-        return torch.logsumexp(torch.stack(log_probs, dim=0), dim=0) - math.log(len(log_probs))
+            return log_probs[0], avg_attn
+        if avg_attn is not None:
+            avg_attn = avg_attn / len(log_probs)
+        return torch.logsumexp(torch.stack(log_probs, dim=0), dim=0) - math.log(len(log_probs)), avg_attn
 
     def _lm_lprobs(self, tokens, incremental_state):
         """sequence_generator.py:318-324: lm_weight x the LM's log-softmax at the last position (the reference recomputes the whole
@@ -456,7 +470,8 @@ class SequenceGenerator:
                     self._engine = BeamDecodeEngine([m.decoder for m in self.models], self.tgt_dict,
                                                     dataclasses.replace(self.options, max_len=max_len),
                                                     lm_decoder=None if self.lm_model is None else self.lm_model.decoder,
-                                                    use_graph=self.use_graph, cross_kernel=self.cross_kernel, lexical=self.lexical)
+                                                    use_graph=self.use_graph, cross_kernel=self.cross_kernel, lexical=self.lexical,
+                                                    attention=self.return_attention)
                 return self._engine.generate(encoder_outs, bsz, prefix_tokens=prefix_tokens, sample_key=key, constraints=constraints)
         if self.lexical is not None:  # (sequence_generator.py:216-222; without constraints the strategy steps like BeamSearch)
             self.search.constraint_states = []
@@ -478,6 +493,7 @@ class SequenceGenerator:
         bbsz_offsets = (torch.arange(0, bsz, device=device) * beam_size).unsqueeze(1)
         cand_offsets = torch.arange(0, cand_size, device=device)
         reorder_state = None
+        attn = None  # return_attention: [bbsz, S, max_len + 2], column step + 1 written at `step`, reordered with the tokens (:349-355)
 
         for step in range(max_len + 1):
             if reorder_state is not None:
@@ -486,7 +502,11 @@ class SequenceGenerator:
                 encoder_outs = [m.encoder.reorder_encoder_out(e, reorder_state) for m, e in zip(self.models, encoder_outs)]
                 if self.lm_model is not None:
                     self.lm_model.decoder.reorder_incremental_state_scripting(lm_state, reorder_state)
-            lprobs = self._forward_decoder(tokens[:, :step + 1], encoder_outs, incremental_states)
+            lprobs, avg_attn = self._forward_decoder(tokens[:, :step + 1], encoder_outs, incremental_states)
+            if avg_attn is not None:
+                if attn is None:
+                    attn = torch.zeros(bsz * beam_size, avg_attn.size(1), max_len + 2, device=device, dtype=torch.float32)
+                attn[:, :, step + 1].copy_(avg_attn)
             if self.lm_model is not None:
                 lprobs = lprobs + self._lm_lprobs(tokens[:, :step + 1], lm_state)
             lprobs[lprobs != lprobs] = -math.inf
@@ -522,8 +542,8 @@ class SequenceGenerator:
                     pos[1:] = pos[1:] - pos[:-1].clone()
                     if self.normalize_scores:
                         sc = sc / (step + 1) ** self.len_penalty
-                    finalized[sent].append({"tokens": toks, "score": sc, "attention": None, "alignment": None,
-                                            "positional_scores": pos})
+                    finalized[sent].append({"tokens": toks, "score": sc, "attention": None if attn is None else attn[bi, :, 1:step + 2].clone(),
+                                            "alignment": None, "positional_scores": pos})
                 for sent in set(s for s, _ in top_eos.nonzero(as_tuple=False).tolist()):
                     if not finished[sent] and (len(finalized[sent]) == beam_size or step == max_len):
                         finished[sent] = True
@@ -543,6 +563,8 @@ class SequenceGenerator:
             if step > 0:
                 scores[:, :step] = torch.index_select(scores[:, :step], dim=0, index=active_bbsz_idx)
             scores.view(bsz, beam_size, -1)[:, :, step] = torch.gather(cand_scores, dim=1, index=active_hypos)
+            if attn is not None:
+                attn[:, :, :step + 2] = torch.index_select(attn[:, :, :step + 2], dim=0, index=active_bbsz_idx)
             reorder_state = active_bbsz_idx
 
         if constraints is not None:  # (the reference dies in `assert step < max_len` there)

@@ -140,7 +140,8 @@ class FairseqTask:
             max_len_b=getattr(args, "max_len_b", 200), min_len=getattr(args, "min_len", 1),
             normalize_scores=(not getattr(args, "unnormalized", False)), len_penalty=getattr(args, "lenpen", 1),
             unk_penalty=getattr(args, "unkpen", 0), temperature=getattr(args, "temperature", 1.0),
-            no_repeat_ngram_size=getattr(args, "no_repeat_ngram_size", 0), search_strategy=search, seed=getattr(args, "seed", 1), **extra)
+            no_repeat_ngram_size=getattr(args, "no_repeat_ngram_size", 0), search_strategy=search, seed=getattr(args, "seed", 1),
+            return_attention=getattr(args, "print_alignment", False), **extra)  # (fairseq_task.py:401-402)
 
 
 def _load_dict(args, default_size):

@@ -607,6 +607,12 @@ int cst_adam_step(float* master, float* exp_avg, float* exp_avg_sq, const void* 
  *   sampling, diverse_groups > 0 and diverse_siblings != 0 are mutually exclusive (fairseq_task.py:338-350): two of them together are
  *   CST_ERR_BAD_ARG.  Either diverse strategy composes with members, no_repeat_ngram and prefix_tokens (where the step's prefix token is
  *   eos, the parent is the sentence's first row as above).  Nothing is launched on an error.
+ *   Ancestry of a finalised hypothesis (a tail field added WITHOUT raising CST_ABI_VERSION: off in a zero-filled tail, and the binding
+ *   resolves cst_attn_avg_probs — declared with it — when it loads the library, so a library built before the field fails to load instead
+ *   of ignoring it; no other launch, kernel or store): fin_anc != NULL makes the
+ *   finalisation that writes fin_tokens / fin_pos also write fin_anc[slot][j] = anc[parent row][j] for j <= s — the cache row that
+ *   computed position j of the hypothesis, which is also the row of any other per-step, append-only history (the attention history
+ *   cst_attn_avg_probs writes).
  * ------------------------------------------------------------------------------------------ */
 typedef struct {
   int dtype;                         /* storage type of logits */
@@ -634,6 +640,7 @@ typedef struct {
   float diverse_strength;            /* ABI 12: S >= 0, the Hamming diversity penalty per earlier selection of the token */
   int64_t diverse_siblings;          /* ABI 12: 0 = off, else the sibling penalty below is applied */
   float sibling_rate;                /* ABI 12: R >= 0, read when diverse_siblings != 0 (a negative rate is an error, not "off") */
+  int32_t* fin_anc;                  /* optional, device [bsz][beam][L1]: the ancestry row of every finalised hypothesis (NULL = off; see above) */
 } cst_beam_desc;
 int64_t cst_beam_workspace(int64_t bsz, int64_t beam);
 int cst_beam_init(const cst_beam_desc* d, cst_stream stream);
@@ -751,6 +758,28 @@ int cst_dec_cross_attn(const void* q, const void* kx, const void* vx, const uint
 int cst_dec_ln_q_cross_attn(const void* x, int64_t ldx, const void* Wg, const float* sg, const float* sb, float eps, const void* kx, const void* vx,
                             const uint8_t* key_padding_mask, void* out, const int32_t* step, int64_t max_len, int64_t bsz, int64_t beam, int64_t H,
                             int64_t D, int64_t S, float scale, int dtype, cst_stream stream);
+
+/* Head-averaged attention probabilities — the `attn` the reference's decoder returns for alignment: the weights of
+ * modules/multihead_attention.py:334-362 averaged over the heads (models/transformer.py:808-812 with alignment_heads = None), which
+ * the fused attention kernels never materialise:
+ *   out(b, t)[j] (+)= out_scale * (1/H) * sum_{h = 0 .. H-1} softmax_j(scale * <q[b,t,h,:], k[b,h,j,:]>),   j in [0, S).
+ * q: [B*Tq, H*D] in `dtype`, row stride ldq (elements).  k in `dtype`, element (b, h, j, 0) at k + b*k_sb + h*k_sh + j*k_st with D
+ * contiguous elements behind it: row-major [B, S, H*D] is (S*H*D, D, H*D), head-major [B, H, S, D] is (H*S*D, S*D, D).
+ * key_padding_mask: uint8 [B, S] or NULL; a masked key has probability exactly 0.  out: fp32; the row of (b, t) starts at
+ * out + (b*Tq + t) * out_row_stride, + *step * S when `step` (device int32, optional) is given, and then the launch does nothing once
+ * *step > max_len, like every launch of a captured decode step (max_len is not read without step).  accumulate != 0 adds to what is
+ * there (the members of an ensemble, one after the other on one stream, with out_scale = 1/N); else the S entries are overwritten.
+ * Scores, maxima, exponentials, sums and the head sum are fp32; the heads are added in the order h = 0 .. H-1 by one thread per
+ * (row, key) — no floating-point atomics, so a call is bit-reproducible.  One launch, two passes over the keys: the (maximum, sum) of
+ * every (row, head), then the probabilities (the scores are recomputed, never stored: any S).  VALU arithmetic for every shape.
+ * DIFFERENCE to the reference: in a bf16 model it rounds every head's probabilities to bf16 before averaging
+ * (attn_weights_float.type_as); here the fp32 probabilities are averaged.  A row whose keys are ALL masked writes zeros where the
+ * reference yields NaN; real input always has a valid key.
+ * D in {32, 64}; any S >= 1, Tq >= 1; H*D <= 16384.  A null q / k / out, q, k or out not 16-byte aligned, ldq or a k stride not a
+ * multiple of 16 bytes, out_row_stride < S, a bad D or dtype: CST_ERR_BAD_ARG, nothing is launched. */
+int cst_attn_avg_probs(const void* q, int64_t ldq, const void* k, int64_t k_sb, int64_t k_sh, int64_t k_st, const uint8_t* key_padding_mask,
+                       float* out, int64_t out_row_stride, const int32_t* step, int64_t max_len, int64_t B, int64_t Tq, int64_t H, int64_t D,
+                       int64_t S, float scale, float out_scale, int accumulate, int dtype, cst_stream stream);
 
 /* ------------------------------------------------------------------------------------------
  * Filter banks of collated 16 kHz audio — replaces the per-utterance host feature extraction of the fbank-input route:
