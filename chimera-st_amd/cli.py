@@ -16,7 +16,7 @@ import time
 
 import torch
 
-from . import checkpoint_utils, criterions, fbank, registry, s2t_transformer, tasks, w2v2_transformer, w2v2_transformer_interlingua  # noqa: F401
+from . import checkpoint_utils, criterions, fbank, registry, s2t_transformer, tasks, w2v2_transformer, w2v2_transformer_interlingua, wav2vec2_asr  # noqa: F401
 from .distributed import distributed_init, launch_ranks, needs_self_launch
 from .hostcfg import limit_host_threads
 from .trainer import Trainer
@@ -66,7 +66,11 @@ def validate(trainer, task, args, subset, rank, world):
         torch.distributed.all_reduce(vec)
     out = dict(zip(keys, vec.tolist()))
     ss = max(out.get("sample_size", 1.0), 1.0)
-    return {k: (v / ss / math.log(2) if k.endswith("loss") else v) for k, v in out.items()}  # per-token, base 2 (criterions reduce_metrics)
+    res = {k: (v / ss / math.log(2) if k.endswith("loss") else v) for k, v in out.items()}  # per-token, base 2 (criterions reduce_metrics)
+    derived = getattr(trainer.criterion, "derived_metrics", None)  # criterion `ctc`: uer / wer / raw_wer from the summed error counts
+    if derived is not None:
+        res.update(derived(out))
+    return res
 
 
 def train_main(argv=None):

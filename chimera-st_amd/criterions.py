@@ -225,3 +225,125 @@ class TripletSTMTContrastiveCriterion(LabelSmoothedCrossEntropyCriterion):
     def logging_keys():
         return ("loss", "nll_loss", "st_loss", "st_nll_loss", "mt_loss", "mt_nll_loss", "contrastive_loss", "ntokens", "nsentences",
                 "sample_size")
+
+
+def post_process(sentence, symbol):
+    """data/data_utils.py:340-351."""
+    if symbol == "sentencepiece":
+        sentence = sentence.replace(" ", "").replace("▁", " ").strip()
+    elif symbol == "wordpiece":
+        sentence = sentence.replace(" ", "").replace("_", " ").strip()
+    elif symbol == "letter":
+        sentence = sentence.replace(" ", "").replace("|", " ").strip()
+    elif symbol == "_EOW":
+        sentence = sentence.replace(" ", "").replace("_EOW", " ").strip()
+    elif symbol is not None and symbol != "none":
+        sentence = (sentence + " ").replace(symbol, "").rstrip()
+    return sentence
+
+
+@register_criterion("ctc")
+class CtcCriterion(FairseqCriterion):
+    """fairseq/criterions/ctc.py:18-253.  The loss runs on the model's RAW logits in the fused cst_ctc kernels (no fp32 [T, B, V]
+    log-probability tensor, csrc/ctc.hip); validation decodes the best path on the device (cst_ctc_greedy) and brings B*T + B int32
+    values to the host instead of the log-probabilities; the edit distances are cst_edit_distance (the reference imports
+    `editdistance`).  A training step adds no host synchronisation: the input lengths are computed from the padding mask on the device
+    and handed to the kernel as a device tensor."""
+    single_pass = True
+
+    def __init__(self, task, sentence_avg=False, zero_infinity=False, post_process="letter", wer_args=None):
+        super().__init__(task)
+        d = task.target_dictionary
+        self.blank_idx, self.pad_idx, self.eos_idx = d.bos(), d.pad(), d.eos()
+        self.post_process = post_process if post_process else "letter"
+        if wer_args is not None:
+            raise NotImplementedError("--wer-args (KenLM / lexicon decoding of the validation set, examples/speech_recognition/"
+                                      "w2l_decoder.py) is not built: validation reports the best-path uer / wer / raw_wer only")
+        self.zero_infinity = bool(zero_infinity)
+        self.sentence_avg = bool(sentence_avg)
+
+    @staticmethod
+    def add_args(parser):
+        """:52-73."""
+        parser.add_argument("--zero-infinity", action="store_true", help="zero inf loss")
+        parser.add_argument("--post-process", "--remove-bpe", default="letter")
+        parser.add_argument("--wer-args", type=str, default=None)
+
+    @classmethod
+    def build_criterion(cls, args, task):
+        return cls(task, getattr(args, "sentence_avg", False), getattr(args, "zero_infinity", False),
+                   getattr(args, "post_process", "letter"), getattr(args, "wer_args", None))
+
+    def _targets(self, sample):
+        """The sample's target with pad and eos removed, left-packed [B, Lmax] (the reference's masked_select keeps the same order),
+        on the device without a synchronisation."""
+        t = sample["target"]
+        keep = (t != self.pad_idx) & (t != self.eos_idx)
+        Lmax = t.size(1)
+        dst = torch.where(keep, keep.cumsum(1) - 1, torch.full_like(t, Lmax))
+        packed = t.new_zeros(t.size(0), Lmax + 1).scatter_(1, dst, t)
+        return packed[:, :Lmax].contiguous(), sample["target_lengths"].to(torch.int64)
+
+    def forward(self, model, sample, reduce=True):
+        """:75-183."""
+        net_output = model(**sample["net_input"])
+        logits = net_output["encoder_out"]  # [T, B, V] raw (model.get_logits): the log-softmax is fused into the loss
+        T, B = logits.shape[0], logits.shape[1]
+        if "src_lengths" in sample["net_input"]:
+            input_lengths = sample["net_input"]["src_lengths"].to(torch.int64)
+        elif net_output.get("padding_mask") is not None:
+            input_lengths = (~net_output["padding_mask"]).long().sum(-1)
+        else:
+            input_lengths = torch.full((B,), T, dtype=torch.int64, device=logits.device)
+        targets, target_lengths = self._targets(sample)
+        loss, _ = CF.ctc_loss(logits, targets, target_lengths, input_lengths, self.blank_idx, self.zero_infinity)
+        ntokens = sample["ntokens"] if "ntokens" in sample else int(target_lengths.sum())
+        sample_size = sample["target"].size(0) if self.sentence_avg else ntokens
+        logging_output = {"loss": loss.data, "ntokens": ntokens, "nsentences": sample["id"].numel() if "id" in sample else B,
+                          "sample_size": sample_size}
+        if not model.training:
+            logging_output.update(self.error_counts(logits, input_lengths, sample))
+        return loss, sample_size, logging_output
+
+    @torch.no_grad()
+    def error_counts(self, logits, input_lengths, sample):
+        """:116-181 without a decoder: unit and word errors of the best path."""
+        from . import kernels as K
+        d = self.task.target_dictionary
+        T, B = logits.shape[0], logits.shape[1]
+        host = CF.ctc_greedy(logits, input_lengths, self.blank_idx)[2].cpu()
+        ids, counts = host[:B * T].view(B, T), host[B * T:]
+        tgt = (sample["target_label"] if "target_label" in sample else sample["target"]).cpu()
+        c_err = c_len = w_errs = w_len = 0
+        for b in range(B):
+            t = tgt[b]
+            targ_units_arr = t[(t != self.pad_idx) & (t != self.eos_idx)].tolist()
+            pred_units_arr = ids[b, :int(counts[b])].tolist()
+            c_err += K.edit_distance(pred_units_arr, targ_units_arr)
+            c_len += len(targ_units_arr)
+            targ_words = post_process(d.string(targ_units_arr), self.post_process).split()
+            pred_words = post_process(d.string(pred_units_arr), self.post_process).split()
+            word_ids = {}
+            enc = lambda ws: [word_ids.setdefault(w, len(word_ids)) for w in ws]
+            w_errs += K.edit_distance(enc(pred_words), enc(targ_words))
+            w_len += len(targ_words)
+        return {"wv_errors": w_errs, "w_errors": w_errs, "w_total": w_len, "c_errors": c_err, "c_total": c_len}
+
+    @staticmethod
+    def derived_metrics(out):
+        """reduce_metrics :208-244: uer / wer / raw_wer in per cent from the summed counts (only where the counts exist)."""
+        d = {}
+        if out.get("c_total", 0) > 0:
+            d["uer"] = round(out["c_errors"] * 100.0 / out["c_total"], 3)
+        if out.get("w_total", 0) > 0:
+            d["wer"] = round(out["w_errors"] * 100.0 / out["w_total"], 3)
+            d["raw_wer"] = round(out["wv_errors"] * 100.0 / out["w_total"], 3)
+        return d
+
+    @staticmethod
+    def logging_outputs_can_be_summed() -> bool:
+        return True
+
+    @staticmethod
+    def logging_keys():
+        return ("loss", "ntokens", "nsentences", "sample_size")

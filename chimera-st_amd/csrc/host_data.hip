@@ -3,8 +3,11 @@
 //   cst_wav_info/read : PCM WAV slice decoding — what the reference gets from libsndfile through
 //                       soundfile.read(path, dtype="float32", start=offset, frames=length)
 //                       (fairseq/data/audio/audio_utils.py:7-55): 16-bit PCM samples / 32768.
+//   cst_edit_distance : Levenshtein distance of two id sequences — editdistance.eval in the CTC criterion's validation
+//                       (fairseq/criterions/ctc.py:150-170)
 #include "cst_common.h"
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 namespace {
@@ -122,6 +125,29 @@ int64_t cst_wav_read_f32(const char* path, int64_t start_frame, int64_t nframes,
   }
   fclose(f);
   return done / h.channels;
+}
+
+int64_t cst_edit_distance(const int64_t* a, int64_t na, const int64_t* b, int64_t nb) {
+  if (na < 0 || nb < 0 || (!a && na > 0) || (!b && nb > 0)) { cst_set_error("cst_edit_distance: bad argument"); return CST_ERR_BAD_ARG; }
+  if (nb > na) { const int64_t* p = a; a = b; b = p; const int64_t n = na; na = nb; nb = n; }  // the row is the shorter sequence
+  int64_t* row = (int64_t*)malloc((size_t)(nb + 1) * sizeof(int64_t));
+  if (!row) { cst_set_error("cst_edit_distance: out of memory"); return CST_ERR_WORKSPACE; }
+  for (int64_t j = 0; j <= nb; ++j) row[j] = j;
+  for (int64_t i = 1; i <= na; ++i) {
+    int64_t diag = row[0];  // D[i-1][j-1]
+    row[0] = i;
+    for (int64_t j = 1; j <= nb; ++j) {
+      const int64_t up = row[j];
+      int64_t best = diag + (a[i - 1] != b[j - 1]);
+      if (up + 1 < best) best = up + 1;
+      if (row[j - 1] + 1 < best) best = row[j - 1] + 1;
+      row[j] = best;
+      diag = up;
+    }
+  }
+  const int64_t d = row[nb];
+  free(row);
+  return d;
 }
 
 }  // extern "C"

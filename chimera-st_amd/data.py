@@ -624,3 +624,125 @@ def get_batch_iterator(dataset, max_tokens=None, max_sentences=None, max_positio
                                           required_batch_size_multiple=required_batch_size_multiple)
     return EpochBatchIterator(dataset, batch_sampler, seed=seed, num_shards=num_shards, shard_id=shard_id, epoch=epoch,
                               pin_memory=pin_memory)
+
+
+class LabelEncoder:
+    """tasks/audio_pretraining.py:26-33: a label line -> ids of a FIXED dictionary, no eos appended, unknown symbols -> unk."""
+
+    def __init__(self, dictionary):
+        self.dictionary = dictionary
+
+    def __call__(self, label):
+        return self.dictionary.encode_line(label, append_eos=False, add_if_not_exist=False)
+
+
+class AudioLabelDataset(torch.utils.data.Dataset):
+    """FileAudioDataset (data/audio/raw_audio_dataset.py:21-187) under AddTargetDataset (data/add_target_dataset.py:11-70, batched
+    targets): the wav2vec manifest `<split>.tsv` — the root directory on line 1, then `relpath<TAB>nsamples` — with one label line per
+    utterance.  Samples: net_input = {source [B, S] float32, padding_mask [B, S] bool (with `pad`)}, target int64 [B, L] padded with
+    `pad_idx`, target_lengths, ntokens, id.  `pad`: pad to the longest of a batch (else crop to the shortest), both capped at
+    max_sample_size; `normalize`: per-utterance layer norm of the waveform.  Audio is read through cst_wav_read_f32 (16-bit PCM WAV)."""
+
+    def __init__(self, manifest_path, sample_rate, labels, pad_idx, process_label, max_sample_size=None, shuffle=True, min_length=0,
+                 pad=False, normalize=False):
+        import sys
+        self.sample_rate = sample_rate
+        self.max_sample_size = max_sample_size if max_sample_size is not None else sys.maxsize
+        self.pad, self.shuffle, self.normalize = pad, shuffle, normalize
+        self.pad_idx, self.process_label = pad_idx, process_label
+        self.fnames, self.n_samples, kept = [], [], []
+        with open(manifest_path, "r") as f:
+            self.root_dir = f.readline().strip()
+            for i, line in enumerate(f):
+                items = line.strip().split("\t")
+                assert len(items) == 2, line
+                if min_length is not None and int(items[1]) < min_length:
+                    continue
+                self.fnames.append(items[0])
+                self.n_samples.append(int(items[1]))
+                kept.append(i)
+        self.labels = None if labels is None else [labels[i] for i in kept]  # (a skipped utterance takes its label line along)
+
+    def __len__(self):
+        return len(self.fnames)
+
+    def __getitem__(self, index):
+        path = op.join(self.root_dir, self.fnames[index])
+        wav, sr = get_waveform(path)  # (FLAC is refused there, with the message of the other audio routes)
+        feats = torch.from_numpy(np.ascontiguousarray(wav)).float()
+        if feats.dim() == 2:
+            feats = feats.mean(-1)
+        if sr != self.sample_rate:
+            raise Exception("sample rate: %d, need %d" % (sr, self.sample_rate))
+        if self.normalize:
+            feats = torch.nn.functional.layer_norm(feats, feats.shape)
+        item = {"id": index, "source": feats}
+        if self.labels is not None:
+            item["label"] = self.process_label(self.labels[index]).long()
+        return item
+
+    def _crop(self, wav, target_size):
+        diff = len(wav) - target_size
+        if diff <= 0:
+            return wav
+        start = np.random.randint(0, diff + 1)
+        return wav[start:len(wav) - diff + start]
+
+    def collater(self, samples):
+        samples = [s for s in samples if s["source"] is not None]
+        if len(samples) == 0:
+            return {}
+        sources = [s["source"] for s in samples]
+        sizes = [len(s) for s in sources]
+        target_size = min(max(sizes) if self.pad else min(sizes), self.max_sample_size)
+        collated = sources[0].new_zeros(len(sources), target_size)
+        padding_mask = torch.zeros(collated.shape, dtype=torch.bool) if self.pad else None
+        for i, (source, size) in enumerate(zip(sources, sizes)):
+            diff = size - target_size
+            if diff == 0:
+                collated[i] = source
+            elif diff < 0:
+                assert self.pad
+                collated[i, :size] = source
+                padding_mask[i, diff:] = True
+            else:
+                collated[i] = self._crop(source, target_size)
+        net_input = {"source": collated}
+        if self.pad:
+            net_input["padding_mask"] = padding_mask
+        out = {"id": torch.LongTensor([s["id"] for s in samples]), "net_input": net_input}
+        if self.labels is not None:
+            target = [s["label"] for s in samples]
+            out["target_lengths"] = torch.LongTensor([len(t) for t in target])
+            size = max(len(t) for t in target)
+            out["target"] = torch.full((len(target), size), self.pad_idx, dtype=torch.int64)
+            for i, t in enumerate(target):
+                out["target"][i, :len(t)] = t
+            out["ntokens"] = int(out["target_lengths"].sum())
+        return out
+
+    def num_tokens(self, index):
+        return self.size(index)
+
+    def size(self, index):
+        return self.n_samples[index] if self.pad else min(self.n_samples[index], self.max_sample_size)
+
+    @property
+    def sizes(self):
+        return np.array(self.n_samples)
+
+    def ordered_indices(self):
+        order = [np.random.permutation(len(self))] if self.shuffle else [np.arange(len(self))]
+        order.append(self.n_samples)
+        return np.lexsort(order)[::-1]
+
+    def filter_indices_by_size(self, indices, max_sizes):
+        indices = np.asarray(indices)
+        limit = max_sizes[0] if isinstance(max_sizes, (tuple, list)) else max_sizes
+        if limit is None:
+            return indices, []
+        keep = np.fromiter((self.size(int(i)) <= limit for i in indices), dtype=bool, count=len(indices))
+        return indices[keep], indices[~keep].tolist()
+
+    def batch_by_size(self, indices, max_tokens=None, max_sentences=None, required_batch_size_multiple=1):
+        return batch_by_size(indices, self.num_tokens, max_tokens, max_sentences, required_batch_size_multiple)

@@ -1277,6 +1277,34 @@ def label_smoothed_nll_loss(logits, target, eps, pad):
     return loss, out2[1]
 
 
+class _CtcFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, targets, target_len, input_len, blank, zero_infinity):
+        loss, nll, saved = K.ctc_fwd(logits, targets, target_len, input_len, blank, zero_infinity, need_grad=ctx.needs_input_grad[0])
+        ctx.save_for_backward(*[t for t in saved if t is not None])
+        ctx.cfg = (blank, zero_infinity)
+        ctx.mark_non_differentiable(nll)
+        return loss[0].clone(), nll
+
+    @staticmethod
+    def backward(ctx, dloss, _):
+        blank, zero_infinity = ctx.cfg
+        g = dloss.reshape(1).float().contiguous()
+        return K.ctc_bwd(ctx.saved_tensors, g, blank, zero_infinity), None, None, None, None, None
+
+
+def ctc_loss(logits, targets, target_len, input_len, blank=0, zero_infinity=False):
+    """CTC on raw logits [T, B, V] (any layout with unit class stride; no log-probability tensor is built): returns
+    (loss_sum [differentiable fp32 scalar], nll fp32 [B], detached).  targets int64 [B, Lmax] padded; target_len / input_len int64 [B]
+    on the device.  F.ctc_loss(F.log_softmax(logits.float(), -1), ..., reduction="sum") of the reference."""
+    return _CtcFn.apply(logits, targets, target_len, input_len, int(blank), bool(zero_infinity))
+
+
+def ctc_greedy(logits, input_len, blank=0):
+    """Best-path decode on the device: (ids int32 [B, T] — counts[b] ids, then -1 —, counts int32 [B], packed) — K.ctc_greedy."""
+    return K.ctc_greedy(logits, input_len, int(blank))
+
+
 class _ContrastiveFn(torch.autograd.Function):
     """compute_contrastive (criterions/triplet_st_mt_contrastive.py:154-169), summed over utterances and text slots."""
 

@@ -776,6 +776,97 @@ def ls_ce_bwd(logits, target, lse, gscale, eps, pad):
     return d
 
 
+CTC_L_MAX = 2047  # include/cst.h: the longest padded target cst_ctc_fwd takes
+
+
+def _ctc_layout(logits):
+    """[T, B, V] logits -> (tensor, stride_t, stride_b) with unit class stride; a copy only where the class stride is not 1."""
+    if logits.dim() != 3:
+        raise ValueError("ctc: logits must be [T, B, V], got %s" % (tuple(logits.shape),))
+    if logits.stride(2) != 1 and logits.shape[2] > 1:
+        logits = logits.contiguous()
+    T, B, V = logits.shape
+    # (a dimension of one element has no stride to speak of)
+    return logits, (logits.stride(0) if T > 1 else max(logits.stride(0), V)), (logits.stride(1) if B > 1 else max(logits.stride(1), V))
+
+
+def _ctc_lens(t, n, name):
+    if t.dtype != torch.int64 or tuple(t.shape) != (n,):
+        raise ValueError("ctc: %s must be int64 [%d], got %s %s" % (name, n, t.dtype, tuple(t.shape)))
+    return t.contiguous()
+
+
+def ctc_fwd(logits, targets, target_len, input_len, blank, zero_infinity=False, need_grad=True, check_targets=False):
+    """cst_ctc_fwd (include/cst.h): logits [T, B, V] fp32 / bf16 in any layout with unit class stride (the time-major view of batch-major
+    memory included), targets int64 [B, Lmax] padded, target_len / input_len int64 [B] ON THE DEVICE ->
+    (loss fp32 [1], nll fp32 [B], saved), `saved` = what ctc_bwd needs.  check_targets=True reads the labels' range on the host (one
+    synchronisation) and raises ValueError for a label outside [0, V) or equal to the blank; the training path leaves it off."""
+    logits, st, sb = _ctc_layout(logits)
+    T, B, V = logits.shape
+    if targets.dtype != torch.int64 or targets.dim() != 2 or targets.shape[0] != B:
+        raise ValueError("ctc: targets must be int64 [%d, Lmax], got %s %s" % (B, targets.dtype, tuple(targets.shape)))
+    targets = targets.contiguous()
+    Lmax = targets.shape[1]
+    target_len, input_len = _ctc_lens(target_len, B, "target_len"), _ctc_lens(input_len, B, "input_len")
+    if check_targets and Lmax:
+        live = targets[torch.arange(Lmax, device=targets.device)[None, :] < target_len[:, None]]
+        if live.numel():
+            lo, hi, nb = torch.stack([live.min(), live.max(), live.eq(blank).sum()]).tolist()
+            if lo < 0 or hi >= V or nb:
+                raise ValueError("ctc: labels must lie in [0, %d) and differ from the blank %d; found %d .. %d, %d blanks" % (V, blank, lo, hi, nb))
+    dev = logits.device
+    S = 2 * min(Lmax, CTC_L_MAX) + 1  # (beyond the cap the entry refuses before it touches a buffer)
+    f32 = dict(dtype=torch.float32, device=dev)
+    nll, loss, lse = torch.empty(B, **f32), torch.empty(1, **f32), torch.empty(B, T, **f32)
+    emit, alpha = torch.empty(B, T, S, **f32), torch.empty(B, T, S, **f32)
+    beta = torch.empty(B, T, S, **f32) if need_grad else None
+    L.check(L.load().cst_ctc_fwd(L.ptr(logits), st, sb, L.ptr(targets), Lmax, L.ptr(target_len), L.ptr(input_len), int(blank),
+                                 int(bool(zero_infinity)), L.ptr(nll), L.ptr(loss), L.ptr(lse), L.ptr(emit), L.ptr(alpha), L.ptr(beta),
+                                 T, B, V, L.dtype_code(logits.dtype), L.stream_ptr()), "cst_ctc_fwd")
+    return loss, nll, (logits, targets, target_len, input_len, nll, lse, alpha, beta)
+
+
+def ctc_bwd(saved, gscale, blank, zero_infinity=False):
+    """cst_ctc_bwd: gscale fp32 device scalar [1] -> dlogits in the logits' dtype, [T, B, V] contiguous."""
+    logits, targets, target_len, input_len, nll, lse, alpha, beta = saved
+    assert beta is not None, "ctc_fwd ran with need_grad=False"
+    _, st, sb = _ctc_layout(logits)
+    T, B, V = logits.shape
+    d = torch.empty(T, B, V, dtype=logits.dtype, device=logits.device)
+    L.check(L.load().cst_ctc_bwd(L.ptr(logits), st, sb, L.ptr(targets), targets.shape[1], L.ptr(target_len), L.ptr(input_len), int(blank),
+                                 int(bool(zero_infinity)), L.ptr(nll), L.ptr(lse), L.ptr(alpha), L.ptr(beta), L.ptr(gscale), L.ptr(d),
+                                 B * V, V, T, B, V, L.dtype_code(logits.dtype), L.stream_ptr()), "cst_ctc_bwd")
+    return d
+
+
+def ctc_greedy(logits, input_len, blank):
+    """cst_ctc_greedy: logits [T, B, V] (layouts as ctc_fwd), input_len int64 [B] on the device -> (ids int32 [B, T], counts int32 [B]),
+    views of ONE int32 buffer `packed` [B*T + B], also returned: one transfer brings both to the host."""
+    logits, st, sb = _ctc_layout(logits)
+    T, B, V = logits.shape
+    input_len = _ctc_lens(input_len, B, "input_len")
+    packed = torch.empty(B * T + B, dtype=torch.int32, device=logits.device)
+    ids, counts = packed[:B * T].view(B, T), packed[B * T:]
+    ws = workspace(B * T * 4, logits.device)
+    L.check(L.load().cst_ctc_greedy(L.ptr(logits), st, sb, L.ptr(input_len), int(blank), L.ptr(ws), L.ptr(ids), L.ptr(counts), T, B, V,
+                                    L.dtype_code(logits.dtype), L.stream_ptr()), "cst_ctc_greedy")
+    return ids, counts, packed
+
+
+def edit_distance(a, b):
+    """cst_edit_distance: Levenshtein distance of two sequences of ints (host)."""
+    import ctypes
+
+    import numpy as np
+    a, b = np.ascontiguousarray(a, dtype=np.int64), np.ascontiguousarray(b, dtype=np.int64)
+    lib = L.load()
+    d = lib.cst_edit_distance(a.ctypes.data_as(ctypes.c_void_p) if a.size else None, a.size,
+                              b.ctypes.data_as(ctypes.c_void_p) if b.size else None, b.size)
+    if d < 0:
+        raise RuntimeError("cst_edit_distance failed (%d): %s" % (d, lib.cst_last_error().decode()))
+    return int(d)
+
+
 def _score_rows(x):
     """[B, T, V] -> the 2-D view [B*T, V] (unit column stride, one row stride); a copy only where [B, T] is not one run of rows."""
     B, T, V = x.shape

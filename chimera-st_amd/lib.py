@@ -192,6 +192,10 @@ SYMBOLS = [
     ("cst_ls_ce_fwd", c_int, [c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_f, c_i64, c_int, c_p]),
     ("cst_ls_ce_bwd", c_int, [c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_f, c_i64, c_int, c_p]),
     ("cst_score_tokens", c_int, [c_p, ctypes.POINTER(c_p), c_i64, c_i64, c_p, c_i64, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_int, c_p]),
+    ("cst_ctc_fwd", c_int, [c_p, c_i64, c_i64, c_p, c_i64, c_p, c_p, c_i64, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_int, c_p]),
+    ("cst_ctc_bwd", c_int, [c_p, c_i64, c_i64, c_p, c_i64, c_p, c_p, c_i64, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64,
+                            c_int, c_p]),
+    ("cst_ctc_greedy", c_int, [c_p, c_i64, c_i64, c_p, c_i64, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_int, c_p]),
     ("cst_contrastive_fwd", c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_f, c_int, c_p]),
     ("cst_contrastive_bwd", c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_f, c_int, c_p]),
     ("cst_sumsq_workspace", c_i64, []),
@@ -209,6 +213,7 @@ SYMBOLS = [
     ("cst_batch_by_size", c_i64, [c_p, c_i64, c_i64, c_i64, ctypes.c_int32, c_p]),
     ("cst_wav_info", c_int, [ctypes.c_char_p, c_p, c_p, c_p, c_p]),
     ("cst_wav_read_f32", c_i64, [ctypes.c_char_p, c_i64, c_i64, c_p, c_i64]),
+    ("cst_edit_distance", c_i64, [c_p, c_i64, c_p, c_i64]),
     ("cst_dec_cross_attn", c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_f, c_int, c_p]),
     ("cst_fbank_workspace_bytes", c_i64, [c_i64, c_i64]),
     ("cst_fbank", c_int, [ctypes.POINTER(FbankDesc), c_p]),

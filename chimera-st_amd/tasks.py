@@ -268,3 +268,57 @@ def synthetic_sample(dictionary, batch_size, audio_lengths, target_lengths, src_
         sample["src_text"] = collate_tokens(src, pad, eos).to(device)
         sample["src_text_lengths"] = torch.tensor([len(s) for s in src], device=device)
     return sample
+
+
+@register_task("audio_pretraining")
+class AudioPretrainingTask(FairseqTask):
+    """tasks/audio_pretraining.py:36-167 with --labels: fine-tuning wav2vec2 on transcripts (criterion ctc, arch wav2vec_ctc).
+    <data>/<split>.tsv is the wav2vec manifest, <data>/<split>.<labels> holds one label line per utterance and
+    <data>/dict.<labels>.txt the target dictionary.  Without --labels the reference pre-trains wav2vec2, which is not built."""
+
+    @staticmethod
+    def add_args(parser):
+        parser.add_argument("data", help="path to data directory")
+        parser.add_argument("--sample-rate", default=16000, type=int)
+        parser.add_argument("--normalize", action="store_true", help="if set, normalizes input to have 0 mean and unit variance")
+        parser.add_argument("--max-sample-size", default=None, type=int)
+        parser.add_argument("--min-sample-size", default=None, type=int)
+        parser.add_argument("--enable-padding", action="store_true", help="pad shorter samples instead of cropping")
+        parser.add_argument("--labels", type=str, default=None, help="extension of the label file to load, if any")
+
+    def __init__(self, args, source_dictionary=None, target_dictionary=None):
+        super().__init__(args)
+        self._target_dictionary, self._source_dictionary = target_dictionary, source_dictionary
+        self.is_ctc = getattr(args, "criterion", None) == "ctc"
+        self.datasets = {}
+
+    @classmethod
+    def setup_task(cls, args, **kwargs):
+        if not getattr(args, "labels", None):
+            raise NotImplementedError("wav2vec2 pre-training is not built: the audio_pretraining task needs --labels (CTC fine-tuning)")
+        target_dictionary = kwargs.pop("target_dictionary", None)
+        if target_dictionary is None:
+            target_dictionary = Dictionary.load(os.path.join(args.data, "dict.%s.txt" % args.labels))
+        return cls(args, target_dictionary=target_dictionary)
+
+    def load_dataset(self, split, **kwargs):
+        from . import data as D
+        with open(os.path.join(self.args.data, "%s.%s" % (split, self.args.labels)), "r") as f:
+            labels = [line for line in f]
+        d = self.target_dictionary
+        self.datasets[split] = D.AudioLabelDataset(
+            os.path.join(self.args.data, "%s.tsv" % split), getattr(self.args, "sample_rate", 16000), labels, d.pad(),
+            D.LabelEncoder(d), max_sample_size=self.args.max_sample_size, min_length=self.args.min_sample_size, pad=self.args.labels is not None or self.args.enable_padding, normalize=self.args.normalize)
+        return self.datasets[split]
+
+    @property
+    def source_dictionary(self):
+        return self._source_dictionary
+
+    @property
+    def target_dictionary(self):
+        return self._target_dictionary
+
+    def max_positions(self):
+        import sys
+        return sys.maxsize, sys.maxsize

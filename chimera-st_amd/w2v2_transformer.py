@@ -34,6 +34,27 @@ def load_w2v_checkpoint(path):
     return torch.load(path, map_location="cpu")
 
 
+W2V_HEAD_PREFIXES = ("quantizer.", "project_q.", "target_glu.", "final_proj.")
+
+
+def asr_finetuned_w2v(ckpt):
+    """(wav2vec2 arguments, wav2vec2 state dict) out of a wav2vec_ctc checkpoint (w2v2_transformer.py:270-282, without its dictionary
+    download and task set-up): the configuration is args.w2v_args, the weights are the w2v_encoder.w2v_model.* entries — without the
+    pre-training heads, which such a checkpoint lacks (remove_pretraining_modules)."""
+    w2v_args = getattr(ckpt["args"], "w2v_args", None)
+    if isinstance(w2v_args, dict):  # (newer reference checkpoints keep a config tree there)
+        w2v_args = w2v_args.get("model", w2v_args)
+        if isinstance(w2v_args, dict):
+            w2v_args = argparse.Namespace(**w2v_args)
+    if w2v_args is None:
+        raise ValueError("--use-asr-finetune-w2v needs a wav2vec_ctc checkpoint whose args carry w2v_args")
+    prefix = "w2v_encoder.w2v_model."
+    given = {k[len(prefix):]: v for k, v in (ckpt["model"] or {}).items() if k.startswith(prefix)}
+    if not given:
+        raise ValueError("--use-asr-finetune-w2v: the checkpoint holds no %s* weights" % prefix)
+    return w2v_args, given
+
+
 @register_model("s2t_transformer_w2v2")
 class S2TTransformerModelW2V2(FairseqEncoderDecoderModel):
     single_use_parameters = True  # one forward pass uses every parameter once (trainer.py: deferred reductions); tied tables are detected by name
@@ -83,14 +104,27 @@ class S2T_W2V2_TransformerEncoder(FairseqEncoder):
         assert args.w2v2_model_path is not None
         self.w2v2_model_path = args.w2v2_model_path
         self.use_asr_finetune_w2v = args.use_asr_finetune_w2v
-        assert not self.use_asr_finetune_w2v, "wav2vec-CTC checkpoints are not on the Chimera script path"
         self.reset_w2v = getattr(args, "reset_w2v", False)
         self.max_source_positions = args.max_source_positions
-        ckpt = load_w2v_checkpoint(self.w2v2_model_path)
-        self.w2v_args = ckpt["args"]
-        self.wav2vec_model = Wav2Vec2Model.build_model(ckpt["args"], task=None)
-        if not self.reset_w2v and ckpt["model"] is not None:
-            self.wav2vec_model.load_state_dict(ckpt["model"])
+        if self.use_asr_finetune_w2v:
+            if str(self.w2v2_model_path).startswith("synthetic:"):
+                raise ValueError("--use-asr-finetune-w2v takes a wav2vec_ctc checkpoint file, not %s" % self.w2v2_model_path)
+            from . import checkpoint_utils
+            ckpt = checkpoint_utils.load_checkpoint_to_cpu(self.w2v2_model_path)  # a full training checkpoint (optimizer history, nested args)
+            self.w2v_args, weights = asr_finetuned_w2v(ckpt)
+        else:
+            ckpt = load_w2v_checkpoint(self.w2v2_model_path)
+            self.w2v_args, weights = ckpt["args"], ckpt["model"]
+        self.wav2vec_model = Wav2Vec2Model.build_model(self.w2v_args, task=None)
+        if not self.reset_w2v and weights is not None:
+            if self.use_asr_finetune_w2v:
+                # the heads the checkpoint lacks keep this model's initial values (they are inert here); nothing else may be missing
+                missing, unexpected = self.wav2vec_model.load_state_dict(weights, strict=False)
+                stray = [k for k in missing if not k.startswith(W2V_HEAD_PREFIXES)]
+                if stray or unexpected:
+                    raise ValueError("wav2vec_ctc checkpoint does not fit its w2v_args: missing %s, unexpected %s" % (stray, list(unexpected)))
+            else:
+                self.wav2vec_model.load_state_dict(weights)
         # this encoder reads the wav2vec2 output only through the subsampler (a few frames past each utterance's end) and masks
         # padding from there on: the padding frames of the wav2vec2 layer stack are never consumed (wav2vec2.TransformerEncoder)
         self.wav2vec_model.encoder.padding_rows_consumed = False

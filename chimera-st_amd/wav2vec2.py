@@ -2,9 +2,10 @@
 path: ConvFeatureExtractionModel (:685-763), Wav2Vec2Model.forward features_only branch (:527-586) and
 extract_features (:650-652), TransformerEncoder (:766-861), TransformerSentenceEncoderLayer (:864-959).
 
-Pre-training-only parts (quantizer, negatives sampling, masking) are out of scope;
+Pre-training-only parts (quantizer, negatives sampling) are out of scope;
 their parameters that exist in every checkpoint (mask_emb, project_q, final_proj) are kept so
-state dicts round-trip.
+state dicts round-trip.  Fine-tuning's time / channel masking (apply_mask :414-452 over
+data_utils.compute_mask_indices) is built for wav2vec2_asr.py: forward(mask=True).
 
 MI355X layout: the whole CNN runs channels-last [B, L, C] so every conv after layer 0 is an implicit GEMM on
 MFMA tiles with the GELU in the epilogue, and `features.transpose(1, 2)` (:539) is free."""
@@ -324,7 +325,9 @@ class Wav2Vec2Model(nn.Module):
     def add_args(parser):
         pass
 
-    def __init__(self, args):
+    def __init__(self, args, pretraining_heads=True):
+        """pretraining_heads=False: built as the reference leaves the model after remove_pretraining_modules() (wav2vec2.py:678-682) —
+        no quantizer / project_q / target_glu / final_proj, the key set of `w2v_encoder.w2v_model.*` in a wav2vec_ctc checkpoint."""
         super().__init__()
         self.args = args
         feature_enc_layers = eval(args.conv_feature_layers)
@@ -365,6 +368,49 @@ class Wav2Vec2Model(nn.Module):
         if getattr(args, "target_glu", False):
             self.target_glu = nn.Sequential(Linear(final_dim, final_dim * 2), nn.GLU())
         self.final_proj = Linear(args.encoder_embed_dim, final_dim)
+        # fine-tuning's time / channel masking (wav2vec2.py:341-353); read with the reference's defaults so that no Namespace grows
+        self.mask_prob, self.mask_length = getattr(args, "mask_prob", 0.65), getattr(args, "mask_length", 10)
+        self.mask_selection, self.mask_other = getattr(args, "mask_selection", "static"), getattr(args, "mask_other", 0)
+        self.no_mask_overlap, self.mask_min_space = getattr(args, "no_mask_overlap", False), getattr(args, "mask_min_space", 1)
+        self.mask_channel_prob, self.mask_channel_length = getattr(args, "mask_channel_prob", 0), getattr(args, "mask_channel_length", 10)
+        self.mask_channel_selection = getattr(args, "mask_channel_selection", "static")
+        self.mask_channel_other = getattr(args, "mask_channel_other", 0)
+        self.no_mask_channel_overlap = getattr(args, "no_mask_channel_overlap", False)
+        self.mask_channel_min_space = getattr(args, "mask_channel_min_space", 1)
+        if not pretraining_heads:
+            self.remove_pretraining_modules()
+
+    def remove_pretraining_modules(self):
+        """wav2vec2.py:678-682."""
+        self.quantizer = self.project_q = self.target_glu = self.final_proj = None
+
+    def draw_masks(self, B, T, host_lens):
+        """The draws of apply_mask (wav2vec2.py:414-452) from numpy's global generator, in its order: the time mask [B, T] over each
+        utterance's real frames (host_lens: host integers, None without a padding mask), then the channel mask [B, C].  Returns device
+        bool tensors (None where the probability is 0); nothing here waits for the device."""
+        dev = self.mask_emb.device
+        tmask = cmask = None
+        if self.mask_prob > 0:
+            tmask = torch.from_numpy(compute_mask_indices((B, T), host_lens, self.mask_prob, self.mask_length, self.mask_selection,
+                                                          self.mask_other, min_masks=2, no_overlap=self.no_mask_overlap,
+                                                          min_space=self.mask_min_space)).to(dev, non_blocking=True)
+        if self.mask_channel_prob > 0:
+            C = self.mask_emb.numel()
+            cmask = torch.from_numpy(compute_mask_indices((B, C), None, self.mask_channel_prob, self.mask_channel_length,
+                                                          self.mask_channel_selection, self.mask_channel_other,
+                                                          no_overlap=self.no_mask_channel_overlap,
+                                                          min_space=self.mask_channel_min_space)).to(dev, non_blocking=True)
+        return tmask, cmask
+
+    def apply_mask(self, x, tmask, cmask):
+        """x[tmask] = mask_emb; x[:, :, cmask] = 0 (wav2vec2.py:429, :450) as where-compositions: a boolean index_put would wait for
+        the device.  Autograd gives mask_emb the sum of the incoming gradient over the masked frames (channel-masked columns excluded)
+        and passes nothing back through a masked position."""
+        if tmask is not None:
+            x = torch.where(tmask.unsqueeze(-1), self.mask_emb.to(x.dtype), x)
+        if cmask is not None:
+            x = x.masked_fill(cmask.unsqueeze(1), 0.0)
+        return x
 
     @classmethod
     def build_model(cls, args, task=None):
@@ -372,12 +418,12 @@ class Wav2Vec2Model(nn.Module):
         return cls(args)
 
     def forward(self, source, padding_mask=None, mask=True, features_only=False):
-        assert features_only and not mask, "only the features_only / mask=False path is built (SURVEY §2.1 #2)"
+        assert features_only, "only the features_only path is built: wav2vec2 pre-training is out of scope (SURVEY §2.1 #2)"
         if self.training:
             # pre-training-only parameters never receive a gradient on this path: without this the gradient bucket that holds
             # final_proj (the FIRST wav2vec2 bucket in backward order) would wait for finish() and un-overlap every later one
-            heads = [self.mask_emb] + list(self.final_proj.parameters()) + list(self.project_q.parameters())
-            for m in (self.quantizer, self.target_glu):
+            heads = [] if (mask and self.mask_prob > 0) else [self.mask_emb]
+            for m in (self.final_proj, self.project_q, self.quantizer, self.target_glu):
                 if m is not None:
                     heads += list(m.parameters())
             notify_unused_parameters(heads)
@@ -399,6 +445,14 @@ class Wav2Vec2Model(nn.Module):
             # every conv layer's weight-gradient reduction and the frames the CNN has to compute at all
             pos = torch.arange(1, t1 + 1, device=frame_mask.device, dtype=torch.int32)
             nz_last = (pos * (~frame_mask)).amax(dim=1).to(torch.int32)
+        masks = None
+        if mask:
+            # fine-tuning's masks are drawn HERE, on host integers, before anything is queued: the per-utterance frame counts are the
+            # packing plan's host lengths (the reference reads them with an .item() per row in the middle of the forward pass)
+            host_lens = None
+            if padding_mask is not None:
+                host_lens = plan.host_lens if plan is not None else (~frame_mask).sum(dim=1).tolist()
+            masks = self.draw_masks(source.shape[0], self.feature_extractor.output_length(source.shape[1]), host_lens)
         self.last_plan = plan  # (the caller's own layer stack derives its packing plan from this one's host lengths)
         feats = self.feature_extractor(source, nz_last)  # [B, T1, C] channels-last
         if self.feature_grad_mult <= 0:
@@ -413,12 +467,73 @@ class Wav2Vec2Model(nn.Module):
             feats = self.post_extract_proj(feats)
         if self.training and self.dropout_input_p > 0:
             feats = CF.dropout(feats, self.dropout_input_p)  # self.dropout_input (:553)
+        if masks is not None:
+            feats = self.apply_mask(feats, *masks)  # (:561-562)
         x, padding_mask = self.encoder(feats, padding_mask=padding_mask, plan=plan)
         return {"x": x, "padding_mask": padding_mask}
 
     def extract_features(self, source, padding_mask, mask=False):
         res = self.forward(source, padding_mask, mask=mask, features_only=True)
         return res["x"], res["padding_mask"]
+
+
+def compute_mask_indices(shape, lengths, mask_prob, mask_length, mask_type="static", mask_other=0.0, min_masks=0, no_overlap=False,
+                         min_space=0):
+    """Span masks [bsz, all_sz] (numpy bool) with the draws of data/data_utils.py:354-478 from numpy's GLOBAL generator, in the same
+    order, so that a seed reproduces the reference's masks.  `lengths`: the real elements per row as host integers where the reference
+    is given a padding mask (it then draws one rounding number per row), None where it is given none."""
+    bsz, all_sz = shape
+    mask = np.zeros((bsz, all_sz), dtype=bool)
+    all_num_mask = max(min_masks, int(mask_prob * all_sz / float(mask_length) + np.random.rand()))
+    rows = []
+    for i in range(bsz):
+        if lengths is not None:
+            sz = int(lengths[i])
+            num_mask = max(min_masks, int(mask_prob * sz / float(mask_length) + np.random.rand()))
+        else:
+            sz, num_mask = all_sz, all_num_mask
+        if mask_type == "static":
+            spans = np.full(num_mask, mask_length)
+        elif mask_type == "uniform":
+            spans = np.random.randint(mask_other, mask_length * 2 + 1, size=num_mask)
+        elif mask_type == "normal":
+            spans = [max(1, int(round(v))) for v in np.random.normal(mask_length, mask_other, size=num_mask)]
+        elif mask_type == "poisson":
+            spans = [int(round(v)) for v in np.random.poisson(mask_length, size=num_mask)]
+        else:
+            raise ValueError("unknown mask selection " + mask_type)
+        if sum(spans) == 0:
+            spans[0] = min(mask_length, sz - 1)
+        if no_overlap:
+            idc = []
+            parts = [(0, sz)]
+            shortest = min(spans)
+            for span in sorted(spans, reverse=True):
+                room = np.array([e - s if e - s >= span + min_space else 0 for s, e in parts], dtype=np.int64)
+                if room.sum() == 0:
+                    break
+                s, e = parts.pop(np.random.choice(len(parts), p=room / room.sum()))
+                start = np.random.randint(s, e - span)
+                idc.extend(range(start, start + span))
+                if start - s - min_space >= shortest:
+                    parts.append((s, start - min_space + 1))
+                if e - start - shortest - min_space > shortest:
+                    parts.append((start + span + min_space, e))
+            idc = np.asarray(idc, dtype=np.int64)
+        else:
+            shortest = min(spans)
+            if sz - shortest <= num_mask:
+                shortest = sz - num_mask - 1
+            starts = np.random.choice(sz - shortest, num_mask, replace=False)
+            idc = np.asarray([starts[j] + o for j in range(len(starts)) for o in range(spans[j])], dtype=np.int64)
+        rows.append(np.unique(idc[idc < sz]))
+    keep = min(len(r) for r in rows)
+    for i, r in enumerate(rows):
+        if len(r) > keep:
+            r = np.random.choice(r, keep, replace=False)
+        mask[i, r] = True
+    return mask
+
 
 class _InertGumbelVectorQuantizer(nn.Module):
     """Parameter shapes of modules/gumbel_vector_quantizer.py:12-76 (combine_groups=False, weight_proj_depth=1): `vars`

@@ -37,7 +37,8 @@ extern "C" {
  * 12: cst_beam_desc.diverse_groups / diverse_strength / diverse_siblings / sibling_rate — diverse beam groups and diverse siblings;
  * 13: cst_score_tokens — scores of given target tokens, --score-reference).  cst_beam_step_lm and cst_lm_fusion_desc were ADDED at 13
  * without a bump: no existing signature or layout changed, and a library without the symbol fails at symbol lookup.  The same holds for
- * cst_lex_desc, cst_lex_workspace, cst_lex_init and cst_beam_step_lex (lexical constraints), added later at 13.
+ * cst_lex_desc, cst_lex_workspace, cst_lex_init and cst_beam_step_lex (lexical constraints), added later at 13, and for cst_ctc_fwd,
+ * cst_ctc_bwd, cst_ctc_greedy and cst_edit_distance (CTC fine-tuning).
  * cst_version() returns the value the library was built with; chimera-st_amd/lib.py refuses a mismatch. */
 #define CST_ABI_VERSION 13
 
@@ -502,6 +503,51 @@ int cst_score_tokens(const void* logits, const void* const* logits_n, int64_t me
                      float* pos, float* score, int32_t* len, int64_t B, int64_t T, int64_t V, int dtype, cst_stream stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Connectionist temporal classification on RAW logits (criterion `ctc`; added at ABI 13 without a bump, as cst_beam_step_lm was: no
+ * existing signature changed).  The fp32 [T, B, V] log-probability tensor of the reference is never materialised, on either pass.
+ *
+ * Common operands.  logits: `dtype` (fp32 or bf16), element (t, b, v) at logits[t * stride_t + b * stride_b + v] — unit class stride,
+ *   strides in elements, both >= V, any element-aligned base: a contiguous [T, B, V] tensor (stride_t = B V, stride_b = V) and the
+ *   time-major view of batch-major memory (stride_t = V, stride_b = T V) are read by the same kernel without a copy, and give EQUAL
+ *   BITS: every sum's order depends on class indices only, never on a row's alignment (16-byte loads where a row's base is 16-byte
+ *   aligned, scalar loads of the same elements in the same order where it is not).
+ *   targets int64 [B, Lmax], padded; target_len int64 [B], input_len int64 [B], both on the device (clamped to [0, Lmax] / [0, T]).
+ *   Labels must lie in [0, V) and differ from `blank` (the kernel cannot validate device data: kernels.ctc_fwd checks on request; a
+ *   label outside the vocabulary reads nothing and yields NaN).  0 <= blank < V.
+ *   Lmax <= 2047 (the recursion keeps the 2 L + 1 states of one time step twice in LDS: 2 x 4099 floats + 4095 flags = 36 KiB of the
+ *   64 KiB a workgroup may hold statically); beyond: CST_ERR_UNSUPPORTED, nothing launched.  Null operands, a bad dtype, T / B / V < 1,
+ *   B > 65535, blank outside [0, V), a stride below V: CST_ERR_BAD_ARG, nothing launched, no output touched.
+ *
+ * cst_ctc_fwd replaces log_softmax(logits.float()) + F.ctc_loss(reduction = "sum") (fairseq/criterions/ctc.py:97-113; likewise
+ *   criterions/ctc_chi.py).  The standard recursion over the extended sequence l' = (blank, l1, blank, ..., blank) of S = 2 L + 1
+ *   states, in log space, in fp32; the skip s - 2 -> s is allowed only when l'_s != blank and l'_s != l'_{s-2}.
+ *   Outputs (fp32, overwritten): nll [B] (+inf for an infeasible utterance, also under zero_infinity); loss [1] = the sum of nll in a
+ *   fixed order (zero_infinity: +inf terms count 0); lse [B, T] = each live frame's log-sum-exp (0 at frames >= input_len[b], whose
+ *   logits are NOT read).  Workspaces kept for backward, [B, T, 2 Lmax + 1] fp32 each, written only at live frames and states:
+ *   emit (the extended labels' log-probabilities), alpha, beta (the forward / backward variables, both INCLUDING the emission at t);
+ *   beta may be NULL when no gradient is wanted — then only alpha runs.  alpha and beta run as two workgroups per utterance in ONE
+ *   launch.  An empty target is legal (all-blank paths).  No atomics: bit-reproducible, and independent of the rest of the batch.
+ * cst_ctc_bwd: dlogits (`dtype`, own strides, every element of the T x B x V box overwritten) = gscale[0] * d loss / d logits, fused
+ *   with the log-softmax backward; at a live frame  softmax(x)[v] - exp(logsumexp_{s: l'_s = v}(alpha_t(s) + beta_t(s)) + nll_b -
+ *   logp_t(v)).  Exactly 0 at frames >= input_len[b] and, under zero_infinity, at every frame of an infeasible utterance; without
+ *   zero_infinity such an utterance's gradient is non-finite (as torch's) and the others are unaffected.  A class's occupancy sum over
+ *   its states has a fixed order (one owner thread per class).  gscale: fp32 device scalar (the upstream gradient; no host read).
+ * cst_ctc_greedy replaces the host copy of the fp32 [B, T, V] log-probabilities and the per-utterance argmax().unique_consecutive()
+ *   loop of criterions/ctc.py:116-160: per utterance the argmax over classes (a tie: the lowest index) of the frames before
+ *   input_len[b], runs of equal ids collapsed, then `blank` dropped.  ids int32 [B, T]: the counts[b] ids of utterance b, then -1;
+ *   counts int32 [B]; argmax_ws int32 [B, T] scratch.
+ * ------------------------------------------------------------------------------------------ */
+int cst_ctc_fwd(const void* logits, int64_t stride_t, int64_t stride_b, const int64_t* targets, int64_t Lmax, const int64_t* target_len,
+                const int64_t* input_len, int64_t blank, int zero_infinity, float* nll, float* loss, float* lse, float* emit, float* alpha,
+                float* beta, int64_t T, int64_t B, int64_t V, int dtype, cst_stream stream);
+int cst_ctc_bwd(const void* logits, int64_t stride_t, int64_t stride_b, const int64_t* targets, int64_t Lmax, const int64_t* target_len,
+                const int64_t* input_len, int64_t blank, int zero_infinity, const float* nll, const float* lse, const float* alpha,
+                const float* beta, const float* gscale, void* dlogits, int64_t dstride_t, int64_t dstride_b, int64_t T, int64_t B,
+                int64_t V, int dtype, cst_stream stream);
+int cst_ctc_greedy(const void* logits, int64_t stride_t, int64_t stride_b, const int64_t* input_len, int64_t blank, int32_t* argmax_ws,
+                   int32_t* ids, int32_t* counts, int64_t T, int64_t B, int64_t V, int dtype, cst_stream stream);
+
+/* ------------------------------------------------------------------------------------------
  * Contrastive term of TripletSTMTContrastiveCriterion.compute_contrastive
  * (criterions/triplet_st_mt_contrastive.py:154-169): a = audio memory, t = text memory, both [B, M, C] batch-major
  * (M <= 64 slots); c[b,i,j] = cosine(a[b,i], t[b,j]) (fp32, eps 1e-8), logits = c / temp with the AUDIO slot as class
@@ -831,11 +877,15 @@ int cst_fbank(const cst_fbank_desc* d, cst_stream stream);
  * cst_wav_info / cst_wav_read_f32 replace soundfile.read(path, dtype="float32", start=, frames=) for 16-bit PCM WAV
  *   (fairseq/data/audio/audio_utils.py:7-55): samples / 32768 as float32, interleaved if multi-channel; nframes < 0 =
  *   to the end; returns frames read or a negative cst_status.  cst_wav_info returns CST_ERR_UNSUPPORTED for non-PCM16.
+ * cst_edit_distance replaces editdistance.eval in the CTC criterion's validation (fairseq/criterions/ctc.py:150-170): the Levenshtein
+ *   distance (insert / delete / substitute, cost 1 each) of two int64 sequences — letters or words mapped to ids by the caller; a or b
+ *   may be NULL when its length is 0; returns the distance or a negative cst_status (a negative length).  O(na nb) time, O(min) space.
  * ------------------------------------------------------------------------------------------ */
 int64_t cst_batch_by_size(const int64_t* num_tokens, int64_t n, int64_t max_tokens, int64_t max_sentences, int32_t bsz_mult,
                           int64_t* batch_sizes);
 int cst_wav_info(const char* path, int32_t* sample_rate, int32_t* channels, int64_t* frames, int32_t* bits);
 int64_t cst_wav_read_f32(const char* path, int64_t start_frame, int64_t nframes, float* out, int64_t capacity_samples);
+int64_t cst_edit_distance(const int64_t* a, int64_t na, const int64_t* b, int64_t nb);
 
 #ifdef __cplusplus
 }
