@@ -298,7 +298,9 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void dec_cross_attn_kernel(const T
         l += sm_l[w * BQ + qi] * f;
         o += sm_o[(w * BQ + qi) * D + dd] * f;
       }
-      DT<T>::st(out + ((int64_t)(b * beam + q0 + qi)) * C + head * D + dd, o / l);
+      // a sentence whose every key is masked has l = 0: its rows come back as +0 (as from the matrix-core kernel), not 0 / 0 — a NaN row
+      // would stay in the state of a replayed graph.  Every other row has l >= 1 (its maximal key counts exp(0)) and the same bits as before.
+      DT<T>::st(out + ((int64_t)(b * beam + q0 + qi)) * C + head * D + dd, l > 0.0f ? o / l : 0.0f);
     }
   }
 }
