@@ -102,6 +102,8 @@ def train_main(argv=None):
     limit_host_threads(int(os.environ.get("LOCAL_WORLD_SIZE", world)))
     device = torch.device("cuda", torch.cuda.current_device())
     torch.manual_seed(args.seed)
+    import numpy as np
+    np.random.seed(args.seed)  # (fairseq_cli/train.py:52: the draws made before the first update — the first batch's crops — follow --seed)
     task = registry.setup_task(args)
     train_ds = task.load_dataset(args.train_subset)
     model = task.build_model(args)

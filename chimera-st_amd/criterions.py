@@ -347,3 +347,98 @@ class CtcCriterion(FairseqCriterion):
     @staticmethod
     def logging_keys():
         return ("loss", "ntokens", "nsentences", "sample_size")
+
+
+@register_criterion("wav2vec")
+class Wav2vecCriterion(FairseqCriterion):
+    """fairseq/criterions/wav2vec_criterion.py, the InfoNCE form.  The contrastive loss is functional.infonce_loss on the model's
+    x / y / negative indices (csrc/w2v_pretrain.hip): no [K + 1, B M, D] targets and no logits tensor; `correct` / `count` come out of
+    the same kernel as two device integers.  Every logged quantity stays on the device — the trainer's one small read brings them to
+    the host together; there is no .item() here."""
+    single_pass = True
+
+    def __init__(self, task, infonce=False, loss_weights=None, log_keys=None):
+        super().__init__(task)
+        if not infonce:
+            raise NotImplementedError("criterion wav2vec without --infonce (the binary cross entropy form) is not built")
+        self.infonce = True
+        self.loss_weights = None if loss_weights is None else [float(w) for w in (eval(loss_weights) if isinstance(loss_weights, str) else loss_weights)]
+        self.log_keys = [] if log_keys is None else list(eval(log_keys) if isinstance(log_keys, str) else log_keys)
+
+    @staticmethod
+    def add_args(parser):
+        parser.add_argument("--infonce", action="store_true", help="cross entropy over the positive and the negatives (InfoNCE)")
+        parser.add_argument("--loss-weights", type=str, default=None, help="weights for additional loss terms (not first one)")
+        parser.add_argument("--log-keys", type=str, default=None, help="output keys to log")
+
+    @classmethod
+    def build_criterion(cls, args, task):
+        return cls(task, getattr(args, "infonce", False), getattr(args, "loss_weights", None), getattr(args, "log_keys", None))
+
+    def forward(self, model, sample, reduce=True):
+        net_output = model(**sample["net_input"])
+        x, y = net_output["x"], net_output["y"]
+        D = x.shape[-1]
+        loss, _, counters = CF.infonce_loss(x.reshape(-1, D), y.reshape(-1, D), net_output["neg_idx"], model.logit_temp)
+        sample_size = x.shape[0] * x.shape[1]  # the masked positions: a host number (the masks are drawn on the host)
+        losses = [loss.detach().clone()]
+        if self.loss_weights is not None:
+            extra = model.get_extra_losses(net_output)
+            weights = self.loss_weights
+            if len(weights) == 1 and len(extra) != 1:
+                weights = [weights[0]] * len(extra)
+            assert len(extra) == len(weights), "%d extra losses, %d --loss-weights" % (len(extra), len(weights))
+            for p, coef in zip(extra, weights):
+                if coef != 0 and p is not None:
+                    p = coef * p.float() * sample_size
+                    loss = loss + p
+                    losses.append(p.detach())
+        logging_output = {"loss": loss.detach(), "ntokens": sample_size, "nsentences": sample["id"].numel() if "id" in sample else x.shape[0],
+                          "sample_size": sample_size, "correct": counters[0], "count": counters[1]}
+        for lk in self.log_keys:
+            if lk in net_output:
+                logging_output[lk] = net_output[lk].detach() if torch.is_tensor(net_output[lk]) else float(net_output[lk])
+        if len(losses) > 1:
+            for i, l in enumerate(losses):
+                logging_output["loss_%d" % i] = l
+        return loss, sample_size, logging_output
+
+    def logging_keys(self):
+        keys = ["loss", "ntokens", "nsentences", "sample_size", "correct", "count"] + list(self.log_keys)
+        if self.loss_weights is not None:
+            keys += ["loss_%d" % i for i in range(1 + len(self.loss_weights))]
+        return tuple(keys)
+
+    @staticmethod
+    def reduce_metrics(logging_outputs):
+        """wav2vec_criterion.py:125-175 as a dictionary: loss (and loss_i) per sample in bits, accuracy = correct / count, the other
+        keys averaged over the logging outputs."""
+        import math
+        tot = lambda k: float(sum(float(log.get(k, 0)) for log in logging_outputs))
+        sample_size = tot("sample_size")
+        out = {"loss": tot("loss") / sample_size / math.log(2), "ntokens": tot("ntokens"), "nsentences": tot("nsentences"),
+               "sample_size": sample_size, "_correct": tot("correct"), "_total": tot("count")}
+        if out["_total"] > 0:
+            out["accuracy"] = round(out["_correct"] / out["_total"], 5)
+        for k in logging_outputs[0]:
+            if k not in ("loss", "ntokens", "nsentences", "sample_size", "correct", "count"):
+                val = tot(k) / len(logging_outputs)
+                out[k] = val / sample_size / math.log(2) if k.startswith("loss") else round(val, 3)
+        return out
+
+    @staticmethod
+    def derived_metrics(out):
+        """What the training log derives from one update's summed scalars: the accuracy and the loss terms per sample in bits."""
+        import math
+        d = {}
+        if out.get("count", 0) > 0:
+            d["accuracy"] = round(out["correct"] / out["count"], 5)
+        ss = max(out.get("sample_size", 1.0), 1.0)
+        for k, v in out.items():
+            if k.startswith("loss_"):
+                d[k] = v / ss / math.log(2)
+        return d
+
+    @staticmethod
+    def logging_outputs_can_be_summed() -> bool:
+        return False

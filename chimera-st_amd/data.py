@@ -662,6 +662,10 @@ class AudioLabelDataset(torch.utils.data.Dataset):
                 self.n_samples.append(int(items[1]))
                 kept.append(i)
         self.labels = None if labels is None else [labels[i] for i in kept]  # (a skipped utterance takes its label line along)
+        # the crop draws have a generator of their own, seeded from numpy's global one HERE (after the driver has seeded that): batches
+        # are collated by a background thread, and draws from the global generator there would race with the trainer's per-update
+        # re-seeding and mask draws — neither the crops nor the masks would be reproducible
+        self._crop_rng = np.random.RandomState(np.random.randint(0, 2 ** 31 - 1))
 
     def __len__(self):
         return len(self.fnames)
@@ -685,7 +689,7 @@ class AudioLabelDataset(torch.utils.data.Dataset):
         diff = len(wav) - target_size
         if diff <= 0:
             return wav
-        start = np.random.randint(0, diff + 1)
+        start = self._crop_rng.randint(0, diff + 1)
         return wav[start:len(wav) - diff + start]
 
     def collater(self, samples):

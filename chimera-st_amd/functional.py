@@ -1305,6 +1305,119 @@ def ctc_greedy(logits, input_len, blank=0):
     return K.ctc_greedy(logits, input_len, int(blank))
 
 
+class _InfoNceFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, y, idx, inv_temp):
+        loss, nll, counters, saved, _ = K.infonce_fwd(x, y, idx, inv_temp)
+        ctx.save_for_backward(*saved)
+        ctx.inv_temp = inv_temp
+        ctx.mark_non_differentiable(nll, counters)
+        return loss[0].clone(), nll, counters
+
+    @staticmethod
+    def backward(ctx, dloss, _nll, _counters):
+        g = dloss.reshape(1).float().contiguous()
+        dx, dy = K.infonce_bwd(ctx.saved_tensors, g, ctx.inv_temp, need_dy=ctx.needs_input_grad[1])
+        return (dx if ctx.needs_input_grad[0] else None), dy, None, None
+
+
+def infonce_loss(x, y, neg_idx, logit_temp):
+    """The contrastive loss of wav2vec2 pre-training on the masked positions: x [N, D] (final_proj), y [N, D] (project_q), neg_idx int32
+    [N, K'] flat row indices of each position's negatives (sample_negatives) -> (loss_sum [differentiable fp32 scalar], nll fp32 [N],
+    counters int32 [2] = (correct, count), both detached).  compute_preds (models/wav2vec/wav2vec2.py:512-525) + F.cross_entropy against
+    class 0 with reduction="sum" (criterions/wav2vec_criterion.py:64-103) without the gathered [K' + 1, N, D] targets or the logits."""
+    return _InfoNceFn.apply(x, y, neg_idx, 1.0 / float(logit_temp))
+
+
+def sample_negatives(B, M, num_negatives, cross_sample_negatives=0, key=None, device="cuda"):
+    """Negatives of B utterances with M masked positions each: int32 [B * M, K + Kx] for infonce_loss.  key: one dropout-site key
+    (rng.next_key() when None), so the draws follow the update's seed like every mask."""
+    if key is None:
+        from . import rng
+        key = rng.next_key()
+    K_, Kx = int(num_negatives), int(cross_sample_negatives)
+    return K.w2v_negatives(key, B, M, K_, Kx, device).view(B * M, K_ + Kx)
+
+
+class _GumbelVqFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, vars_, G, tau, training, key, noise):
+        q, idx, onehot, avg, stats, exph = K.gumbel_vq_fwd(logits, vars_, G, training, key, noise)
+        ctx.save_for_backward(logits.contiguous(), vars_.contiguous(), onehot, avg, exph, noise)
+        ctx.cfg = (G, tau, key, training)
+        ctx.set_materialize_grads(False)  # an output nobody differentiated arrives as None in backward, not as zeros
+        code_ppl = stats[1].clone()
+        ctx.mark_non_differentiable(idx, avg, code_ppl)  # (ONE call: a second one replaces the first's list)
+        return q, stats[0].clone(), code_ppl, idx, avg
+
+    @staticmethod
+    def backward(ctx, dq, dppl, *_):
+        logits, vars_, onehot, avg, exph, noise = ctx.saved_tensors
+        G, tau, key, training = ctx.cfg
+        N, GV = logits.shape
+        V, d = GV // G, vars_.shape[1]
+        if dq is None and dppl is None:
+            return None, None, None, None, None, None, None
+        has_dq = dq is not None
+        if not has_dq:  # only prob_perplexity was differentiated
+            dq = torch.zeros(N, G * d, dtype=logits.dtype, device=logits.device)
+        dq = dq.contiguous()
+        dl = dvars = None
+        if ctx.needs_input_grad[0] and not training:
+            # eval takes the hard argmax of the raw logits: as in the reference, q passes nothing to them there; prob_perplexity would
+            # (softmax of the logits), and that gradient is not built for eval — refused rather than returned as zeros
+            if dppl is not None:
+                raise NotImplementedError("gumbel_vector_quantize: the gradient of prob_perplexity in eval mode is not built; run "
+                                          "evaluation under torch.no_grad() or differentiate q alone")
+            dl = torch.zeros_like(logits)
+        elif ctx.needs_input_grad[0]:
+            gy = torch.empty(N, GV, dtype=logits.dtype, device=logits.device)
+            for g in range(G):  # gy_g [N, V] = dq_g [N, d] vars_g^T: a forward-form product with K = d
+                K.gemm(dq, vars_, gy, N, V, d, a_kmajor=1, b_kmajor=1, lda=G * d, ldb=d, ldc=GV, a_off=g * d, b_off=g * V * d, c_off=g * V,
+                       split_k=1)
+            g1 = (dppl if dppl is not None else torch.zeros((), device=logits.device)).reshape(1).float().contiguous()
+            dl = K.gumbel_vq_bwd(logits, gy, avg, exph, g1, G, 1.0 / tau, key, noise)
+        if ctx.needs_input_grad[1] and has_dq:
+            dvars = torch.empty_like(vars_)
+            for g in range(G):  # d vars_g [V, d] = onehot_g^T dq_g over the N rows: the weight-gradient form, dense and exact in the one-hot
+                K.gemm(onehot, dq, dvars, V, d, N, a_kmajor=0, b_kmajor=0, lda=GV, ldb=G * d, ldc=d, a_off=g * V, b_off=g * d, c_off=g * V * d,
+                       split_k=-1)
+        return dl, dvars, None, None, None, None, None
+
+
+def gumbel_vector_quantize(logits, vars_, groups, tau, training=True, key=None, noise=None):
+    """GumbelVectorQuantizer.forward after its weight_proj (modules/gumbel_vector_quantizer.py:148-199): logits [N, G * V], vars_
+    [G * V, d] -> (q [N, G * d], prob_perplexity, code_perplexity, idx int32 [N, G], avg_probs fp32 [G, V]).  q carries the
+    straight-through gradient of F.gumbel_softmax(hard=True) to the logits and the dense gradient to vars_; prob_perplexity carries
+    the diversity term.  In eval mode (the hard argmax of the raw logits) q still carries the dense gradient to vars_, as the
+    reference's hard_x * vars does, and nothing to the logits; a gradient of prob_perplexity is refused there.  key: one dropout-site key (rng.next_key() when None and training); noise: fp32 [N, G, V] used instead."""
+    if training and key is None and noise is None:
+        from . import rng
+        key = rng.next_key()
+    return _GumbelVqFn.apply(logits, vars_, int(groups), float(tau), bool(training), int(key or 0), noise)
+
+
+class _MeanSquareFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        x = x.contiguous()
+        out = torch.zeros(1, dtype=torch.float32, device=x.device)
+        K.sumsq(x, out)  # fixed-order two-stage reduction: reproducible
+        ctx.save_for_backward(x)
+        return out[0] / x.numel()
+
+    @staticmethod
+    def backward(ctx, g):
+        (x,) = ctx.saved_tensors
+        return (x.float() * (g.float() * (2.0 / x.numel()))).to(x.dtype)
+
+
+def mean_square(x):
+    """x.float().pow(2).mean() — the features_pen of wav2vec2 pre-training (models/wav2vec/wav2vec2.py:537) — through cst_sumsq: no
+    fp32 copy or square of the CNN's output is built."""
+    return _MeanSquareFn.apply(x)
+
+
 class _ContrastiveFn(torch.autograd.Function):
     """compute_contrastive (criterions/triplet_st_mt_contrastive.py:154-169), summed over utterances and text slots."""
 

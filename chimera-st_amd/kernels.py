@@ -933,6 +933,99 @@ def attn_avg_probs(q, k, H, kpm, scale, k_strides=None, out=None, out_row_stride
     return out
 
 
+def w2v_negatives(key, B, M, K, Kx=0, device="cuda"):
+    """cst_w2v_negatives: the negatives of every masked position, int32 [B, M, K + Kx] flat row indices into [B * M] (K from the position's
+    own utterance, Kx from the whole batch), drawn from the counter hash at `key` (rng.next_key()); rng.negatives_numpy is the twin."""
+    out = torch.empty(B, M, K + Kx, dtype=torch.int32, device=device)
+    L.check(L.load().cst_w2v_negatives(int(key) & 0xFFFFFFFF, B, M, K, Kx, L.ptr(out), L.stream_ptr()), "cst_w2v_negatives")
+    return out
+
+
+def infonce_fwd(x, y, idx, inv_temp, want_logits=False):
+    """cst_infonce_fwd (include/cst.h): x, y [N, D] fp32 / bf16, idx int32 [N, K'] -> (loss fp32 [1], nll fp32 [N], counters int32 [2] =
+    (correct, count), saved, logits); `saved` is what infonce_bwd needs, `logits` fp32 [N, K' + 1] only under want_logits (tests)."""
+    if x.dim() != 2 or x.shape != y.shape or x.dtype != y.dtype:
+        raise ValueError("infonce: x and y must be [N, D] of one dtype, got %s %s / %s %s" % (tuple(x.shape), x.dtype, tuple(y.shape), y.dtype))
+    N, D = x.shape
+    if idx.dtype != torch.int32 or idx.dim() != 2 or idx.shape[0] != N:
+        raise ValueError("infonce: idx must be int32 [%d, K'], got %s %s" % (N, idx.dtype, tuple(idx.shape)))
+    x, y, idx = x.contiguous(), y.contiguous(), idx.contiguous()
+    KP = idx.shape[1]
+    dev = x.device
+    f32 = dict(dtype=torch.float32, device=dev)
+    nll, loss, stats = torch.empty(N, **f32), torch.empty(1, **f32), torch.empty(3, N, **f32)
+    counters = torch.empty(2, dtype=torch.int32, device=dev)
+    logits = torch.empty(N, KP + 1, **f32) if want_logits else None
+    flags = workspace(N * 4, dev)
+    lse, nx, ny = stats[0], stats[1], stats[2]
+    L.check(L.load().cst_infonce_fwd(L.ptr(x), L.ptr(y), L.ptr(idx), float(inv_temp), L.ptr(nll), L.ptr(loss), L.ptr(counters), L.ptr(lse),
+                                     L.ptr(nx), L.ptr(ny), L.ptr(flags), L.ptr(logits), N, KP, D, L.dtype_code(x.dtype), L.stream_ptr()),
+            "cst_infonce_fwd")
+    return loss, nll, counters, (x, y, idx, stats), logits
+
+
+def infonce_bwd(saved, gscale, inv_temp, need_dy=True):
+    """cst_infonce_bwd_x, then cst_infonce_bwd_y through the inverted index of the targets: gscale fp32 device scalar [1] -> (dx, dy) in
+    the operands' dtype.  The index is integers only and is built on the device without a host read: a stable sort of the keys
+    cat(0 .. N-1, idx.flatten()) (a row's own positive first, then its draws in ascending (position, j)) and the rows' first places."""
+    x, y, idx, stats = saved
+    N, D = x.shape
+    KP = idx.shape[1]
+    lse, nx, ny = stats[0], stats[1], stats[2]
+    dx = torch.empty_like(x)
+    pairs = torch.empty(N, KP + 1, 2, dtype=torch.float32, device=x.device)
+    code = L.dtype_code(x.dtype)
+    L.check(L.load().cst_infonce_bwd_x(L.ptr(x), L.ptr(y), L.ptr(idx), float(inv_temp), L.ptr(lse), L.ptr(nx), L.ptr(ny), L.ptr(gscale),
+                                       L.ptr(dx), L.ptr(pairs), N, KP, D, code, L.stream_ptr()), "cst_infonce_bwd_x")
+    if not need_dy:
+        return dx, None
+    rows = torch.arange(N + 1, dtype=torch.int32, device=x.device)
+    keys = torch.cat([rows[:N], idx.reshape(-1).clamp(0, N - 1)])
+    skeys, perm = torch.sort(keys, stable=True)
+    offs = torch.searchsorted(skeys, rows, out_int32=True)
+    dy = torch.empty_like(y)
+    L.check(L.load().cst_infonce_bwd_y(L.ptr(x), L.ptr(y), L.ptr(perm), L.ptr(offs), L.ptr(pairs), L.ptr(nx), L.ptr(ny), L.ptr(dy), N, KP, D,
+                                       code, L.stream_ptr()), "cst_infonce_bwd_y")
+    return dx, dy
+
+
+def gumbel_vq_fwd(logits, vars_, G, training, key=0, noise=None):
+    """cst_gumbel_vq_fwd (include/cst.h): logits [N, G * V], vars_ [G * V, d] of one dtype -> (q [N, G * d], idx int32 [N, G], onehot
+    [N, G * V], avg_probs fp32 [G, V], stats fp32 [2] = (prob_perplexity, code_perplexity), exph fp32 [G]).  noise: fp32 [N, G, V] read
+    instead of the counter hash at `key` (tests, fixtures)."""
+    if logits.dim() != 2 or vars_.dim() != 2 or logits.dtype != vars_.dtype or logits.shape[1] != vars_.shape[0] or logits.shape[1] % G:
+        raise ValueError("gumbel_vq: logits [N, G V] and vars [G V, d] of one dtype expected, got %s %s / %s %s, G = %d"
+                         % (tuple(logits.shape), logits.dtype, tuple(vars_.shape), vars_.dtype, G))
+    logits, vars_ = logits.contiguous(), vars_.contiguous()
+    N, GV = logits.shape
+    V, d = GV // G, vars_.shape[1]
+    if noise is not None:
+        if noise.dtype != torch.float32 or noise.numel() != N * GV:
+            raise ValueError("gumbel_vq: noise must be fp32 [%d, %d, %d], got %s %s" % (N, G, V, noise.dtype, tuple(noise.shape)))
+        noise = noise.contiguous()
+    dev = logits.device
+    lib = L.load()
+    q = torch.empty(N, G * d, dtype=logits.dtype, device=dev)
+    onehot = torch.empty(N, GV, dtype=logits.dtype, device=dev)
+    idx = torch.empty(N, G, dtype=torch.int32, device=dev)
+    avg = torch.empty(G, V, dtype=torch.float32, device=dev)
+    stats = torch.empty(2 + G, dtype=torch.float32, device=dev)
+    ws = workspace(max(int(lib.cst_gumbel_vq_workspace(N, G, V)), 4), dev)
+    L.check(lib.cst_gumbel_vq_fwd(L.ptr(logits), L.ptr(vars_), L.ptr(noise), int(key) & 0xFFFFFFFF, int(bool(training)), L.ptr(q), L.ptr(idx),
+                                  L.ptr(onehot), L.ptr(avg), L.ptr(stats), L.ptr(stats[2:]), L.ptr(ws), N, G, V, d,
+                                  L.dtype_code(logits.dtype), L.stream_ptr()), "cst_gumbel_vq_fwd")
+    return q, idx, onehot, avg, stats[:2], stats[2:]
+
+
+def gumbel_vq_bwd(logits, gy, avg, exph, dppl, G, inv_tau, key=0, noise=None):
+    """cst_gumbel_vq_bwd: gy [N, G * V] in the logits' dtype, dppl fp32 device scalar [1] -> d logits [N, G * V]."""
+    N, GV = logits.shape
+    dl = torch.empty_like(logits)
+    L.check(L.load().cst_gumbel_vq_bwd(L.ptr(logits), L.ptr(noise), int(key) & 0xFFFFFFFF, float(inv_tau), L.ptr(gy), L.ptr(avg), L.ptr(exph),
+                                       L.ptr(dppl), L.ptr(dl), N, G, GV // G, L.dtype_code(logits.dtype), L.stream_ptr()), "cst_gumbel_vq_bwd")
+    return dl
+
+
 def sumsq(x, out):
     lib = L.load()
     ws = workspace(lib.cst_sumsq_workspace(), x.device)

@@ -196,6 +196,13 @@ SYMBOLS = [
     ("cst_ctc_bwd", c_int, [c_p, c_i64, c_i64, c_p, c_i64, c_p, c_p, c_i64, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64,
                             c_int, c_p]),
     ("cst_ctc_greedy", c_int, [c_p, c_i64, c_i64, c_p, c_i64, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_int, c_p]),
+    ("cst_w2v_negatives", c_int, [ctypes.c_uint32, c_i64, c_i64, c_i64, c_i64, c_p, c_p]),
+    ("cst_infonce_fwd", c_int, [c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_int, c_p]),
+    ("cst_infonce_bwd_x", c_int, [c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_int, c_p]),
+    ("cst_infonce_bwd_y", c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_int, c_p]),
+    ("cst_gumbel_vq_workspace", c_i64, [c_i64, c_i64, c_i64]),
+    ("cst_gumbel_vq_fwd", c_int, [c_p, c_p, c_p, ctypes.c_uint32, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_int, c_p]),
+    ("cst_gumbel_vq_bwd", c_int, [c_p, c_p, ctypes.c_uint32, c_f, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_int, c_p]),
     ("cst_contrastive_fwd", c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_f, c_int, c_p]),
     ("cst_contrastive_bwd", c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_f, c_int, c_p]),
     ("cst_sumsq_workspace", c_i64, []),

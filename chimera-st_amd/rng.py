@@ -63,6 +63,46 @@ def keep_mask_numpy(key, n, p):
     return half >= u(int(p * 65536.0 + 0.5))
 
 
+def hash_bits_numpy(key, idx):
+    """cst_drop_bits(key, idx) (csrc/cst_common.h): the 32-bit word of the counter hash at the 64-bit counter `idx` (uint64 array)."""
+    u = np.uint64
+    idx = np.asarray(idx, dtype=np.uint64)
+    key = int(key) & _M32
+    key2 = (key * 0x2C1B3C6D + 0x297A2D39) & _M32
+    x = (((idx & u(_M32)) ^ u(key)) + (idx >> u(32)) * u(0x9E3779B1)) & u(_M32)
+    x = (x * u(0x9E3779B1)) & u(_M32)
+    x = ((x ^ (x >> u(15))) + u(key2)) & u(_M32)
+    x = (x * u(0x85EBCA77)) & u(_M32)
+    return x ^ (x >> u(13))
+
+
+def negatives_numpy(key, B, M, K, Kx=0):
+    """cst_w2v_negatives (csrc/w2v_pretrain.hip) in numpy, bit for bit: int32 [B, M, K + Kx] flat row indices into [B * M].  Element e
+    takes the word hash_bits_numpy(key, e); the first K of a position are drawn from its own utterance, r = mulhi(bits, M - 1),
+    r += (r >= m), + b M (never the position itself); the other Kx from the whole batch, r = mulhi(bits, B M - 1), r += (r >= m) — the
+    shift against the TIME index m that sample_negatives applies (models/wav2vec/wav2vec2.py:481-493)."""
+    u = np.uint64
+    KP = K + Kx
+    e = np.arange(B * M * KP, dtype=np.uint64).reshape(B, M, KP)
+    bits = hash_bits_numpy(key, e)
+    m = np.arange(M, dtype=np.uint64)[None, :, None]
+    b = np.arange(B, dtype=np.uint64)[:, None, None]
+    own = (bits * u(max(M - 1, 0))) >> u(32)
+    own = own + (own >= m).astype(np.uint64) + b * u(M)
+    cross = (bits * u(max(B * M - 1, 0))) >> u(32)
+    cross = cross + (cross >= m).astype(np.uint64)
+    j = np.arange(KP)[None, None, :]
+    return np.where(j < K, own, cross).astype(np.int32)
+
+
+def gumbel_uniform_numpy(key, n):
+    """The uniforms behind the Gumbel noise of cst_gumbel_vq_fwd / _bwd for elements [0, n) of the site `key`, exactly: float32
+    u = ((bits >> 9) + 0.5) * 2^-23 with bits = hash_bits_numpy(key, element) — 23 bits, so every value is exact in fp32 and lies in
+    [2^-24, 1 - 2^-24]; the kernels' noise is -log(-log(u)) in fp32."""
+    k = (hash_bits_numpy(key, np.arange(n, dtype=np.uint64)) >> np.uint64(9)).astype(np.float32)
+    return (k + np.float32(0.5)) * np.float32(2.0 ** -23)
+
+
 def _bits32(key, key2, idx):
     """cst_drop_bits32 (csrc/cst_common.h) on uint64 arrays holding 32-bit values."""
     u = np.uint64

@@ -274,7 +274,7 @@ def synthetic_sample(dictionary, batch_size, audio_lengths, target_lengths, src_
 class AudioPretrainingTask(FairseqTask):
     """tasks/audio_pretraining.py:36-167 with --labels: fine-tuning wav2vec2 on transcripts (criterion ctc, arch wav2vec_ctc).
     <data>/<split>.tsv is the wav2vec manifest, <data>/<split>.<labels> holds one label line per utterance and
-    <data>/dict.<labels>.txt the target dictionary.  Without --labels the reference pre-trains wav2vec2, which is not built."""
+    <data>/dict.<labels>.txt the target dictionary.  Without --labels and with --criterion wav2vec it pre-trains wav2vec2 on the manifest alone (cropped batches)."""
 
     @staticmethod
     def add_args(parser):
@@ -295,7 +295,12 @@ class AudioPretrainingTask(FairseqTask):
     @classmethod
     def setup_task(cls, args, **kwargs):
         if not getattr(args, "labels", None):
-            raise NotImplementedError("wav2vec2 pre-training is not built: the audio_pretraining task needs --labels (CTC fine-tuning)")
+            if getattr(args, "criterion", None) != "wav2vec":
+                raise NotImplementedError("wav2vec2 pre-training is not built: the audio_pretraining task needs --labels (CTC fine-tuning)"
+                                          " — or --criterion wav2vec, which pre-trains")
+            if getattr(args, "enable_padding", False):
+                raise NotImplementedError("--enable-padding is not built for wav2vec2 pre-training: batches are cropped to their shortest utterance")
+            return cls(args)
         target_dictionary = kwargs.pop("target_dictionary", None)
         if target_dictionary is None:
             target_dictionary = Dictionary.load(os.path.join(args.data, "dict.%s.txt" % args.labels))
@@ -303,6 +308,11 @@ class AudioPretrainingTask(FairseqTask):
 
     def load_dataset(self, split, **kwargs):
         from . import data as D
+        if not getattr(self.args, "labels", None):  # pre-training: the manifest alone, every batch cropped to its shortest utterance
+            self.datasets[split] = D.AudioLabelDataset(
+                os.path.join(self.args.data, "%s.tsv" % split), getattr(self.args, "sample_rate", 16000), None, 0, None,
+                max_sample_size=self.args.max_sample_size, min_length=self.args.min_sample_size, pad=False, normalize=self.args.normalize)
+            return self.datasets[split]
         with open(os.path.join(self.args.data, "%s.%s" % (split, self.args.labels)), "r") as f:
             labels = [line for line in f]
         d = self.target_dictionary

@@ -2,8 +2,9 @@
 path: ConvFeatureExtractionModel (:685-763), Wav2Vec2Model.forward features_only branch (:527-586) and
 extract_features (:650-652), TransformerEncoder (:766-861), TransformerSentenceEncoderLayer (:864-959).
 
-Pre-training-only parts (quantizer, negatives sampling) are out of scope;
-their parameters that exist in every checkpoint (mask_emb, project_q, final_proj) are kept so
+The pre-training forward (:527-641, forward_pretrain below: quantizer, negatives, the operands of the fused InfoNCE loss) runs on the
+kernels of csrc/w2v_pretrain.hip; padded batches, --quantize-input, --target-glu, --negatives-from-everywhere and
+--codebook-negatives are refused.  The parameters of the pre-training heads that exist in every checkpoint (mask_emb, project_q, final_proj) are kept so
 state dicts round-trip.  Fine-tuning's time / channel masking (apply_mask :414-452 over
 data_utils.compute_mask_indices) is built for wav2vec2_asr.py: forward(mask=True).
 
@@ -319,11 +320,27 @@ class TransformerEncoder(nn.Module):
 
 @register_model("wav2vec2")
 class Wav2Vec2Model(nn.Module):
-    """wav2vec2.py:33-680, restricted to what extract_features (features_only) touches."""
+    """wav2vec2.py:33-680: the feature path (features_only: fine-tuning, ST) and the pre-training forward on cropped batches."""
 
     @staticmethod
     def add_args(parser):
-        pass
+        """wav2vec2.py:36-300: the architecture and pre-training flags.  No defaults here (base_architecture fills what is absent)."""
+        import argparse
+        S = argparse.SUPPRESS
+        for flag, typ in (("--extractor-mode", str), ("--encoder-layers", int), ("--encoder-embed-dim", int), ("--encoder-ffn-embed-dim", int),
+                          ("--encoder-attention-heads", int), ("--activation-fn", str), ("--dropout", float), ("--attention-dropout", float),
+                          ("--activation-dropout", float), ("--encoder-layerdrop", float), ("--dropout-input", float),
+                          ("--dropout-features", float), ("--final-dim", int), ("--conv-feature-layers", str), ("--logit-temp", float),
+                          ("--feature-grad-mult", float), ("--latent-vars", int), ("--latent-groups", int), ("--latent-dim", int),
+                          ("--latent-temp", str), ("--mask-length", int), ("--mask-prob", float), ("--mask-selection", str),
+                          ("--mask-other", float), ("--mask-min-space", int), ("--mask-channel-length", int), ("--mask-channel-prob", float),
+                          ("--mask-channel-selection", str), ("--mask-channel-other", float), ("--mask-channel-min-space", int),
+                          ("--num-negatives", int), ("--cross-sample-negatives", int), ("--codebook-negatives", int), ("--conv-pos", int),
+                          ("--conv-pos-groups", int)):
+            parser.add_argument(flag, type=typ, default=S)
+        for flag in ("--layer-norm-first", "--quantize-targets", "--quantize-input", "--same-quantizer", "--target-glu", "--conv-bias",
+                     "--no-mask-overlap", "--no-mask-channel-overlap", "--negatives-from-everywhere"):
+            parser.add_argument(flag, action="store_true", default=S)
 
     def __init__(self, args, pretraining_heads=True):
         """pretraining_heads=False: built as the reference leaves the model after remove_pretraining_modules() (wav2vec2.py:678-682) —
@@ -338,6 +355,17 @@ class Wav2Vec2Model(nn.Module):
                                   if self.embed != args.encoder_embed_dim and not args.quantize_input else None)
         self.feature_grad_mult = args.feature_grad_mult
         self.dropout_input_p = getattr(args, "dropout_input", 0)
+        self.dropout_features_p = getattr(args, "dropout_features", 0)
+        self.logit_temp = getattr(args, "logit_temp", 0.1)
+        self.n_negatives = getattr(args, "num_negatives", 100)
+        self.cross_sample_negatives = getattr(args, "cross_sample_negatives", 0)
+        # variants of the pre-training head that are in no published recipe: refused by name, here, not in the middle of an update
+        if getattr(args, "negatives_from_everywhere", False):
+            raise NotImplementedError("--negatives-from-everywhere (negatives sampled from unmasked frames too) is not built")
+        if getattr(args, "codebook_negatives", 0) > 0:
+            raise NotImplementedError("--codebook-negatives > 0 (negatives drawn from the codebook) is not built")
+        if getattr(args, "target_glu", False) and pretraining_heads and getattr(args, "criterion", None) == "wav2vec":
+            raise NotImplementedError("--target-glu (a GLU over the targets and negatives) is not built for pre-training")
         final_dim = args.final_dim if args.final_dim > 0 else args.encoder_embed_dim
         # registration ORDER follows wav2vec2.py:306-420 (post_extract_proj, quantizer, project_q, [input_quantizer, project_inp],
         # mask_emb, encoder, layer_norm, [target_glu], final_proj): model.parameters() order is the index space of the
@@ -349,7 +377,7 @@ class Wav2Vec2Model(nn.Module):
         self.quantizer = self.input_quantizer = self.project_inp = self.target_glu = None
         if getattr(args, "quantize_targets", False):
             vq_dim = args.latent_dim if getattr(args, "latent_dim", 0) > 0 else final_dim
-            self.quantizer = _InertGumbelVectorQuantizer(self.embed, args.latent_vars, args.latent_groups, vq_dim)
+            self.quantizer = GumbelVectorQuantizer(self.embed, args.latent_vars, args.latent_groups, vq_dim, _latent_temp(args))
             self.project_q = Linear(vq_dim, final_dim)
         else:
             self.project_q = Linear(self.embed, final_dim)
@@ -359,9 +387,9 @@ class Wav2Vec2Model(nn.Module):
                 self.input_quantizer = self.quantizer
             else:
                 vq_dim = args.latent_dim if getattr(args, "latent_dim", 0) > 0 else args.encoder_embed_dim
-                self.input_quantizer = _InertGumbelVectorQuantizer(self.embed, args.latent_vars, args.latent_groups, vq_dim)
+                self.input_quantizer = GumbelVectorQuantizer(self.embed, args.latent_vars, args.latent_groups, vq_dim, _latent_temp(args))
             self.project_inp = Linear(vq_dim, args.encoder_embed_dim)
-            raise NotImplementedError("quantize_input wav2vec2 models feed the quantised features to the encoder: not on the ST path")
+            raise NotImplementedError("--quantize-input (the quantised features feed the encoder) is not built, for pre-training or the ST path")
         self.mask_emb = nn.Parameter(torch.FloatTensor(args.encoder_embed_dim).uniform_())
         self.encoder = TransformerEncoder(args)
         self.layer_norm = LayerNorm(self.embed)
@@ -384,23 +412,24 @@ class Wav2Vec2Model(nn.Module):
         """wav2vec2.py:678-682."""
         self.quantizer = self.project_q = self.target_glu = self.final_proj = None
 
-    def draw_masks(self, B, T, host_lens):
+    def draw_masks_host(self, B, T, host_lens):
         """The draws of apply_mask (wav2vec2.py:414-452) from numpy's global generator, in its order: the time mask [B, T] over each
-        utterance's real frames (host_lens: host integers, None without a padding mask), then the channel mask [B, C].  Returns device
-        bool tensors (None where the probability is 0); nothing here waits for the device."""
-        dev = self.mask_emb.device
+        utterance's real frames (host_lens: host integers, None without a padding mask), then the channel mask [B, C] — numpy bool
+        arrays on the host (None where the probability is 0)."""
         tmask = cmask = None
         if self.mask_prob > 0:
-            tmask = torch.from_numpy(compute_mask_indices((B, T), host_lens, self.mask_prob, self.mask_length, self.mask_selection,
-                                                          self.mask_other, min_masks=2, no_overlap=self.no_mask_overlap,
-                                                          min_space=self.mask_min_space)).to(dev, non_blocking=True)
+            tmask = compute_mask_indices((B, T), host_lens, self.mask_prob, self.mask_length, self.mask_selection, self.mask_other,
+                                         min_masks=2, no_overlap=self.no_mask_overlap, min_space=self.mask_min_space)
         if self.mask_channel_prob > 0:
-            C = self.mask_emb.numel()
-            cmask = torch.from_numpy(compute_mask_indices((B, C), None, self.mask_channel_prob, self.mask_channel_length,
-                                                          self.mask_channel_selection, self.mask_channel_other,
-                                                          no_overlap=self.no_mask_channel_overlap,
-                                                          min_space=self.mask_channel_min_space)).to(dev, non_blocking=True)
+            cmask = compute_mask_indices((B, self.mask_emb.numel()), None, self.mask_channel_prob, self.mask_channel_length,
+                                         self.mask_channel_selection, self.mask_channel_other, no_overlap=self.no_mask_channel_overlap,
+                                         min_space=self.mask_channel_min_space)
         return tmask, cmask
+
+    def draw_masks(self, B, T, host_lens):
+        """draw_masks_host as device bool tensors; nothing here waits for the device."""
+        dev = self.mask_emb.device
+        return tuple(None if m is None else torch.from_numpy(m).to(dev, non_blocking=True) for m in self.draw_masks_host(B, T, host_lens))
 
     def apply_mask(self, x, tmask, cmask):
         """x[tmask] = mask_emb; x[:, :, cmask] = 0 (wav2vec2.py:429, :450) as where-compositions: a boolean index_put would wait for
@@ -417,8 +446,19 @@ class Wav2Vec2Model(nn.Module):
         base_architecture(args)
         return cls(args)
 
-    def forward(self, source, padding_mask=None, mask=True, features_only=False):
-        assert features_only, "only the features_only path is built: wav2vec2 pre-training is out of scope (SURVEY §2.1 #2)"
+    def set_num_updates(self, num_updates):
+        """The quantizers' Gumbel temperature follows the update count (the reference's walk over the children, fairseq_model.py)."""
+        for m in (self.quantizer, self.input_quantizer):
+            if m is not None:
+                m.set_num_updates(num_updates)
+
+    def forward(self, source, padding_mask=None, mask=True, features_only=False, mask_indices=None, neg_idxs=None, noise=None):
+        """features_only: the feature path (fine-tuning, ST).  Otherwise the pre-training forward (wav2vec2.py:527-641), see
+        forward_pretrain; mask_indices / neg_idxs / noise replay recorded draws (tests, fixtures)."""
+        if not features_only:
+            return self.forward_pretrain(source, padding_mask, mask_indices, neg_idxs, noise)
+        if mask_indices is not None or neg_idxs is not None or noise is not None:
+            raise ValueError("mask_indices / neg_idxs / noise replay the draws of the pre-training forward; the feature path takes none")
         if self.training:
             # pre-training-only parameters never receive a gradient on this path: without this the gradient bucket that holds
             # final_proj (the FIRST wav2vec2 bucket in backward order) would wait for finish() and un-overlap every later one
@@ -475,6 +515,86 @@ class Wav2Vec2Model(nn.Module):
     def extract_features(self, source, padding_mask, mask=False):
         res = self.forward(source, padding_mask, mask=mask, features_only=True)
         return res["x"], res["padding_mask"]
+
+    def forward_pretrain(self, source, padding_mask=None, mask_indices=None, neg_idxs=None, noise=None):
+        """wav2vec2.py:527-641 on cropped batches (no padding mask).  The masked positions are known on the host (the masks are drawn
+        there, the same number per utterance), so x and y are gathered by index without a device read.  Returns the operands of the
+        fused contrastive loss instead of logits — x = final_proj(encoder output) and y = project_q(quantised targets) at the masked
+        positions, both [B, M, final_dim], and neg_idx int32 [B * M, K'] — plus features_pen, and with a quantizer num_vars /
+        code_perplexity / prob_perplexity / temp.  get_logits builds the reference's [B * M, K' + 1] logits from them on request."""
+        if padding_mask is not None:
+            raise NotImplementedError("wav2vec2 pre-training on padded batches (--enable-padding) is not built: batches are cropped")
+        if self.final_proj is None or self.project_q is None:
+            raise RuntimeError("this wav2vec2 model was built without its pre-training heads")
+        B, T = source.shape[0], self.feature_extractor.output_length(source.shape[1])
+        dev = source.device
+        cmask = None
+        if mask_indices is None:
+            assert self.mask_prob > 0, "pre-training needs --mask-prob > 0"
+            host, cmask = self.draw_masks_host(B, T, None)
+            tmask = torch.from_numpy(host).to(dev, non_blocking=True)
+            cmask = None if cmask is None else torch.from_numpy(cmask).to(dev, non_blocking=True)
+        else:
+            host = np.asarray(mask_indices.cpu() if torch.is_tensor(mask_indices) else mask_indices, dtype=bool)
+            tmask = torch.from_numpy(host).to(dev, non_blocking=True)
+        per_row = host.sum(1)
+        M = int(per_row[0])
+        assert (per_row == M).all() and M > 0, "the time masks must cover the same number of frames in every utterance"
+        pos = torch.from_numpy(np.flatnonzero(host.reshape(-1))).to(dev, non_blocking=True)
+        self.last_plan = None
+        feats = self.feature_extractor(source, None)
+        if self.feature_grad_mult <= 0:
+            feats = feats.detach()
+        elif self.feature_grad_mult != 1.0:
+            feats = _GradMultiply.apply(feats, self.feature_grad_mult)
+        features_pen = CF.mean_square(feats)  # (:537, on the CNN's output)
+        feats = self.layer_norm(feats)
+        unmasked = feats
+        if self.post_extract_proj is not None:
+            feats = self.post_extract_proj(feats)
+        if self.training and self.dropout_input_p > 0:
+            feats = CF.dropout(feats, self.dropout_input_p)
+        if self.training and self.dropout_features_p > 0:
+            unmasked = CF.dropout(unmasked, self.dropout_features_p)
+        x = self.apply_mask(feats, tmask, cmask)
+        y = unmasked.reshape(B * T, -1).index_select(0, pos)
+        x, _ = self.encoder(x, padding_mask=None, plan=None)
+        x = x.reshape(B * T, -1).index_select(0, pos)
+        result = {"padding_mask": None, "features_pen": features_pen, "mask_indices": tmask}
+        if self.quantizer is not None:
+            q = self.quantizer(y.view(B, M, -1), produce_targets=True, noise=noise)
+            y = q["x"].reshape(B * M, -1)
+            result.update(num_vars=q["num_vars"], code_perplexity=q["code_perplexity"], prob_perplexity=q["prob_perplexity"], temp=q["temp"],
+                          quantizer_targets=q["targets"])
+        y = self.project_q(y)
+        x = self.final_proj(x)
+        if neg_idxs is None:
+            neg_idxs = CF.sample_negatives(B, M, self.n_negatives, self.cross_sample_negatives, device=dev)
+        else:
+            neg_idxs = torch.as_tensor(neg_idxs).to(dev).to(torch.int32).reshape(B * M, -1)
+        result.update(x=x.view(B, M, -1), y=y.view(B, M, -1), neg_idx=neg_idxs)
+        return result
+
+    def get_logits(self, net_output):
+        """The reference's logits [B * M, K' + 1] (positive first, -inf where a negative equals it) in fp32: built on request only —
+        the training path (criterion wav2vec) goes through functional.infonce_loss and never has them."""
+        x, y = net_output["x"], net_output["y"]
+        D = x.shape[-1]
+        return K.infonce_fwd(x.reshape(-1, D).detach(), y.reshape(-1, D).detach(), net_output["neg_idx"], 1.0 / self.logit_temp,
+                             want_logits=True)[4]
+
+    def get_targets(self, sample, net_output, expand_steps=True):
+        x = net_output["x"]
+        return x.new_zeros(x.shape[0] * x.shape[1], dtype=torch.long)
+
+    def get_extra_losses(self, net_output):
+        """(:665-676) the diversity loss where there is a quantizer, then the feature penalty."""
+        pen = []
+        if "prob_perplexity" in net_output:
+            pen.append((net_output["num_vars"] - net_output["prob_perplexity"]) / net_output["num_vars"])
+        if "features_pen" in net_output:
+            pen.append(net_output["features_pen"])
+        return pen
 
 
 def compute_mask_indices(shape, lengths, mask_prob, mask_length, mask_type="static", mask_other=0.0, min_masks=0, no_overlap=False,
@@ -535,21 +655,59 @@ def compute_mask_indices(shape, lengths, mask_prob, mask_length, mask_type="stat
     return mask
 
 
-class _InertGumbelVectorQuantizer(nn.Module):
-    """Parameter shapes of modules/gumbel_vector_quantizer.py:12-76 (combine_groups=False, weight_proj_depth=1): `vars`
-    [1, groups * num_vars, vq_dim / groups] and `weight_proj` Linear(dim, groups * num_vars).  Pre-training only (the
-    contrastive targets): never called on the ST path."""
+class GumbelVectorQuantizer(nn.Module):
+    """modules/gumbel_vector_quantizer.py (combine_groups=False, weight_proj_depth=1, time_first): `vars` [1, groups * num_vars,
+    vq_dim / groups] and `weight_proj` Linear(dim, groups * num_vars) — the reference's names, shapes, init and registration order, so
+    its checkpoints load strictly.  forward: the projection is this library's GEMM, everything after it ONE fused call
+    (functional.gumbel_vector_quantize over csrc/w2v_pretrain.hip): the hard choice of l + Gumbel noise (training) or of l (eval), the
+    codebook rows, both perplexities, and in backward the straight-through and diversity gradients.  The noise comes from the
+    dropout counter hash (one site key per call), `noise` (fp32 [B * T, groups, num_vars]) replaces it where a recorded draw is replayed.
+    Pre-training only: nothing on the ST or CTC paths calls it."""
 
-    def __init__(self, dim, num_vars, groups, vq_dim):
+    def __init__(self, dim, num_vars, groups, vq_dim, temp=(2.0, 0.5, 0.999995)):
         super().__init__()
         assert vq_dim % groups == 0
+        self.groups, self.num_vars, self.input_dim = groups, num_vars, dim
         self.vars = nn.Parameter(torch.FloatTensor(1, groups * num_vars, vq_dim // groups).uniform_())
         self.weight_proj = nn.Linear(dim, groups * num_vars)
         nn.init.normal_(self.weight_proj.weight, mean=0, std=1)
         nn.init.zeros_(self.weight_proj.bias)
+        assert len(temp) == 3, temp
+        self.max_temp, self.min_temp, self.temp_decay = (float(t) for t in temp)
+        self.curr_temp = self.max_temp
 
-    def forward(self, *a, **k):
-        raise NotImplementedError("the wav2vec2 quantizer is a pre-training module; the ST path never calls it")
+    def set_num_updates(self, num_updates):
+        self.curr_temp = max(self.max_temp * self.temp_decay ** num_updates, self.min_temp)
+
+    def forward(self, x, produce_targets=False, noise=None):
+        """x [B, T, dim] -> dict(x = the quantised features [B, T, vq_dim], num_vars, code_perplexity, prob_perplexity (device scalars;
+        prob_perplexity carries the diversity gradient), temp, and under produce_targets `targets` int64 [B, T, groups])."""
+        B, T, C = x.shape
+        logits = CF.linear(x.reshape(B * T, C), self.weight_proj.weight, self.weight_proj.bias)
+        q, ppl, cpl, idx, _ = CF.gumbel_vector_quantize(logits, self.vars.view(self.groups * self.num_vars, -1), self.groups, self.curr_temp,
+                                                        training=self.training, noise=noise)
+        result = {"num_vars": self.num_vars * self.groups, "code_perplexity": cpl, "prob_perplexity": ppl, "temp": self.curr_temp,
+                  "x": q.view(B, T, -1)}
+        if produce_targets:
+            result["targets"] = idx.view(B, T, self.groups).long()
+        return result
+
+    def forward_idx(self, x):
+        res = self.forward(x, produce_targets=True)
+        return res["x"], res["targets"]
+
+    def quantize(self, x):
+        """The quantised features alone (the hard choice's codebook rows)."""
+        return self.forward(x)["x"]
+
+
+def _latent_temp(args):
+    """--latent-temp '(start, stop, decay)' as the reference passes it around: a string or a tuple."""
+    t = getattr(args, "latent_temp", None) or (2.0, 0.5, 0.999995)
+    if isinstance(t, str):
+        import ast
+        t = ast.literal_eval(t)
+    return tuple(t)
 
 
 class _GradMultiply(torch.autograd.Function):
@@ -576,6 +734,10 @@ def base_architecture(args):
         logit_temp=0.1, quantize_targets=False, quantize_input=False, same_quantizer=False, feature_grad_mult=1.0,
         latent_vars=320, latent_groups=2, latent_dim=0, dropout_input=0, dropout_features=0, conv_pos=128,
         conv_pos_groups=16, conv_bias=False, target_glu=False,
+        num_negatives=100, cross_sample_negatives=0, codebook_negatives=0, negatives_from_everywhere=False,
+        latent_temp="(2,0.5,0.999995)", mask_length=10, mask_prob=0.65, mask_selection="static", mask_other=0, no_mask_overlap=False,
+        mask_min_space=1, mask_channel_length=10, mask_channel_prob=0, mask_channel_selection="static", mask_channel_other=0,
+        no_mask_channel_overlap=False, mask_channel_min_space=1,
     )
     for k, v in d.items():
         if not hasattr(args, k):

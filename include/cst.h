@@ -38,7 +38,8 @@ extern "C" {
  * 13: cst_score_tokens — scores of given target tokens, --score-reference).  cst_beam_step_lm and cst_lm_fusion_desc were ADDED at 13
  * without a bump: no existing signature or layout changed, and a library without the symbol fails at symbol lookup.  The same holds for
  * cst_lex_desc, cst_lex_workspace, cst_lex_init and cst_beam_step_lex (lexical constraints), added later at 13, and for cst_ctc_fwd,
- * cst_ctc_bwd, cst_ctc_greedy and cst_edit_distance (CTC fine-tuning).
+ * cst_ctc_bwd, cst_ctc_greedy and cst_edit_distance (CTC fine-tuning), and for cst_w2v_negatives, cst_infonce_fwd, cst_infonce_bwd_x and
+ * cst_infonce_bwd_y, cst_gumbel_vq_workspace, cst_gumbel_vq_fwd and cst_gumbel_vq_bwd (the head of wav2vec2 pre-training).
  * cst_version() returns the value the library was built with; chimera-st_amd/lib.py refuses a mismatch. */
 #define CST_ABI_VERSION 13
 
@@ -546,6 +547,84 @@ int cst_ctc_bwd(const void* logits, int64_t stride_t, int64_t stride_b, const in
                 int64_t V, int dtype, cst_stream stream);
 int cst_ctc_greedy(const void* logits, int64_t stride_t, int64_t stride_b, const int64_t* input_len, int64_t blank, int32_t* argmax_ws,
                    int32_t* ids, int32_t* counts, int64_t T, int64_t B, int64_t V, int dtype, cst_stream stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Contrastive head of wav2vec2 pre-training (added at ABI 13 without a bump: no existing signature changed).  Replaces sample_negatives
+ * and compute_preds (fairseq/models/wav2vec/wav2vec2.py:454-525) and the cross entropy of criterions/wav2vec_criterion.py:64-103.  The
+ * reference's [K' + 1, B, M, D] tensor of gathered targets and its [K' + 1, B M] logits are never built: one wave owns one masked
+ * position and reads its K' + 1 target rows by index.  fp32 arithmetic on fp32 / bf16 storage; no float atomics and no host
+ * synchronisation anywhere: every output is bit-reproducible.
+ *
+ * cst_w2v_negatives: out int32 [B, M, K + Kx] = the flat row indices (into [B M]) of each position's negatives.  Element e of `out`
+ *   takes the 32-bit word bits = hash(key, e) of the dropout counter hash (csrc/cst_common.h: cst_drop_bits with e as the pair index).
+ *   j < K (own utterance):  r = mulhi(bits, M - 1);  r += (r >= m);  out = b M + r  — never the position itself.
+ *   j >= K (any utterance): r = mulhi(bits, B M - 1);  r += (r >= m);  out = r      — shifted past the position's TIME index m, which is
+ *   what the reference does (its `tszs`, :481-493), so at b > 0 a cross-sample negative may be the position itself (it is then masked
+ *   by cst_infonce_fwd like any negative equal to its positive).  The reference's cat(dim = 1) + view, which at Kx > 0 hands position m
+ *   draws shifted against OTHER positions, is not reproduced.  Integers only; rng.negatives_numpy restates it bit for bit.
+ *   Refused (CST_ERR_BAD_ARG, nothing launched): null out, B / M < 1, K + Kx < 1, K > 0 with M < 2, Kx > 0 with B M < 2, 2^31 elements.
+ *
+ * Common operands of the three cst_infonce entries: x [N, D] (the final_proj output at the masked positions, N = B M), y [N, D] (the
+ *   project_q output), both `dtype`, contiguous, 16-byte aligned; idx int32 [N, KP] on the device, KP = K + Kx, values in [0, N) (the
+ *   kernels cannot refuse device data: a value outside is clamped into the range); inv_temp = 1 / logit_temp.
+ *   Target j of position p: j = 0 the positive y[p], j >= 1 the negative y[idx[p][j - 1]].
+ *   cos = x.t / (max(|x|, 1e-8) max(|t|, 1e-8)) — the installed torch.cosine_similarity, each norm clamped on its own; logit = cos *
+ *   inv_temp in fp32 (the reference rounds the logits to the storage type first: DESIGN.md); a negative whose row equals the positive's
+ *   row element for element has logit -inf (compute_preds :514-523).
+ *   Refused (CST_ERR_BAD_ARG, nothing launched, nothing touched): null operands, a bad dtype, N / KP / D < 1, D not a multiple of 8 or
+ *   above 1024, KP > 1023, N (KP + 1) >= 2^31, a base that is not 16-byte aligned.
+ * cst_infonce_fwd: nll fp32 [N] = logsumexp_j logit - logit_0 (exactly 0 where every negative is masked); loss fp32 [1] = their sum in
+ *   a fixed tree, in double; counters int32 [2] = (correct, count): count = N, correct = the positions where argmax_j == 0 and not
+ *   argmin_j == 0, ties to the lowest index (wav2vec_criterion.py:97-103).  Kept for backward: lse fp32 [N], nx fp32 [N] = |x_p|,
+ *   ny fp32 [N] = |y_r| (each y row's norm is computed once, in a pre-pass).  flags int32 [N]: scratch.  logits_dbg: NULL on the training
+ *   path; fp32 [N, KP + 1] receives the logits (tests).
+ * cst_infonce_bwd_x: dx (`dtype`, [N, D]) = gscale[0] * d loss / d x; pairs fp32 [N, KP + 1, 2] = per (position, j) the pair
+ *   (gscale[0] * d loss / d cos, cos), which cst_infonce_bwd_y consumes.  gscale: fp32 device scalar (no host read).  The logits are
+ *   recomputed with the forward's operation sequence (equal bits), so only lse / nx / ny are kept between the passes.
+ * cst_infonce_bwd_y: dy (`dtype`, [N, D]) through the inverted index (perm, offs) of the targets: perm int64 [N (KP + 1)] = the STABLE
+ *   argsort of the keys cat(0 .. N-1, idx.flatten()) (value v < N: the positive of position v; else (p, j) = ((v - N) / KP, (v - N) %
+ *   KP + 1)), offs int32 [N + 1] = the first sorted place of each row (offs[N] = N (KP + 1)): row r's list is perm[offs[r] ..
+ *   offs[r + 1]), its own positive first, then the negatives that drew it in ascending (p, j).  The index holds integers only and is
+ *   built on the device (kernels.infonce_bwd: torch's stable sort + searchsorted).  One wave sums a row's list in list order.
+ * ------------------------------------------------------------------------------------------ */
+int cst_w2v_negatives(uint32_t key, int64_t B, int64_t M, int64_t K, int64_t Kx, int32_t* out, cst_stream stream);
+int cst_infonce_fwd(const void* x, const void* y, const int32_t* idx, float inv_temp, float* nll, float* loss, int32_t* counters,
+                    float* lse, float* nx, float* ny, int32_t* flags, float* logits_dbg, int64_t N, int64_t KP, int64_t D, int dtype,
+                    cst_stream stream);
+int cst_infonce_bwd_x(const void* x, const void* y, const int32_t* idx, float inv_temp, const float* lse, const float* nx,
+                      const float* ny, const float* gscale, void* dx, float* pairs, int64_t N, int64_t KP, int64_t D, int dtype,
+                      cst_stream stream);
+int cst_infonce_bwd_y(const void* x, const void* y, const int64_t* perm, const int32_t* offs, const float* pairs, const float* nx,
+                      const float* ny, void* dy, int64_t N, int64_t KP, int64_t D, int dtype, cst_stream stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Gumbel vector quantizer of wav2vec2 pre-training (added at ABI 13 without a bump).  Replaces GumbelVectorQuantizer.forward after its
+ * weight_proj (fairseq/modules/gumbel_vector_quantizer.py:148-199): the argmax / scatter one-hot, F.gumbel_softmax(hard = True), the
+ * two perplexities and the [N, G V, 1] * vars product, and their autograd.  One wave owns one (row, group); V <= 1024 codes per group.
+ *   logits `dtype` [N, G V] contiguous (the weight_proj output); vars `dtype` [G V, d] (the codebook, groups not combined), d % 8 == 0.
+ *   Noise of element e = (n G + g) V + v: g_e = -log(-log u), u = ((bits >> 9) + 0.5) 2^-23, bits = the counter hash of (key, e)
+ *   (cst_drop_bits) — 23 bits: u is exact in fp32 and never 1; rng.gumbel_uniform_numpy restates u exactly.  noise != NULL (fp32
+ *   [N, G, V]) is read instead.
+ * cst_gumbel_vq_fwd: k = argmax_v (l_v + g_v) when training, argmax_v l_v otherwise, ties to the lowest index.  Writes q `dtype` [N, G d]
+ *   = vars[g V + k] (a copy: exact), idx int32 [N, G], onehot `dtype` [N, G V] (the hard choice; the weight-gradient GEMM's operand),
+ *   avg_probs fp32 [G, V] = the mean over rows of softmax(l) (no noise, no tau: :161-163), stats fp32 [2] = (prob_perplexity,
+ *   code_perplexity) = sum_g exp(-sum_v a log(a + 1e-7)) over avg_probs and over the frequencies of the RAW logits' argmax (:150-166),
+ *   exph fp32 [G] = exp(H_g) of avg_probs.  The sums over rows run as per-workgroup partials (32 rows each) and a second, one-workgroup
+ *   launch that adds them in block order: no atomics.  workspace: cst_gumbel_vq_workspace(N, G, V) bytes.  Nothing is kept for backward.
+ * cst_gumbel_vq_bwd (training): dl `dtype` [N, G V] = (1 / tau) s~ (gy - sum_v s~ gy) + (1 / N) s (h - sum_v s h), with s~ =
+ *   softmax((l + g) / tau) recomputed from the logits and the same noise source, gy `dtype` [N, G, V] = dq . vars^T per group (the
+ *   caller's GEMM), s = softmax(l), h_v = -dppl[0] exph[g] (log(a_v + 1e-7) + a_v / (a_v + 1e-7)); dppl: fp32 device scalar, d loss /
+ *   d prob_perplexity.  d vars = onehot^T dq per group is the caller's weight-gradient GEMM (dense and exact in the one-hot operand; not
+ *   a scatter: code usage is skewed).
+ * Refused (CST_ERR_BAD_ARG, nothing launched, nothing touched): null operands, a bad dtype, N / G / V < 1, V > 1024, d not a multiple
+ *   of 8, 1 / tau <= 0, vars / q not 16-byte aligned.
+ * ------------------------------------------------------------------------------------------ */
+int64_t cst_gumbel_vq_workspace(int64_t N, int64_t G, int64_t V);
+int cst_gumbel_vq_fwd(const void* logits, const void* vars, const float* noise, uint32_t key, int training, void* q, int32_t* idx,
+                      void* onehot, float* avg_probs, float* stats, float* exph, void* workspace, int64_t N, int64_t G, int64_t V, int64_t d,
+                      int dtype, cst_stream stream);
+int cst_gumbel_vq_bwd(const void* logits, const float* noise, uint32_t key, float inv_tau, const void* gy, const float* avg_probs,
+                      const float* exph, const float* dppl, void* dl, int64_t N, int64_t G, int64_t V, int dtype, cst_stream stream);
 
 /* ------------------------------------------------------------------------------------------
  * Contrastive term of TripletSTMTContrastiveCriterion.compute_contrastive
