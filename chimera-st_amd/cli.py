@@ -70,6 +70,9 @@ def validate(trainer, task, args, subset, rank, world):
     derived = getattr(trainer.criterion, "derived_metrics", None)  # criterion `ctc`: uer / wer / raw_wer from the summed error counts
     if derived is not None:
         res.update(derived(out))
+    derived = getattr(task, "derived_metrics", None)  # task `translation` with --eval-bleu: bleu from the summed n-gram statistics
+    if derived is not None:
+        res.update(derived(out))
     return res
 
 
@@ -184,7 +187,8 @@ def train_main(argv=None):
         if not args.disable_validation and epoch % args.validate_interval == 0:
             stats = validate(trainer, task, args, args.valid_subset.split(",")[0], rank, world)
             val = stats.get(args.best_checkpoint_metric, stats.get("loss"))
-            _log(rank, event="valid", epoch=epoch, num_updates=trainer.num_updates, **{k: v for k, v in stats.items()})
+            # (keys with a leading underscore are summed statistics behind a derived metric, as in the reference's progress bar)
+            _log(rank, event="valid", epoch=epoch, num_updates=trainer.num_updates, **{k: v for k, v in stats.items() if not k.startswith("_")})
         files = [] if args.no_epoch_checkpoints else ["checkpoint%d.pt" % epoch]
         better = val is not None and (best is None or (val > best if args.maximize_best_checkpoint_metric else val < best))
         if better:
@@ -371,13 +375,13 @@ def generate_main(argv=None):
     ds = task.load_dataset(args.gen_subset)
     itr = task.get_batch_iterator(ds, max_tokens=args.max_tokens, max_sentences=args.batch_size,
                                   max_positions=(args.max_source_positions, args.max_target_positions), ignore_invalid_inputs=True)
-    if args.score_reference and any(d.tgt_texts is None for d in getattr(ds, "datasets", [ds])):  # before any batch is decoded
+    if args.score_reference and any(getattr(d, "tgt_texts", getattr(d, "tgt", None)) is None for d in getattr(ds, "datasets", [ds])):  # before any batch is decoded
         raise ValueError("--score-reference needs the references of subset %s: it has no target text" % args.gen_subset)
     lm = None
     if args.lm_path is not None:  # fairseq_cli/generate.py:112-128: one LM over the target dictionary
         lm = checkpoint_utils.load_language_model(args.lm_path, task.target_dictionary).to("cuda", dtype).eval()
     gen = task.build_generator(models, args, extra_gen_cls_kwargs={"lm_model": lm, "lm_weight": args.lm_weight})
-    tgt_dict = task.target_dictionary
+    tgt_dict, src_dict = task.target_dictionary, task.source_dictionary
     lexical = None
     if args.constraints is not None:
         from .lexical_constraints import pack_constraints
@@ -398,6 +402,9 @@ def generate_main(argv=None):
         if not sample:
             continue
         ni = sample["net_input"]
+        if "pair_idx" in ni:  # translation task, device-resident corpus (language_pair_dataset.py): the batch from its indices
+            dev = ni["pair_corpus"].materialize(sample)
+            ni, sample = dev["net_input"], dict(sample, target=dev["target"].cpu(), net_input=dev["net_input"])
         if "src_audio" in ni:  # fbank route (data.py): filter banks of the audio batch, computed on the device
             ni = fbank.materialize({k: (v.cuda() if torch.is_tensor(v) else v) for k, v in ni.items()},
                                    max_frames=int(ni["src_lengths"].max()))
@@ -420,8 +427,13 @@ def generate_main(argv=None):
         if lexical is not None:  # interactive.py:188-197: the batch's constraints, packed
             packed = pack_constraints([lexical[i] for i in sample["id"].tolist()], pad=tgt_dict.pad(), eos=tgt_dict.eos())
         results = task.inference_step(gen, models, s, prefix_tokens=prefix, constraints=packed)
+        src_text = None
+        if not args.quiet and src_dict is not None and not src.is_floating_point():  # text input: the S- lines of fairseq-generate
+            src_text = [src_dict.string(row) for row in src.tolist()]
         for i, sid in enumerate(sample["id"].tolist()):
             ref = tgt_dict.string(sample["target"][i]) if sample.get("target") is not None else None
+            if src_text is not None:
+                print("S-%d\t%s" % (sid, src_text[i]), file=out)
             if not args.quiet and ref is not None:
                 print("T-%d\t%s" % (sid, ref), file=out)
             if not args.quiet and lexical is not None:  # interactive.py:257-260

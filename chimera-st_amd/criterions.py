@@ -9,6 +9,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import functional as CF
+from .dictionary import post_process  # noqa: F401  (data/data_utils.py:340-351; the ctc criterion's WER and its tests use it from here)
 from .distributed import notify_unused_parameters
 from .registry import register_criterion
 
@@ -225,21 +226,6 @@ class TripletSTMTContrastiveCriterion(LabelSmoothedCrossEntropyCriterion):
     def logging_keys():
         return ("loss", "nll_loss", "st_loss", "st_nll_loss", "mt_loss", "mt_nll_loss", "contrastive_loss", "ntokens", "nsentences",
                 "sample_size")
-
-
-def post_process(sentence, symbol):
-    """data/data_utils.py:340-351."""
-    if symbol == "sentencepiece":
-        sentence = sentence.replace(" ", "").replace("▁", " ").strip()
-    elif symbol == "wordpiece":
-        sentence = sentence.replace(" ", "").replace("_", " ").strip()
-    elif symbol == "letter":
-        sentence = sentence.replace(" ", "").replace("|", " ").strip()
-    elif symbol == "_EOW":
-        sentence = sentence.replace(" ", "").replace("_EOW", " ").strip()
-    elif symbol is not None and symbol != "none":
-        sentence = (sentence + " ").replace(symbol, "").rstrip()
-    return sentence
 
 
 @register_criterion("ctc")

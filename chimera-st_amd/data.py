@@ -226,10 +226,15 @@ def numpy_seed(seed, *addl_seeds):
         np.random.set_state(state)
 
 
-def batch_by_size(indices, num_tokens_fn, max_tokens=None, max_sentences=None, required_batch_size_multiple=1):
-    """data_utils.py:276-337 over the native cst_batch_by_size (the reference's Cython batch_by_size_fast)."""
+def batch_by_size(indices, num_tokens_fn, max_tokens=None, max_sentences=None, required_batch_size_multiple=1, sizes=None):
+    """data_utils.py:276-337 over the native cst_batch_by_size (the reference's Cython batch_by_size_fast).  `sizes`: the samples'
+    token counts in batching order, for a dataset that has them as one array (num_tokens_fn is then not called)."""
     indices = np.asarray(indices, dtype=np.int64)
-    sizes = np.fromiter((num_tokens_fn(int(i)) for i in indices), dtype=np.int64, count=len(indices))
+    if sizes is not None:
+        sizes = np.ascontiguousarray(sizes, dtype=np.int64)
+        assert len(sizes) == len(indices)
+    else:
+        sizes = np.fromiter((num_tokens_fn(int(i)) for i in indices), dtype=np.int64, count=len(indices))
     out = np.empty(max(len(indices), 1), dtype=np.int64)
     lib = L.load()
     nb = lib.cst_batch_by_size(sizes.ctypes.data_as(ctypes.c_void_p), len(indices), -1 if max_tokens is None else int(max_tokens),
@@ -573,7 +578,9 @@ class EpochBatchIterator:
         def gen():
             for b in batches:
                 sample = self.dataset.collater([self.dataset[i] for i in b])
-                if self.pin_memory and sample:
+                # (a record of the resident translation route holds indices only and is staged by the trainer's thread:
+                # language_pair_dataset.ResidentPairs — no HIP call is made for it here)
+                if self.pin_memory and sample and "pair_idx" not in (sample.get("net_input") or {}):
                     sample = _pin(sample)
                 yield sample
         return _buffered(gen(), buffer_size) if buffer_size > 0 else gen()

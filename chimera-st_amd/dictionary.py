@@ -2,6 +2,22 @@
 (e.g. chimera/resources/wmt14-en-de-spm/spm_unigram10000_wave_joint.txt: 9 996 lines + 4 specials = 10 000)."""
 
 
+def post_process(sentence, symbol):
+    """data/data_utils.py:340-351 — --remove-bpe / --eval-bleu-remove-bpe: `sentencepiece`, `wordpiece`, `letter`, `_EOW`, or a
+    continuation marker such as "@@ " that is deleted."""
+    if symbol == "sentencepiece":
+        sentence = sentence.replace(" ", "").replace("▁", " ").strip()
+    elif symbol == "wordpiece":
+        sentence = sentence.replace(" ", "").replace("_", " ").strip()
+    elif symbol == "letter":
+        sentence = sentence.replace(" ", "").replace("|", " ").strip()
+    elif symbol == "_EOW":
+        sentence = sentence.replace(" ", "").replace("_EOW", " ").strip()
+    elif symbol is not None and symbol != "none":
+        sentence = (sentence + " ").replace(symbol, "").rstrip()
+    return sentence
+
+
 class Dictionary:
     def __init__(self, bos="<s>", pad="<pad>", eos="</s>", unk="<unk>"):
         self.symbols, self.count, self.indices = [], [], {}
@@ -44,9 +60,12 @@ class Dictionary:
     def unk(self):
         return self.unk_index
 
-    def string(self, tensor, bpe_symbol=None, escape_unk=False):
-        toks = [self[int(i)] for i in tensor if int(i) not in (self.eos_index, self.pad_index)]
-        return " ".join(toks)
+    def string(self, tensor, bpe_symbol=None, escape_unk=False, extra_symbols_to_ignore=None, unk_string=None):
+        """data/dictionary.py:65-103: eos and pad (and `extra_symbols_to_ignore`) are dropped, the unknown token prints as
+        `unk_string` when given, and `bpe_symbol` is taken out of the joined string (post_process)."""
+        skip = {self.eos_index, self.pad_index} | set(extra_symbols_to_ignore or ())
+        toks = [(unk_string if unk_string is not None and int(i) == self.unk_index else self[int(i)]) for i in tensor if int(i) not in skip]
+        return post_process(" ".join(toks), bpe_symbol)
 
     def encode_line(self, line, add_if_not_exist=True, append_eos=True, reverse_order=False):
         """data/dictionary.py:292-317 with tokenizer.tokenize_line (:12-15): whitespace split -> IntTensor of indices (+ eos)."""

@@ -1110,3 +1110,32 @@ def transpose2d_multi(table):
     """Every matrix of a transpose_table in one launch (cst_transpose2d_multi)."""
     dev, n, total, dt = table[:4]
     L.check(L.load().cst_transpose2d_multi(dev.data_ptr(), n, total, dt, L.stream_ptr()), "cst_transpose2d_multi")
+
+
+TOK_U8, TOK_U16, TOK_I32, TOK_I64 = range(4)  # include/cst.h: cst_tok_dtype
+TOK_BYTES = (1, 2, 4, 8)
+
+
+def collate_pairs(src_stream, tgt_stream, tok_dtype, src_off, tgt_off, idx, S, T, pad, eos, left_pad_source, left_pad_target, out=None):
+    """One translation batch from a device-resident binarised corpus (cst_collate_pairs).  src_stream / tgt_stream: uint8 tensors
+    holding the token streams' BYTES as stored (`tok_dtype` names the element type of both); src_off / tgt_off int64 [N + 1] element
+    offsets; idx int64 [B] sentence indices in row order.  Returns (src_tokens [B, S], src_lengths [B], prev_output_tokens [B, T],
+    target [B, T], buffer): int64 views of ONE buffer (`out`, int64 [B*S + 2*B*T + B], allocated when not given); every word is written."""
+    B, N = idx.numel(), src_off.numel() - 1
+    for t in (src_off, tgt_off, idx):
+        if t.dtype != torch.int64 or not t.is_contiguous():
+            raise ValueError("collate_pairs: offsets and indices must be contiguous int64 tensors")
+    if tgt_off.numel() != N + 1:
+        raise ValueError("collate_pairs: %d source and %d target sentences" % (N, tgt_off.numel() - 1))
+    if src_stream.dtype != torch.uint8 or tgt_stream.dtype != torch.uint8:
+        raise ValueError("collate_pairs: the token streams are passed as their bytes (uint8 tensors)")
+    total = B * S + 2 * B * T + B
+    if out is None:
+        out = torch.empty(total, dtype=torch.int64, device=idx.device)
+    elif out.dtype != torch.int64 or out.numel() != total or not out.is_contiguous():
+        raise ValueError("collate_pairs: out must be a contiguous int64 tensor of %d words" % total)
+    L.check(L.load().cst_collate_pairs(L.ptr(src_stream), L.ptr(tgt_stream), int(tok_dtype), L.ptr(src_off), L.ptr(tgt_off), N, L.ptr(idx),
+                                       B, int(S), int(T), int(pad), int(eos), int(bool(left_pad_source)), int(bool(left_pad_target)),
+                                       L.ptr(out), L.stream_ptr()), "cst_collate_pairs")
+    a, b = B * S, B * S + B * T
+    return out[:a].view(B, S), out[b + B * T:], out[a:b].view(B, T), out[b:b + B * T].view(B, T), out

@@ -227,6 +227,7 @@ SYMBOLS = [
     ("cst_dec_ln_q_cross_attn", c_int, [c_p, c_i64, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_f, c_int, c_p]),
     ("cst_attn_avg_probs", c_int, [c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_f, c_f,
                                    c_int, c_int, c_p]),
+    ("cst_collate_pairs", c_int, [c_p, c_p, c_int, c_p, c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_int, c_int, c_p, c_p]),
 ]
 
 _lib = None

@@ -1,6 +1,7 @@
 """Mirror of the task surface the hot path is called through: fairseq/tasks/fairseq_task.py (build_model :265-281,
 build_criterion :283-298, train_step :414-445, valid_step :447-451, inference_step :453-459, build_generator
-:309-412), fairseq/tasks/speech_to_text.py (:27-154) and fairseq/tasks/triplet.py (:23-241).
+:309-412), fairseq/tasks/speech_to_text.py (:27-154), fairseq/tasks/triplet.py (:23-241) and fairseq/tasks/translation.py (:164-475:
+the MT pre-training stage on binarised parallel text, with BLEU during validation).
 
 Datasets / TSV manifests / audio decoding are a "next" row; this build provides the collater's
 `sample` dict layout (data/audio/triplet_dataset.py:220-234) through `synthetic_sample`, the same shapes the
@@ -268,6 +269,171 @@ def synthetic_sample(dictionary, batch_size, audio_lengths, target_lengths, src_
         sample["src_text"] = collate_tokens(src, pad, eos).to(device)
         sample["src_text_lengths"] = torch.tensor([len(s) for s in src], device=device)
     return sample
+
+
+def eval_bool(x, default=False):
+    """utils.eval_bool: --left-pad-source / --left-pad-target arrive as the strings "True" / "False"."""
+    if x is None:
+        return default
+    if isinstance(x, bool):
+        return x
+    if str(x) in ("True", "False"):
+        return str(x) == "True"
+    raise ValueError("expected True or False, got %r" % (x,))
+
+
+@register_task("translation")
+class TranslationTask(FairseqTask):
+    """tasks/translation.py:164-475 — parallel text from a binarised directory (indexed_dataset.py, language_pair_dataset.py), and BLEU
+    during validation (--eval-bleu, bleu.py).  The MT pre-training stage of the Chimera recipe (chimera/scripts/train-en2any-MT.sh)."""
+
+    @staticmethod
+    def add_args(parser):
+        """translation.py:187-243, with the two dataset options the reference keeps among its common ones."""
+        parser.add_argument("data", help="path to the binarised data directory")
+        parser.add_argument("-s", "--source-lang", default=None, metavar="SRC", help="source language")
+        parser.add_argument("-t", "--target-lang", default=None, metavar="TARGET", help="target language")
+        parser.add_argument("--load-alignments", action="store_true", help="(not built)")
+        parser.add_argument("--left-pad-source", default="True", type=str, metavar="BOOL", help="pad the source on the left")
+        parser.add_argument("--left-pad-target", default="False", type=str, metavar="BOOL", help="pad the target on the left")
+        parser.add_argument("--max-source-positions", default=1024, type=int, metavar="N")
+        parser.add_argument("--max-target-positions", default=1024, type=int, metavar="N")
+        parser.add_argument("--upsample-primary", default=1, type=int, help="(values other than 1 are not built)")
+        parser.add_argument("--truncate-source", action="store_true", default=False, help="(not built)")
+        parser.add_argument("--num-batch-buckets", default=0, type=int, metavar="N", help="(values above 0 are not built)")
+        parser.add_argument("--dataset-impl", default=None, metavar="FORMAT", help="mmap (the other implementations are not built)")
+        parser.add_argument("--required-seq-len-multiple", default=1, type=int, metavar="N", help="pad the batch widths to a multiple of N")
+        parser.add_argument("--eval-bleu", action="store_true", help="evaluation with BLEU scores")
+        parser.add_argument("--eval-bleu-detok", type=str, default="space", help="detokenize before computing BLEU: space (off) or moses")
+        parser.add_argument("--eval-bleu-detok-args", type=str, metavar="JSON", help="args for building the detokenizer, if needed")
+        parser.add_argument("--eval-bleu-bpe", type=str, metavar="BPE", default=None, help="sentencepiece")
+        parser.add_argument("--eval-bleu-bpe-path", type=str, metavar="BPE", help="the sentencepiece model")
+        parser.add_argument("--eval-tokenized-bleu", action="store_true", default=False, help="compute tokenized BLEU (what this build always does)")
+        parser.add_argument("--eval-bleu-remove-bpe", nargs="?", const="@@ ", default=None, help="remove BPE before computing BLEU")
+        parser.add_argument("--eval-bleu-args", type=str, metavar="JSON", help='generation args for BLEU scoring, e.g. \'{"beam": 4, "lenpen": 0.6}\'')
+        parser.add_argument("--eval-bleu-print-samples", action="store_true", help="print sample generations during validation")
+        parser.add_argument("--normalize", action="store_true")
+
+    def __init__(self, args, src_dict, tgt_dict):
+        super().__init__(args)
+        self.src_dict, self.tgt_dict = src_dict, tgt_dict
+        self.datasets = {}
+
+    @classmethod
+    def setup_task(cls, args, **kwargs):
+        """translation.py:250-285."""
+        args.left_pad_source = eval_bool(getattr(args, "left_pad_source", "True"), True)
+        args.left_pad_target = eval_bool(getattr(args, "left_pad_target", "False"), False)
+        data = getattr(args, "data", None)
+        if not data:  # a checkpoint whose data directory is not reachable (checkpoint_utils.load_model_ensemble_and_task): ids only
+            d = Dictionary.synthetic(getattr(args, "synthetic_vocab_size", 10000))
+            return cls(args, d, d)
+        from . import language_pair_dataset as P
+        paths = P.split_paths(data)
+        if len(paths) > 1:
+            raise NotImplementedError("several colon-separated data paths (%d given) are not built: the round-robin over data shards of "
+                                      "the reference's translation task; pass one directory" % len(paths))
+        if getattr(args, "source_lang", None) is None or getattr(args, "target_lang", None) is None:
+            args.source_lang, args.target_lang = P.infer_language_pair(paths[0])
+        if args.source_lang is None or args.target_lang is None:
+            raise Exception("Could not infer language pair, please provide it explicitly")
+        src_dict = Dictionary.load(os.path.join(paths[0], "dict.{}.txt".format(args.source_lang)))
+        tgt_dict = Dictionary.load(os.path.join(paths[0], "dict.{}.txt".format(args.target_lang)))
+        assert src_dict.pad() == tgt_dict.pad()
+        assert src_dict.eos() == tgt_dict.eos()
+        assert src_dict.unk() == tgt_dict.unk()
+        return cls(args, src_dict, tgt_dict)
+
+    def load_dataset(self, split, epoch=1, combine=False, **kwargs):
+        """translation.py:287-322.  The split's route of batch assembly (device-resident corpus or host collater) is decided here."""
+        from . import language_pair_dataset as P
+        a = self.args
+        ds = P.load_langpair_dataset(
+            a.data, split, a.source_lang, self.src_dict, a.target_lang, self.tgt_dict, combine=combine,
+            dataset_impl=getattr(a, "dataset_impl", None), upsample_primary=getattr(a, "upsample_primary", 1),
+            left_pad_source=a.left_pad_source, left_pad_target=a.left_pad_target,
+            max_source_positions=getattr(a, "max_source_positions", 1024), max_target_positions=getattr(a, "max_target_positions", 1024),
+            load_alignments=getattr(a, "load_alignments", False), truncate_source=getattr(a, "truncate_source", False),
+            num_buckets=getattr(a, "num_batch_buckets", 0), shuffle=(split != "test"),
+            pad_to_multiple=getattr(a, "required_seq_len_multiple", 1))
+        ds.enable_resident()
+        self.datasets[split] = ds
+        return ds
+
+    def build_model(self, args):
+        """translation.py:333-362: with --eval-bleu also the detokeniser, the BPE and the generator of --eval-bleu-args."""
+        import json
+        import logging
+        from argparse import Namespace
+
+        from . import bleu as B
+        model = super().build_model(args)
+        if getattr(args, "eval_bleu", False):
+            log = logging.getLogger(__name__)
+            assert getattr(args, "eval_bleu_detok", None) is not None, \
+                "--eval-bleu-detok is required if using --eval-bleu; try --eval-bleu-detok=moses (or --eval-bleu-detok=space to disable detokenization)"
+            detok_args = json.loads(getattr(args, "eval_bleu_detok_args", None) or "{}")
+            self.tokenizer = B.build_detokenizer(args.eval_bleu_detok, log, **detok_args)
+            self.bpe = None
+            if getattr(args, "eval_bleu_bpe", None) is not None:
+                from . import data as D
+                self.bpe = D.build_bpe({"bpe": args.eval_bleu_bpe, "sentencepiece_model": getattr(args, "eval_bleu_bpe_path", None)})
+            if not getattr(args, "eval_tokenized_bleu", False):
+                B.note_once(log, "13a", "--eval-bleu: sacrebleu's 13a tokeniser is not available in this build; BLEU is counted on whitespace "
+                            "tokens (as under --eval-tokenized-bleu) and compares between runs of this build only")
+            gen_args = json.loads(getattr(args, "eval_bleu_args", None) or "{}")
+            self.sequence_generator = self.build_generator([model], Namespace(**gen_args))
+        return model
+
+    def decode_for_bleu(self, toks, escape_unk=False):
+        """translation.py:436-451: ids -> text: the dictionary's string without the BPE marker, then the BPE's and the detokeniser's
+        decode.  The unknown token prints as one word that cannot match between hypothesis and reference."""
+        s = self.tgt_dict.string(toks.tolist() if torch.is_tensor(toks) else toks, getattr(self.args, "eval_bleu_remove_bpe", None),
+                                 extra_symbols_to_ignore=(self.tgt_dict.bos(),),
+                                 unk_string=("UNKNOWNTOKENINREF" if escape_unk else "UNKNOWNTOKENINHYP"))
+        if getattr(self, "bpe", None) is not None:
+            s = self.bpe.decode(s)
+        if getattr(self, "tokenizer", None) is not None:
+            s = self.tokenizer.decode(s)
+        return s
+
+    def bleu_strings(self, hyp_tokens, target):
+        """(hypothesis strings, reference strings) of a batch: hyp_tokens a list of id sequences, target the padded [B, T] batch."""
+        pad = self.tgt_dict.pad()
+        hyps = [self.decode_for_bleu(h) for h in hyp_tokens]
+        refs = [self.decode_for_bleu([t for t in row if t != pad], escape_unk=True) for row in target.tolist()]
+        return hyps, refs
+
+    def valid_step(self, sample, model, criterion):
+        """translation.py:364-376: the criterion's log plus the batch's BLEU statistics (summed over batches and ranks by cli.validate)."""
+        loss, sample_size, logging_output = super().valid_step(sample, model, criterion)
+        if getattr(self.args, "eval_bleu", False):
+            from . import bleu as B
+            gen_out = self.inference_step(self.sequence_generator, [model], sample, prefix_tokens=None)
+            hyps, refs = self.bleu_strings([g[0]["tokens"].tolist() for g in gen_out], sample["target"].cpu())
+            if getattr(self.args, "eval_bleu_print_samples", False):
+                import logging
+                logging.getLogger(__name__).info("example hypothesis: " + hyps[0])
+                logging.getLogger(__name__).info("example reference: " + refs[0])
+            logging_output = dict(logging_output)
+            logging_output.update(B.corpus_stats(hyps, refs))
+        return loss, sample_size, logging_output
+
+    def derived_metrics(self, summed):
+        """`bleu` from the summed statistics (translation.py:378-417)."""
+        from . import bleu as B
+        return B.derived_bleu(summed) if getattr(self.args, "eval_bleu", False) else {}
+
+    def max_positions(self):
+        return (getattr(self.args, "max_source_positions", 1024), getattr(self.args, "max_target_positions", 1024))
+
+    @property
+    def source_dictionary(self):
+        return self.src_dict
+
+    @property
+    def target_dictionary(self):
+        return self.tgt_dict
 
 
 @register_task("audio_pretraining")

@@ -966,6 +966,29 @@ int cst_wav_info(const char* path, int32_t* sample_rate, int32_t* channels, int6
 int64_t cst_wav_read_f32(const char* path, int64_t start_frame, int64_t nframes, float* out, int64_t capacity_samples);
 int64_t cst_edit_distance(const int64_t* a, int64_t na, const int64_t* b, int64_t nb);
 
+/* ------------------------------------------------------------------------------------------
+ * Device batch assembly for the `translation` task (added at ABI 13 without a bump, as cst_score_tokens' successors were: a pure
+ * addition).  Replaces LanguagePairDataset.collater on a device-resident binarised corpus: collate() of
+ * fairseq/data/language_pair_dataset.py:16-126 over data_utils.py collate_tokens :34-64.
+ *   src_stream / tgt_stream: the token streams of the split's two .bin files as stored, both of type tok_dtype.
+ *   src_offsets / tgt_offsets: int64 [n_sentences + 1] ELEMENT offsets; sentence i is stream[off[i] .. off[i + 1]).  The caller
+ *     guarantees they are non-decreasing and end at the stream's length (the binding checks this once, at upload).
+ *   idx: int64 [B] sentence indices in the batch's row order (the collater's descending-source-length order is the caller's).
+ *   out: int64 [B*S + 2*B*T + B], 16-byte aligned = src_tokens [B, S] | prev_output_tokens [B, T] | target [B, T] | src_lengths [B].
+ *     Every word is written, padding included: pad outside a sentence, on the left of it when the side's left_pad flag is set;
+ *     prev_output_tokens is the target with eos moved to the front (eos, t[0], .., t[n - 2]).  S / T are the caller's widths (at
+ *     least the batch's longest sentence — rounded up for --required-seq-len-multiple; a longer sentence is truncated to the width).
+ *   An idx outside [0, n_sentences) gives an all-pad row and length 0 and reads no token.
+ * One launch, no atomics, every word a pure function of its index: bit-reproducible.  Token loads are one element wide (sentences
+ * start at any element offset); stores are 16 bytes.
+ * A null operand, a bad tok_dtype, B / S / T / n_sentences < 1, B * (S + 2T + 1) > 2^31, a misaligned out or stream: CST_ERR_BAD_ARG,
+ * nothing is launched.
+ * ------------------------------------------------------------------------------------------ */
+typedef enum { CST_TOK_U8 = 0, CST_TOK_U16 = 1, CST_TOK_I32 = 2, CST_TOK_I64 = 3 } cst_tok_dtype;
+int cst_collate_pairs(const void* src_stream, const void* tgt_stream, int tok_dtype, const int64_t* src_offsets,
+                      const int64_t* tgt_offsets, int64_t n_sentences, const int64_t* idx, int64_t B, int64_t S, int64_t T, int64_t pad,
+                      int64_t eos, int left_pad_source, int left_pad_target, int64_t* out, cst_stream stream);
+
 #ifdef __cplusplus
 }
 #endif
