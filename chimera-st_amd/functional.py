@@ -1016,12 +1016,19 @@ def conv1d_cl(x, weight, bias, stride, pad=0, act=None, prev_z=None, grad_is_dz=
 # 1.5 rounds of the 512 that fit the chip): 2 or 3 slices measured the same as 1 inside the update (64.5-65.8 ms per update in all
 # three settings on one box) — a switch for the tools, default 1
 _POSCONV_DW_SPLIT = int(_os.environ.get("CST_POSCONV_DW_SPLIT", 1))
+# the sliding-window kernels (posconv.hip) are built for 48 channels per group and up to 128 taps
+_POSCONV_WINDOW_CG, _POSCONV_WINDOW_KMAX = 48, 128
 
 
 class _PosConvFn(torch.autograd.Function):
-    """Grouped conv as a batched implicit GEMM.  The input is re-staged GROUP-MAJOR ([B, G, T+k, C/G], one 74 MB copy at
-    B=32) so that for one (utterance, group) the im2col row of frame t is the contiguous window starting at frame t:
-    a plain k-major operand with lda = C/G < K (overlapping rows) — no segmented addressing in the inner loop."""
+    """Grouped conv, two routes with the same bits.
+    bf16 with 48 channels per group (wav2vec2: 768 / 16) and k <= 128: the sliding-window kernels of posconv.hip, which read x / dz
+    in their channels-last layout, keep a workgroup's frame window in LDS and write dw in the parameter's layout — no staging tensors.
+    Everything else, and every call while CST_POSCONV_GEMM is set (read per call: A/B runs and parity tests): a batched implicit GEMM.
+    For it the input is re-staged GROUP-MAJOR ([G, B, T+k, C/G]: a permuting copy of x plus two zero fills, and the same again for
+    dz in the backward pass — 136 us of copies and 22 us of fills per call at B=32, profiles/posconv_before.txt) so that for one
+    (utterance, group) the im2col row of frame t is the contiguous window starting at frame t: a plain k-major operand with
+    lda = C/G < K (overlapping rows) — no segmented addressing in the inner loop."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, groups, lens=None, grad_rows=None, grad_rows_host=None):
@@ -1037,6 +1044,18 @@ class _PosConvFn(torch.autograd.Function):
         cg = C // groups
         padl = k // 2
         Tp = T + k - 1 + (1 if k % 2 == 0 else 0)  # even k: torch pads k//2 both sides, SamePad drops the last output
+        ml = None if lens is None else torch.clamp(lens.to(torch.int32) + padl, max=T).contiguous()
+        window = (x.dtype == torch.bfloat16 and weight.dtype == x.dtype and cg == _POSCONV_WINDOW_CG and k <= _POSCONV_WINDOW_KMAX
+                  and (bias is None or bias.dtype == x.dtype) and not _os.environ.get("CST_POSCONV_GEMM"))
+        ctx.window = window
+        if window:
+            xc = x.contiguous()
+            wg = weight.view(groups, cg, cg, k).permute(0, 1, 3, 2).contiguous()  # [g][co][j][ci]
+            y, z = K.posconv_fwd(xc, wg, bias, groups, ml)
+            ctx.save_for_backward(xc, weight, z)
+            ctx.cfg = (B, T, C, k, groups, cg, padl, Tp)
+            ctx.grad_rows, ctx.grad_rows_host = grad_rows, grad_rows_host
+            return y
         # [G, B, Tp, C/G]: group-major OUTSIDE the batch, so that one group's frames of all utterances are one [B * Tp, C/G] matrix
         # (the weight-gradient GEMM below runs over it with K = every frame of the batch)
         xg = torch.empty(groups, B, Tp, cg, dtype=x.dtype, device=x.device)  # (zero rows around the frames: only those are filled)
@@ -1047,7 +1066,6 @@ class _PosConvFn(torch.autograd.Function):
         y = torch.empty(B, T, C, dtype=x.dtype, device=x.device)
         z = torch.empty_like(y)
         xc = x.contiguous()
-        ml = None if lens is None else torch.clamp(lens.to(torch.int32) + padl, max=T).contiguous()
         K.gemm(xg, wg, y, T, cg, k * cg, a_kmajor=1, b_kmajor=1, lda=cg, ldb=k * cg, ldc=C, batch0=B, batch1=groups,
                sa=(Tp * cg, B * Tp * cg), sb=(0, cg * k * cg), sc=(T * C, cg), bias=bias, sbias=(0, cg), act=L.ACT_GELU,
                aux_out=z, ld_aux_out=C, resid=xc, ld_resid=C, split_k=1, m_len=ml)
@@ -1063,10 +1081,15 @@ class _PosConvFn(torch.autograd.Function):
         dy = dy.contiguous()
         dz = K.act_bwd(dy, z, L.ACT_GELU)
         dx = dw = db = None
+        window = ctx.window and (_POSCONV_DW_SPLIT == 1 or not ctx.needs_input_grad[1])
+        if ctx.window and not window:  # (a split weight gradient is the GEMM route's: rebuild its operand from the saved input)
+            xc = xg
+            xg = torch.zeros(groups, B, Tp, cg, dtype=xc.dtype, device=xc.device)
+            xg[:, :, padl:padl + T] = xc.view(B, T, groups, cg).permute(2, 0, 1, 3)
         # dzg[g, b, lp + t] = dz[b, t, group g], zero rows around it, in the frame stride Tp of xg: the operand of BOTH gradient GEMMs
         lp = k - 1 - padl
         dzg = None
-        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+        if (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]) and not window:
             dzg = torch.empty(groups, B, Tp, cg, dtype=dy.dtype, device=dy.device)
             dzg[:, :, :lp].zero_()
             dzg[:, :, lp + T:].zero_()
@@ -1074,11 +1097,14 @@ class _PosConvFn(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             # dx[m] = dy[m] + sum_j dz[m + padl - j] w_j  = dy[m] + sum_j' dzp[m + j'] wflip[j'],  dzp[(k-1-padl) + t] = dz[t]
             wflip = weight.view(groups, cg, cg, k).flip(3).permute(0, 2, 3, 1).contiguous()  # [g][ci][j'][co]
-            dx = torch.empty(B, T, C, dtype=dy.dtype, device=dy.device)
             gr = ctx.grad_rows
             ml = None if gr is None else torch.clamp(gr.to(torch.int32) + lp, max=T).contiguous()  # (dead tiles: dx = 0 + dy = dy, exactly)
-            K.gemm(dzg, wflip, dx, T, cg, k * cg, a_kmajor=1, b_kmajor=1, lda=cg, ldb=k * cg, ldc=C, batch0=B, batch1=groups,
-                   sa=(Tp * cg, B * Tp * cg), sb=(0, cg * k * cg), sc=(T * C, cg), resid=dy, ld_resid=C, split_k=1, m_len=ml)
+            if window:
+                dx = K.posconv_dx(dz, wflip, dy, groups, ml)
+            else:
+                dx = torch.empty(B, T, C, dtype=dy.dtype, device=dy.device)
+                K.gemm(dzg, wflip, dx, T, cg, k * cg, a_kmajor=1, b_kmajor=1, lda=cg, ldb=k * cg, ldc=C, batch0=B, batch1=groups,
+                       sa=(Tp * cg, B * Tp * cg), sb=(0, cg * k * cg), sc=(T * C, cg), resid=dy, ld_resid=C, split_k=1, m_len=ml)
         if ctx.needs_input_grad[1]:
             # dw[g][co][(j,ci)] = sum_{b,t} dz[b, t, g, co] xg[g, b, t + j, ci]: ONE reduction over the frames of the whole batch per
             # group.  Row kappa = b Tp + t of A is dzg's row kappa + lp (zero for t >= T: the windows that would run from one
@@ -1086,7 +1112,6 @@ class _PosConvFn(torch.autograd.Function):
             # (overlapping mn-major rows, ldb = cg).  (Before: one [cg, k cg] product per (utterance, group) — 600 MB of fp32
             # partial sums written and read back by a sum over the batch.)
             Kr = B * Tp - (k - 1)
-            dwg = torch.empty(groups, cg, k * cg, dtype=torch.float32, device=dy.device)
             if ctx.needs_input_grad[2] and not _os.environ.get("CST_NO_GEMM_COLSUM"):
                 # the bias gradient = column sums of this GEMM's A operand (every dz row is inside its K range, the rest are zeros):
                 # [groups][cg] = channel order (cst_gemm_desc.colsum)
@@ -1117,11 +1142,18 @@ class _PosConvFn(torch.autograd.Function):
                     nxt = torch.clamp(b0 + 1, max=B - 1)
                     stamps = ((t0 < n[b0]) | ((t0 + 64 > Tp) & (b0 + 1 < B) & (n[nxt] > 0))).to(torch.int32)
                 live = (stamps, 1)
-            K.gemm(dzg, xg, dwg, cg, k * cg, Kr, a_kmajor=0, b_kmajor=0, lda=cg, ldb=cg, ldc=k * cg, batch0=1, batch1=groups,
-                   sa=(0, B * Tp * cg), sb=(0, B * Tp * cg), sc=(0, cg * k * cg), a_off=lp * cg, split_k=_POSCONV_DW_SPLIT, colsum=db, k_live=live)
-            dw = dwg.view(groups, cg, k, cg).permute(0, 1, 3, 2).reshape(C, cg, k).to(weight.dtype)
-            if db is not None:
-                db = db.to(weight.dtype)
+            if window:
+                # the same sums in the same order, from the channels-last dz and the saved channels-last input (xg here), written as
+                # [C, C/g, k] in the parameter's dtype
+                dw = K.posconv_dw(dz, xg, groups, k, db, live)
+            else:
+                dwg = torch.empty(groups, cg, k * cg, dtype=torch.float32, device=dy.device)
+                K.gemm(dzg, xg, dwg, cg, k * cg, Kr, a_kmajor=0, b_kmajor=0, lda=cg, ldb=cg, ldc=k * cg, batch0=1, batch1=groups,
+                       sa=(0, B * Tp * cg), sb=(0, B * Tp * cg), sc=(0, cg * k * cg), a_off=lp * cg, split_k=_POSCONV_DW_SPLIT, colsum=db,
+                       k_live=live)
+                dw = dwg.view(groups, cg, k, cg).permute(0, 1, 3, 2).reshape(C, cg, k).to(weight.dtype)
+                if db is not None:
+                    db = db.to(weight.dtype)
         if ctx.needs_input_grad[2] and db is None:
             db = K.colsum(dz.view(B * T, C), weight.dtype)
         return dx, dw, db, None, None, None, None

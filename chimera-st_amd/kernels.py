@@ -605,6 +605,42 @@ def act_bwd(dy, z, act):
     return dx
 
 
+def posconv_fwd(x, wg, bias, groups, m_len=None):
+    """Positional convolution forward on the channels-last input (posconv.hip): x [B,T,C] bf16, wg [g][co][j][ci] -> (y, z)."""
+    B, T, C = x.shape
+    k = wg.shape[2]
+    assert x.is_contiguous() and wg.is_contiguous() and x.dtype == torch.bfloat16 and wg.dtype == x.dtype
+    y = torch.empty_like(x)
+    z = torch.empty_like(x)
+    L.check(L.load().cst_posconv_fwd(L.ptr(x), L.ptr(wg), L.ptr(bias) if bias is not None else None, L.ptr(y), L.ptr(z),
+                                     _per_batch(m_len, B, "gemm_m_len"), B, T, C, groups, k, L.stream_ptr()), "cst_posconv_fwd")
+    return y, z
+
+
+def posconv_dx(dz, wflip, dy, groups, m_len=None):
+    """dx = dy + the transposed convolution of dz: wflip [g][ci][j'][co]."""
+    B, T, C = dz.shape
+    k = wflip.shape[2]
+    assert dz.is_contiguous() and dy.is_contiguous() and wflip.is_contiguous() and dz.dtype == torch.bfloat16
+    dx = torch.empty_like(dz)
+    L.check(L.load().cst_posconv_dx(L.ptr(dz), L.ptr(wflip), L.ptr(dy), L.ptr(dx), _per_batch(m_len, B, "gemm_m_len"),
+                                    B, T, C, groups, k, L.stream_ptr()), "cst_posconv_dx")
+    return dx
+
+
+def posconv_dw(dz, x, groups, k, db=None, k_live=None):
+    """Weight gradient [C, C/groups, k] (the parameter's layout) over every frame of the batch; db ([C], optional) receives the bias gradient."""
+    B, T, C = dz.shape
+    assert dz.is_contiguous() and x.is_contiguous() and dz.dtype == torch.bfloat16 and x.dtype == dz.dtype
+    assert db is None or (db.dtype == dz.dtype and db.numel() == C and db.is_contiguous())
+    dw = torch.empty(C, C // groups, k, dtype=dz.dtype, device=dz.device)
+    Tp = T + k - 1 + (1 if k % 2 == 0 else 0)
+    stamps, epoch = _stamps(k_live, B * Tp - (k - 1), "gemm_k_live")  # (the limits count under the GEMM route's names: same meaning)
+    L.check(L.load().cst_posconv_dw(L.ptr(dz), L.ptr(x), L.ptr(dw), L.ptr(db) if db is not None else None,
+                                    stamps, epoch, B, T, C, groups, k, L.stream_ptr()), "cst_posconv_dw")
+    return dw
+
+
 def act_fwd(x, act):
     assert x.is_contiguous()
     y = torch.empty_like(x)

@@ -149,6 +149,9 @@ SYMBOLS = [
     ("cst_gemm_splits", c_int, [ctypes.POINTER(GemmDesc)]),
     ("cst_reduce_multi", c_int, [ctypes.POINTER(ReduceItem), c_int, c_p]),
     ("cst_gemm", c_int, [ctypes.POINTER(GemmDesc), c_p]),
+    ("cst_posconv_fwd", c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_p]),
+    ("cst_posconv_dx", c_int, [c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_p]),
+    ("cst_posconv_dw", c_int, [c_p, c_p, c_p, c_p, c_p, ctypes.c_uint32, c_i64, c_i64, c_i64, c_i64, c_i64, c_p]),
     ("cst_prof_dump", c_i64, [c_int, ctypes.c_char_p, c_i64]),
     ("cst_gemm_reserve_cus", c_int, [c_int]),
     ("cst_transpose2d", c_int, [c_p, c_p, c_i64, c_i64, c_int, c_p]),

@@ -196,6 +196,22 @@ int cst_gemm_reserve_cus(int n);
 int cst_gemm(const cst_gemm_desc* d, cst_stream stream);
 
 /* ------------------------------------------------------------------------------------------
+ * wav2vec2 positional convolution, sliding-window kernels (posconv.hip): bf16, C = 48 * groups, k <= 128 taps, pad k / 2,
+ * SamePad.  x / dz / dy / y / z / dx are channels-last [B, T, C]; the results have the bits of the cst_gemm route
+ * (functional._PosConvFn).  m_len (int32 [B], device, or NULL): frame blocks from m_len[b] on keep zero accumulators.
+ *   fwd: z = conv(x) + bias, y = x + GELU(z);              w     = [g][co][j][ci]
+ *   dx : dx = dy + sum_j' dz[m - (k - 1 - k / 2) + j'] w;   wflip = [g][ci][j'][co]  (taps reversed)
+ *   dw : dw [C][48][k] (the parameter's layout) and db [C] (or NULL) over all frames of the batch; k_live / k_epoch: the
+ *        stamps of cst_gemm_desc.k_live for the zero-padded frame axis [B][T + k - 1 (+ 1 for even k)], or NULL.
+ * ------------------------------------------------------------------------------------------ */
+int cst_posconv_fwd(const void* x, const void* w, const void* bias, void* y, void* z, const int32_t* m_len, int64_t B, int64_t T,
+                    int64_t C, int64_t groups, int64_t k, cst_stream stream);
+int cst_posconv_dx(const void* dz, const void* wflip, const void* dy, void* dx, const int32_t* m_len, int64_t B, int64_t T,
+                   int64_t C, int64_t groups, int64_t k, cst_stream stream);
+int cst_posconv_dw(const void* dz, const void* x, void* dw, void* db, const uint32_t* k_live, uint32_t k_epoch, int64_t B,
+                   int64_t T, int64_t C, int64_t groups, int64_t k, cst_stream stream);
+
+/* ------------------------------------------------------------------------------------------
  * Fused attention (flash-style, scores never reach HBM) — replaces
  * F.multi_head_attention_forward (modules/multihead_attention.py:155-187) and the in-tree
  * bmm/softmax/bmm branch (:326-361):  O = softmax(scale * Q K^T + masks) V, softmax in fp32.
