@@ -17,7 +17,7 @@
 #include "gemm_common.h"
 #include <vector>
 #include <stdlib.h>
-#include <string>
+#include <string.h>
 #include <type_traits>
 
 namespace {
@@ -836,8 +836,7 @@ int launch(GemmParams p, int64_t M, int64_t N, int64_t nbatch, hipStream_t s) {
   }
   p.tiles_m = (int)cst_ceil_div(M, C::BM);
   p.tiles_n = (int)cst_ceil_div(N, C::BN);
-  static const bool no_split_order = getenv("CST_GEMM_NO_SPLIT_ORDER") != nullptr;
-  p.split_order = (p.splits > 1 && nbatch == 1 && !no_split_order) ? 1 : 0;
+  p.split_order = (p.splits > 1 && nbatch == 1) ? 1 : 0;
   dim3 grid(p.tiles_m * p.tiles_n, 1, (unsigned)(nbatch * p.splits));
   if constexpr (!AK && !BK_ && !SEG && C::NT <= 256) {
     if (p.colsum) {
@@ -874,16 +873,75 @@ int launch_glds(GemmParams p, int64_t M, int64_t N, int64_t nbatch, hipStream_t 
   return cst_check_launch("cst_gemm");
 }
 
-// Large tiles when they still give every CU a workgroup (256 CUs, 1 large block each); else the small configuration.
-bool use_large(const cst_gemm_desc* d, int splits) {
-  if ((d->a_kmajor && d->a_seg) || (d->b_kmajor && d->b_seg)) return false;
-  const int64_t tiles = cst_ceil_div(d->M, 256) * cst_ceil_div(d->N, 256) * d->batch0 * d->batch1 * splits;
-  return d->M >= 256 && d->N >= 256 && tiles >= 200;
+// ---------------------------------------------------------------------------------------
+// Host side.  cst_gemm is: validate -> fill_params -> take_route (gemm_route + what depends on it) -> credited_work -> launch_route ->
+// finish.  gemm_route is the ONE place that decides which kernel serves a descriptor; the queries (cst_gemm_splits,
+// cst_gemm_colsum_is_fused, cst_gemm_workspace, cst_gemm_route) read it too.
+// ---------------------------------------------------------------------------------------
+
+// The dispatcher's environment switches, all read in gemm_switches().  Once per process (at the first call) except force_cfg.
+// (The launchers keep their own: gemm8p.hip CST_GEMM8P_STATIC, CST_GEMM8P_NO_HALVES — per launch — and CST_GEMM_RESERVE_CUS;
+//  cst_gemm4w_supported CST_GEMM_4W_MAXTILES.)
+struct GemmSwitches {
+  bool no_klive;          // CST_GEMM_NO_KLIVE: ignore k_live / m_live / k_len / m_len, i.e. visit the all-zero blocks too (A/B runs)
+  int group_m;            // CST_GEMM8P_GROUP_M: m tiles per group of the persistent kernel's XCD-local tile walk (default 4, see below)
+  bool no_narrow;         // CST_GEMM_NO_NARROW: no 128 x 64 / 64 x 128 tiles for narrow problems (tools/bench_posconv.py)
+  bool no_4w;             // CST_GEMM_NO_4W: the persistent 8-wave kernel also where gemm4w.hip is the default (A/B runs: same bits)
+  bool experiment;        // CST_GEMM_EXPERIMENT: the hook of the next line is on
+  const char* force_cfg;  // CST_GEMM_FORCE_CFG, read PER CALL (tests and tools/bench_gemm_*.py toggle it in-process): see kForced
+};
+
+GemmSwitches gemm_switches() {
+  static const GemmSwitches once = [] {
+    GemmSwitches w;
+    w.no_klive = getenv("CST_GEMM_NO_KLIVE") != nullptr;
+    // 4 (a 4 x 8 patch of concurrent tiles per XCD) measured 2-8 % faster than 8 on the N = 768 / 2304 / 3072 Linear shapes at
+    // M = 47 968 (same-box sweep over 2 / 4 / 8 / 16 / 32, tools/bench_gemm4w.py)
+    const char* gm = getenv("CST_GEMM8P_GROUP_M");
+    w.group_m = gm && atoi(gm) > 0 ? atoi(gm) : 4;
+    w.no_narrow = getenv("CST_GEMM_NO_NARROW") != nullptr;
+    w.no_4w = getenv("CST_GEMM_NO_4W") != nullptr;
+    w.experiment = getenv("CST_GEMM_EXPERIMENT") != nullptr;
+    w.force_cfg = nullptr;
+    return w;
+  }();
+  GemmSwitches w = once;
+  if (w.experiment) {
+    const char* f = getenv("CST_GEMM_FORCE_CFG");
+    w.force_cfg = f && *f ? f : nullptr;
+  }
+  return w;
 }
 
-bool getenv_no_glds() {
-  static const bool v = getenv("CST_GEMM_NO_GLDS") != nullptr;
-  return v;
+enum class Family { Reg, Dma, Persistent8, FourWave };  // gemm_kernel (register-staged), gemm_glds_kernel (DMA ring), gemm8p.hip, gemm4w.hip
+enum class Tile { Small, Large, Skinny, NarrowN, NarrowM, Big4, Big4N, Unknown };  // from Big4 on: the experiment hook only
+enum class Colsum { None, Fused, Separate };  // cst_gemm_desc.colsum: by-product of the launch's own kernel / the two-launch column sum behind it
+using CfgBig4 = Cfg<256, 256, 2, 2>;   // 4 waves x (128 x 128): tools/bench_gemm_big4.py
+using CfgBig4N = Cfg<256, 192, 2, 2>;  // 128 x 96 wave tiles: N = 768 is 4 tiles
+
+// Every choice the dispatcher makes for one descriptor.  Persistent8 / FourWave have one tile shape and no ring choice: tile and
+// stages are not read for them.
+struct GemmRoute {
+  Family family;
+  Tile tile;
+  bool bf16, ak, bk;  // storage dtype; A / B k-major
+  bool seg;           // the SEG instantiation: only where a k-major operand is segmented (grouped conv with channel-major input);
+                      // mn-major segments are folded into the per-thread base pointer and cost nothing per tile
+  int stages;         // Dma: stages of the LDS ring
+  int splits;         // K slices (1 = no workspace slabs, no reduce launch)
+  Colsum colsum;
+};
+
+struct TileDims { int bm, bn, nt; };
+template <typename C> constexpr TileDims dims_of() { return {C::BM, C::BN, C::NT}; }
+constexpr TileDims kTileDims[] = {dims_of<CfgSmall>(),   dims_of<CfgLarge>(), dims_of<CfgSkinny>(), dims_of<CfgNarrowN>(),  // (in the order of Tile)
+                                  dims_of<CfgNarrowM>(), dims_of<CfgBig4>(),  dims_of<CfgBig4N>(),  {0, 0, 0}};
+
+// Large tiles when they still give every CU a workgroup (256 CUs, 1 large block each); else the small configuration.
+bool use_large(const cst_gemm_desc* d, bool seg, int splits) {
+  if (seg) return false;
+  const int64_t tiles = cst_ceil_div(d->M, 256) * cst_ceil_div(d->N, 256) * d->batch0 * d->batch1 * splits;
+  return d->M >= 256 && d->N >= 256 && tiles >= 200;
 }
 
 int choose_splits(const cst_gemm_desc* d) {
@@ -921,32 +979,123 @@ int choose_splits(const cst_gemm_desc* d) {
   return (int)s;
 }
 
-}  // namespace
+// The experiment hook (CST_GEMM_EXPERIMENT=1): CST_GEMM_FORCE_CFG names ONE configuration for the unbatched, unsegmented bf16
+// launches of a layout.  k/k (unsplit launches only): tools/bench_gemm_cfg.py, one shape through every k/k configuration.  m/m (the dW
+// layouts; the split count comes from the caller's split_k): tools/bench_gemm_cfg_dw.py — its back-to-back launches keep the
+// operands in L2 / Infinity Cache: 64 x 64 tiles with a quarter of the K slices won there (512 x 512 x 4064: 19.9 -> 16.2 us) and
+// LOST inside the update, where the operands come from HBM and the longer K loop per workgroup is exposed (22.4 -> 24.6 us;
+// x 7901: 24.8 -> 35.2): not adopted.
+struct Forced { const char* name; bool kk; Family family; Tile tile; int stages; };
+const Forced kForced[] = {
+    {"small", false, Family::Reg, Tile::Small, 0},     {"narrowm", false, Family::Reg, Tile::NarrowM, 0},
+    {"narrown", false, Family::Reg, Tile::NarrowN, 0}, {"skinny", false, Family::Reg, Tile::Skinny, 0},
+    {"large", false, Family::Reg, Tile::Large, 0},     {"big4r", false, Family::Reg, Tile::Big4, 0},
+    {"skinny4", true, Family::Dma, Tile::Skinny, 4},   {"skinny2", true, Family::Dma, Tile::Skinny, 2},
+    {"small2", true, Family::Dma, Tile::Small, 2},     {"small3", true, Family::Dma, Tile::Small, 3},
+    {"big4", true, Family::Dma, Tile::Big4, 2},        {"big4n", true, Family::Dma, Tile::Big4N, 2},
+    {"big4r", true, Family::Reg, Tile::Big4, 0},       {"large", true, Family::Reg, Tile::Large, 0},
+    {"8p", true, Family::Persistent8, Tile::Large, 0}, {"4w", true, Family::FourWave, Tile::Big4N, 0},
+};
 
-// cst_gemm_desc.colsum is a by-product of the 4-wave register-staged configurations (both operands mn-major: the dW layout); every
-// other launch gets it from the two-launch column sum over A, run by cst_gemm itself behind the GEMM (unbatched problems only).
-static bool colsum_fused(const cst_gemm_desc* d, int splits) {
-  return d->colsum && !d->a_kmajor && !d->b_kmajor && !d->a_seg && !d->b_seg && !use_large(d, splits);
+// Which kernel serves descriptor d.  p: the launch parameters derived from d (fill_params; its splits / ws / colsum fields are not
+// read).  Pure: no HIP call, no operand memory, no state.
+GemmRoute gemm_route(const cst_gemm_desc* d, const GemmParams& p, const GemmSwitches& sw) {
+  GemmRoute r;
+  r.bf16 = d->dtype == CST_BF16;
+  r.ak = d->a_kmajor != 0;
+  r.bk = d->b_kmajor != 0;
+  r.seg = (r.ak && d->a_seg) || (r.bk && d->b_seg);
+  r.stages = 2;
+  r.splits = choose_splits(d);
+  const bool kk = r.ak && r.bk, mm = !r.ak && !r.bk;
+  const bool large = use_large(d, r.seg, r.splits);
+  const int64_t nbatch = d->batch0 * d->batch1;
+  // colsum is a by-product of the 4-wave register-staged configurations (both operands mn-major: the dW layout) — eight more live
+  // VGPRs do not fit the 16-wave one; every other launch gets it from the two-launch column sum over A, run by cst_gemm itself
+  // behind the GEMM (unbatched problems only).
+  r.colsum = !d->colsum ? Colsum::None : (mm && !d->a_seg && !d->b_seg && !large) ? Colsum::Fused : Colsum::Separate;
+  auto take = [&r](Family f, Tile t, int stages = 2) { r.family = f; r.tile = t; r.stages = stages; return r; };
+
+  // narrow problems (the pos-conv GEMMs per (utterance, group)): see CfgNarrowN
+  if (!sw.no_narrow && !r.seg && !large && kk && d->N <= 64 && d->M > 256) return take(Family::Dma, Tile::NarrowN);
+  if (!sw.no_narrow && !r.seg && !large && mm && d->M <= 64 && d->N > 256) return take(Family::Reg, Tile::NarrowM);
+
+  GemmParams q = p;  // what the two persistent kernels' own conditions read
+  q.splits = r.splits;
+  const bool unsplit1 = !r.seg && nbatch == 1 && r.splits == 1;
+  if (sw.force_cfg && r.bf16 && !r.seg && nbatch == 1 && (mm || (kk && r.splits == 1))) {
+    for (const Forced& f : kForced) {
+      if (f.kk != kk || strcmp(f.name, sw.force_cfg) != 0) continue;
+      if (f.family == Family::Persistent8 && !cst_gemm8p_supported(q, r.ak, r.bk, nbatch)) break;
+      if (f.family == Family::FourWave && !cst_gemm4w_supported(q, r.ak, r.bk, nbatch)) break;
+      return take(f.family, f.tile, f.stages);
+    }
+    return take(Family::Reg, Tile::Unknown);  // launch_route reports it
+  }
+
+  // k/k problems of 150-199 tiles of 256 x 256 (7901 x 1536 x 512: 186): the persistent kernel on 3/4 of the CUs still beats 744
+  // workgroups of 128 x 128 (19.5 vs 28.4 us)
+  const bool mid8p = kk && unsplit1 && d->M >= 256 && d->N >= 256 && cst_ceil_div(d->M, 256) * cst_ceil_div(d->N, 256) >= 150;
+  // 64 x 64 tiles on the DMA ring: decode-time problems (M <= 256, see CfgSkinny) and mid-size ones — the Linear layers of the
+  // 512-wide encoder / decoder: few 128 x 128 tiles per CU leave CUs idle; 64 x 64 tiles quadruple the workgroups.
+  // (Below 256 tiles of 128 x 128: -0.3 ms per update, 512 no better than 0.  400 looked better in back-to-back launches with the
+  //  two-stage ring (4064 x 1536 x 512 17.4 -> 15.9 us) and was worse inside the update, where the operands are not L2-warm:
+  //  21.5 -> 24.4 us.)
+  if (kk && unsplit1 && (d->M <= 256 || (!large && !mid8p && cst_ceil_div(d->M, 128) * cst_ceil_div(d->N, 128) < 256))) {
+    // Ring depth: four stages keep 48 KB per workgroup in flight, which is what a decode-step projection (<= 256 rows, a few dozen
+    // workgroups, long K) is bound by; with more workgroups than fit two per CU the LDS they hold is the limit instead — two stages
+    // let five of them share a CU (tools/bench_gemm_cfg.py: 7901 x 512 x 512 14.9 -> 12.1 us, 7901 x 512 x 2048 33.7 -> 28.7,
+    // 12000 x 512 x 512 17.1 -> 15.3; same bits: the K order per output element does not change).
+    const bool two_stage = d->M > 256 && cst_ceil_div(d->M, 64) * cst_ceil_div(d->N, 64) > 512;
+    return take(Family::Dma, Tile::Skinny, two_stage ? 2 : 4);
+  }
+  if (r.bf16 && !r.seg && !d->colsum) {
+    // gemm4w.hip (four waves, pinned issue order, three A stages): long K, N a multiple of 192 — the N = 768 long-K launches of the
+    // step; same bits as the 8-wave kernel, 3-8 % faster inside the update
+    if (!sw.no_4w && cst_gemm4w_supported(q, r.ak, r.bk, nbatch)) return take(Family::FourWave, Tile::Big4N);
+    // gemm8p.hip, the 8-phase DMA-pipelined persistent kernel: bf16 problems that fill the chip with 256 x 256 tiles.  A k-major
+    // only: with an mn-major A the register-staged 16-wave kernel measured 20-30 % faster on the dW shapes (and all layouts on the
+    // persistent kernel measured no better inside the update, profiles/r06_step_jitter.txt).  act'(aux_in) epilogues: taken since
+    // the operand vectors are requested in one burst ahead of the epilogue passes (gemm8p.hip) — with a second operand (resid,
+    // aux_out) the 128 KiB-per-tile operand read is exposed at one workgroup per CU (0.49 vs 0.42 ms): the 16-wave kernel.
+    if (r.ak && (!d->dact || (!d->resid && !d->aux_out)) && (large || mid8p) && cst_gemm8p_supported(q, r.ak, r.bk, nbatch))
+      return take(Family::Persistent8, Tile::Large);
+  }
+  const Tile t = large ? Tile::Large : Tile::Small;
+  if (r.seg) return take(Family::Reg, Tile::Small);
+  // measured on MI355X (tools/bench_kernels.py): the DMA path wins when both operands are k-major (716 vs 661 TF/s, fc1
+  // forward); with an mn-major operand the register-staged path + padded LDS rows is faster (690 vs 649, 562 vs 486).
+  // (Column sums live in gemm_kernel.)
+  return take(kk && !d->colsum ? Family::Dma : Family::Reg, t);
 }
+
+// The route as text (cst_gemm_route): "reg <bf16|f32> <a><b>[ seg] <BM>x<BN> nt<threads>[ colsum] split<s>",
+// "glds <bf16|f32> <a><b> <BM>x<BN> nt<threads> ns<stages> split<s>", "8p <a><b>", "4w"; <a>/<b> = k or m (k-major / mn-major).
+void route_text(const GemmRoute& r, char* out, int64_t n) {
+  const TileDims t = kTileDims[(int)r.tile];
+  const char* dt = r.bf16 ? "bf16" : "f32";
+  const char a = r.ak ? 'k' : 'm', b = r.bk ? 'k' : 'm';
+  switch (r.family) {
+    case Family::Reg:
+      snprintf(out, (size_t)n, "reg %s %c%c%s %dx%d nt%d%s split%d", dt, a, b, r.seg ? " seg" : "", t.bm, t.bn, t.nt,
+               r.colsum == Colsum::Fused ? " colsum" : "", r.splits);
+      break;
+    case Family::Dma: snprintf(out, (size_t)n, "glds %s %c%c %dx%d nt%d ns%d split%d", dt, a, b, t.bm, t.bn, t.nt, r.stages, r.splits); break;
+    case Family::Persistent8: snprintf(out, (size_t)n, "8p %c%c", a, b); break;
+    case Family::FourWave: snprintf(out, (size_t)n, "4w"); break;
+  }
+}
+
+}  // namespace
 
 extern "C" int64_t cst_colsum_workspace(int64_t rows, int64_t cols);
 extern "C" int cst_colsum_typed(const void* x, int64_t ldx, void* out, void* workspace, int64_t rows, int64_t cols, int dtype, int out_dtype, cst_stream stream);
 extern "C" int cst_colsum_typed_live(const void* x, int64_t ldx, void* out, void* workspace, int64_t rows, int64_t cols, int dtype, int out_dtype,
                                      const uint32_t* row_live, uint32_t epoch, cst_stream stream);
 
-extern "C" int cst_gemm_splits(const cst_gemm_desc* d) { return d ? choose_splits(d) : 0; }
+namespace {
 
-extern "C" int cst_gemm_colsum_is_fused(const cst_gemm_desc* d) { return d && colsum_fused(d, choose_splits(d)) ? 1 : 0; }
-
-extern "C" int64_t cst_gemm_workspace(const cst_gemm_desc* d) {
-  const int s = choose_splits(d);
-  const int64_t nb = d->batch0 * d->batch1;
-  int64_t bytes = s > 1 ? (int64_t)s * d->M * d->N * nb * (int64_t)sizeof(float) : 0;
-  if (d->colsum) bytes += colsum_fused(d, s) ? (s > 1 ? (int64_t)s * d->M * nb * (int64_t)sizeof(float) : 0) : cst_colsum_workspace(d->K, d->M);
-  return bytes;
-}
-
-static int gemm_one(const cst_gemm_desc* d, cst_stream stream, int64_t drop_row0) {
+int validate(const cst_gemm_desc* d) {
   CST_REQUIRE(d && d->A && d->B && d->C, "cst_gemm: null operand");
   CST_REQUIRE(d->dtype == CST_F32 || d->dtype == CST_BF16, "cst_gemm: bad dtype %d", d->dtype);
   CST_REQUIRE(d->c_dtype == d->dtype || d->c_dtype == CST_F32, "cst_gemm: c_dtype must be dtype or f32");
@@ -963,7 +1112,14 @@ static int gemm_one(const cst_gemm_desc* d, cst_stream stream, int64_t drop_row0
   CST_REQUIRE(d->sa0 % vec == 0 && d->sa1 % vec == 0 && d->sb0 % vec == 0 && d->sb1 % vec == 0, "cst_gemm: batch strides of A/B must be multiples of %d", vec);
   CST_REQUIRE(d->batch0 >= 1 && d->batch1 >= 1, "cst_gemm: batch counts must be >= 1");
   CST_REQUIRE(!d->dact || d->aux_in, "cst_gemm: dact needs aux_in");
+  CST_REQUIRE(d->drop_p >= 0.0f && d->drop_p < 1.0f, "cst_gemm: drop_p must be in [0, 1)");
+  CST_REQUIRE(d->drop_p == 0.0f || d->batch0 * d->batch1 == 1, "cst_gemm: fused dropout needs an unbatched problem");
+  CST_REQUIRE(!d->colsum || (!d->a_kmajor && !d->a_seg), "cst_gemm: colsum needs an mn-major, unsegmented A");
+  return CST_OK;
+}
 
+// Everything the kernels read that follows from the descriptor alone; take_route adds what follows from the route.
+GemmParams fill_params(const cst_gemm_desc* d, const GemmSwitches& sw) {
   GemmParams p;
   p.M = d->M; p.N = d->N; p.K = d->K;
   p.A = d->A; p.lda = d->lda; p.a_seg = d->a_seg; p.a_seg_stride = d->a_seg_stride;
@@ -975,16 +1131,13 @@ static int gemm_one(const cst_gemm_desc* d, cst_stream stream, int64_t drop_row0
   p.dact = d->dact; p.aux_in = d->aux_in; p.ld_aux_in = d->ld_aux_in;
   p.resid = d->resid; p.ld_resid = d->ld_resid;
   p.alpha = d->alpha;
-  CST_REQUIRE(d->drop_p >= 0.0f && d->drop_p < 1.0f, "cst_gemm: drop_p must be in [0, 1)");
-  CST_REQUIRE(d->drop_p == 0.0f || d->batch0 * d->batch1 == 1, "cst_gemm: fused dropout needs an unbatched problem");
   p.drop_thr = d->drop_p > 0.0f ? cst_drop_thr16(d->drop_p) : 0u;
   p.drop_key = d->drop_key;
   p.drop_scale = d->drop_p > 0.0f ? 1.0f / (1.0f - d->drop_p) : 1.0f;
-  p.drop_row0 = drop_row0;
+  p.drop_row0 = 0;
   p.batch1 = d->batch1;
   p.sa0 = d->sa0; p.sa1 = d->sa1; p.sb0 = d->sb0; p.sb1 = d->sb1; p.sc0 = d->sc0; p.sc1 = d->sc1;
-  p.c_f32 = (d->c_dtype == CST_F32 && d->dtype != CST_F32) ? 1 : 0;
-  if (d->dtype == CST_F32) p.c_f32 = 0;  // T == float already stores fp32
+  p.c_f32 = (d->c_dtype == CST_F32 && d->dtype != CST_F32) ? 1 : 0;  // T == float already stores fp32
   {
     auto al16 = [](const void* q) { return q == nullptr || ((uintptr_t)q % 16) == 0; };
     bool ok = d->ldc % 8 == 0 && d->sc0 % 8 == 0 && d->sc1 % 8 == 0 && al16(d->C) && al16(d->bias) && al16(d->aux_out) && al16(d->aux_in) && al16(d->resid);
@@ -998,219 +1151,183 @@ static int gemm_one(const cst_gemm_desc* d, cst_stream stream, int64_t drop_row0
   p.tiles_m = p.tiles_n = 0;  // set per configuration in launch()
   p.split_order = 0;
   p.sched = nullptr;  // set by the persistent kernel's launcher
-  p.gperm_full = 0;  // (likewise)
+  p.gperm_full = 0;   // (likewise)
   p.mrot = 0;
-  {
-    static const bool no_klive = getenv("CST_GEMM_NO_KLIVE") != nullptr;  // A/B switch: visit the all-zero K blocks too
-    p.k_live = no_klive ? nullptr : d->k_live;
-    p.k_epoch = d->k_epoch;
-    p.m_live = no_klive ? nullptr : d->m_live;
-    p.m_epoch = d->m_epoch;
-    p.k_len = no_klive ? nullptr : d->k_len;
-    p.m_len = no_klive ? nullptr : d->m_len;
-  }
-  {
-    // m tiles per group of the XCD-local tile walk: 4 (a 4 x 8 patch of concurrent tiles per XCD) measured 2-8 % faster than 8 on the
-    // N = 768 / 2304 / 3072 Linear shapes at M = 47 968 (same-box sweep over 2 / 4 / 8 / 16 / 32, tools/bench_gemm4w.py)
-    static const int gm = getenv("CST_GEMM8P_GROUP_M") ? atoi(getenv("CST_GEMM8P_GROUP_M")) : 4;
-    p.group_m = gm > 0 ? gm : 4;
-  }
-  p.splits = choose_splits(d);
+  p.k_live = sw.no_klive ? nullptr : d->k_live;
+  p.k_epoch = d->k_epoch;
+  p.m_live = sw.no_klive ? nullptr : d->m_live;
+  p.m_epoch = d->m_epoch;
+  p.k_len = sw.no_klive ? nullptr : d->k_len;
+  p.m_len = sw.no_klive ? nullptr : d->m_len;
+  p.group_m = sw.group_m;
+  p.splits = 1;
   p.ws = nullptr;
-  CST_REQUIRE(!d->colsum || (!d->a_kmajor && !d->a_seg), "cst_gemm: colsum needs an mn-major, unsegmented A");
-  const bool cs_fused = colsum_fused(d, p.splits);
-  CST_REQUIRE(!d->colsum || cs_fused || (d->batch0 * d->batch1 == 1 && d->M % 8 == 0 && d->lda % 8 == 0),
-              "cst_gemm: colsum of this configuration runs as a separate column sum: unbatched, M and lda multiples of 8");
-  p.colsum = cs_fused ? d->colsum : nullptr;
+  p.colsum = nullptr;
   p.colsum_ws = nullptr;
+  return p;
+}
+
+// Workspace bytes of a route: the split-K slabs, then the column sum's share (the slices' partial sums, or the separate sum's row chunks).
+int64_t route_workspace(const cst_gemm_desc* d, const GemmRoute& r) {
+  const int64_t s = r.splits, nb = d->batch0 * d->batch1;
+  int64_t bytes = s > 1 ? s * d->M * d->N * nb * (int64_t)sizeof(float) : 0;
+  if (r.colsum == Colsum::Fused) bytes += s > 1 ? s * d->M * nb * (int64_t)sizeof(float) : 0;
+  else if (r.colsum == Colsum::Separate) bytes += cst_colsum_workspace(d->K, d->M);
+  return bytes;
+}
+
+// The route of a validated descriptor, the checks that depend on it, and the launch parameters that follow from it.
+int take_route(const cst_gemm_desc* d, const GemmSwitches& sw, GemmParams& p, GemmRoute& r) {
+  r = gemm_route(d, p, sw);
+  const int64_t nbatch = d->batch0 * d->batch1;
+  CST_REQUIRE(r.colsum != Colsum::Separate || (nbatch == 1 && d->M % 8 == 0 && d->lda % 8 == 0),
+              "cst_gemm: colsum of this configuration runs as a separate column sum: unbatched, M and lda multiples of 8");
+  CST_REQUIRE(cst_ceil_div(d->M, 128) * cst_ceil_div(d->N, 128) < (1ll << 31) && nbatch * r.splits < 65536, "cst_gemm: grid too large");
+  p.splits = r.splits;
+  p.colsum = r.colsum == Colsum::Fused ? d->colsum : nullptr;
 #ifdef CST_TRACE
   if (p.splits == 1 && d->workspace) p.ws = (float*)d->workspace;  // cycle-stamp buffer of tools/gemm8p_trace.py
 #endif
-  const int64_t nbatch = d->batch0 * d->batch1;
-  CST_REQUIRE(cst_ceil_div(d->M, 128) * cst_ceil_div(d->N, 128) < (1ll << 31) && nbatch * p.splits < 65536, "cst_gemm: grid too large");
-  if (p.splits > 1) {
-    const int64_t need = cst_gemm_workspace(d);
-    if (!d->workspace || d->workspace_bytes < need) {
-      cst_set_error("cst_gemm: split_k=%d needs %lld workspace bytes, got %lld", p.splits, (long long)need,
-                    (long long)d->workspace_bytes);
-      return CST_ERR_WORKSPACE;
-    }
-    p.ws = (float*)d->workspace;
-    p.colsum_ws = p.ws + (int64_t)p.splits * d->M * d->N * nbatch;
-  } else if (d->colsum && !cs_fused && (!d->workspace || d->workspace_bytes < cst_gemm_workspace(d))) {
-    cst_set_error("cst_gemm: colsum needs %lld workspace bytes, got %lld", (long long)cst_gemm_workspace(d), (long long)d->workspace_bytes);
+  const int64_t need = route_workspace(d, r);
+  if (need > 0 && (!d->workspace || d->workspace_bytes < need)) {
+    if (r.splits > 1) cst_set_error("cst_gemm: split_k=%d needs %lld workspace bytes, got %lld", r.splits, (long long)need, (long long)d->workspace_bytes);
+    else cst_set_error("cst_gemm: colsum needs %lld workspace bytes, got %lld", (long long)need, (long long)d->workspace_bytes);
     return CST_ERR_WORKSPACE;
   }
-  hipStream_t s = (hipStream_t)stream;
-  // Work that is skipped is never credited: with live-tile stamps only the live K blocks count.  The stamps live on the device,
-  // so this costs a synchronous read-back — done only while the profiling table is recording (bench.py's untimed roofline step).
-  double kfrac = 1.0;
-  if (p.k_live && cst_prof_is_on()) {
-    const int64_t nt = cst_ceil_div(d->K, 64);
-    std::vector<uint32_t> st((size_t)nt);
-    if (hipStreamSynchronize(s) == hipSuccess && hipMemcpy(st.data(), p.k_live, sizeof(uint32_t) * nt, hipMemcpyDeviceToHost) == hipSuccess) {
+  if (r.splits > 1) {
+    p.ws = (float*)d->workspace;
+    p.colsum_ws = p.ws + (int64_t)r.splits * d->M * d->N * nbatch;
+  }
+  return CST_OK;
+}
+
+// Device words (live-tile stamps, per-batch lengths) read back to the host: synchronous, so only while the profiler records.
+template <typename W>
+bool read_back(hipStream_t s, const W* dev, int64_t n, std::vector<W>& host) {
+  host.resize((size_t)n);
+  return hipStreamSynchronize(s) == hipSuccess && hipMemcpy(host.data(), dev, sizeof(W) * n, hipMemcpyDeviceToHost) == hipSuccess;
+}
+
+// FLOPs and bytes the profiling table credits this launch with.  Work that is skipped is never credited: with live-tile stamps or
+// row limits only the live part counts.  They live on the device, so this costs synchronous read-backs — done only while the
+// table is recording (bench.py's untimed roofline step).
+struct Work { double flops, bytes; };
+Work credited_work(const cst_gemm_desc* d, const GemmParams& p, hipStream_t s) {
+  double frac = 1.0;
+  if (cst_prof_is_on()) {
+    std::vector<uint32_t> st;
+    std::vector<int32_t> len;
+    const int64_t mtiles = cst_ceil_div(d->M, 256);
+    if (p.k_live && read_back(s, p.k_live, cst_ceil_div(d->K, 64), st)) {  // the live K blocks
       int64_t live = 0;
-      for (int64_t i = 0; i < nt; ++i) live += st[i] == p.k_epoch;
-      kfrac = (double)live / (double)nt;
+      for (uint32_t v : st) live += v == p.k_epoch;
+      frac *= (double)live / (double)st.size();
     }
-  }
-  if (p.k_len && cst_prof_is_on()) {
-    std::vector<int32_t> kl((size_t)d->batch0);
-    if (hipStreamSynchronize(s) == hipSuccess && hipMemcpy(kl.data(), p.k_len, sizeof(int32_t) * d->batch0, hipMemcpyDeviceToHost) == hipSuccess) {
+    if (p.k_len && read_back(s, p.k_len, d->batch0, len)) {  // the K range below each batch's limit
       double sum = 0.0;
-      for (int64_t b = 0; b < d->batch0; ++b) sum += (double)(kl[b] < 0 ? 0 : (kl[b] < d->K ? kl[b] : d->K));
-      kfrac *= sum / ((double)d->batch0 * (double)d->K);
+      for (int32_t v : len) sum += (double)(v < 0 ? 0 : (v < d->K ? v : d->K));
+      frac *= sum / ((double)d->batch0 * (double)d->K);
     }
-  }
-  if (p.m_len && cst_prof_is_on()) {  // conv GEMMs: credit the output tiles that still run their K loop
-    std::vector<int32_t> ml((size_t)d->batch0);
-    if (hipStreamSynchronize(s) == hipSuccess && hipMemcpy(ml.data(), p.m_len, sizeof(int32_t) * d->batch0, hipMemcpyDeviceToHost) == hipSuccess) {
-      const int64_t tiles = cst_ceil_div(d->M, 256);
+    if (p.m_len && read_back(s, p.m_len, d->batch0, len)) {  // conv GEMMs: the output tiles that still run their K loop
       double live = 0.0;
-      for (int64_t b = 0; b < d->batch0; ++b) {
-        const int64_t t = ml[b] <= 0 ? 0 : cst_ceil_div((int64_t)ml[b], 256);
-        live += (double)(t < tiles ? t : tiles);
+      for (int32_t v : len) {
+        const int64_t t = v <= 0 ? 0 : cst_ceil_div((int64_t)v, 256);
+        live += (double)(t < mtiles ? t : mtiles);
       }
-      kfrac *= live / ((double)d->batch0 * (double)tiles);
+      frac *= live / ((double)d->batch0 * (double)mtiles);
     }
-  }
-  if (p.m_live && cst_prof_is_on()) {  // dX GEMMs: credit the 256-row output tiles that still run their K loop (8p / 16-wave tile)
-    const int64_t nt = cst_ceil_div(d->M, 64);
-    std::vector<uint32_t> st((size_t)nt);
-    if (hipStreamSynchronize(s) == hipSuccess && hipMemcpy(st.data(), p.m_live, sizeof(uint32_t) * nt, hipMemcpyDeviceToHost) == hipSuccess) {
-      int64_t live = 0, tiles = cst_ceil_div(d->M, 256);
-      for (int64_t t = 0; t < tiles; ++t) {
+    if (p.m_live && read_back(s, p.m_live, cst_ceil_div(d->M, 64), st)) {  // dX GEMMs: the 256-row output tiles with a live 64-row block
+      const int64_t nt = (int64_t)st.size();
+      int64_t live = 0;
+      for (int64_t t = 0; t < mtiles; ++t) {
         bool l = false;
         for (int64_t i = 4 * t; i < 4 * t + 4 && i < nt; ++i) l |= st[i] == p.m_epoch;
         live += l;
       }
-      kfrac *= (double)live / (double)tiles;
+      frac *= (double)live / (double)mtiles;
     }
   }
-  const double flops = 2.0 * (double)d->M * (double)d->N * (double)d->K * (double)nbatch * kfrac;
-  const double esz = (double)cst_dtype_size(d->dtype);
-  const double bytes = ((double)d->M * d->K + (double)d->N * d->K) * esz * nbatch * kfrac + (double)d->M * d->N * cst_dtype_size(d->c_dtype) * nbatch;
-  CstProfScope prof(CST_K_GEMM, s, flops, bytes);
-  int rc;
-  const bool ak = d->a_kmajor != 0, bk = d->b_kmajor != 0;
-  // SEG instantiation only where a k-major operand is segmented (grouped conv with channel-major input); mn-major
-  // segments are folded into the per-thread base pointer and cost nothing per tile.
-  const bool seg = (ak && d->a_seg) || (bk && d->b_seg);
-  const bool large = use_large(d, p.splits);
-#define CST_GEMM_LAYOUT(T, SEGV, CFG)                                                                                   \
-  (ak ? (bk ? launch<T, true, true, SEGV, CFG>(p, d->M, d->N, nbatch, s) : launch<T, true, false, SEGV, CFG>(p, d->M, d->N, nbatch, s)) \
-      : (bk ? launch<T, false, true, SEGV, CFG>(p, d->M, d->N, nbatch, s) : launch<T, false, false, SEGV, CFG>(p, d->M, d->N, nbatch, s)))
-#define CST_GLDS_LAYOUT(T, CFG, NS)                                                                                     \
-  (ak ? (bk ? launch_glds<T, true, true, CFG, NS>(p, d->M, d->N, nbatch, s) : launch_glds<T, true, false, CFG, NS>(p, d->M, d->N, nbatch, s)) \
-      : (bk ? launch_glds<T, false, true, CFG, NS>(p, d->M, d->N, nbatch, s) : launch_glds<T, false, false, CFG, NS>(p, d->M, d->N, nbatch, s)))
-  // measured on MI355X (tools/bench_kernels.py): the DMA path wins when both operands are k-major (716 vs 661 TF/s, fc1
-  // forward); with an mn-major operand the register-staged path + padded LDS rows is faster (690 vs 649, 562 vs 486).
-  static const bool glds_all = getenv("CST_GEMM_GLDS_ALL") != nullptr;
-  const bool no_glds = getenv_no_glds() || (!(ak && bk) && !glds_all) || d->colsum != nullptr;  // (column sums live in gemm_kernel)
-#define CST_GEMM_DISPATCH(T)                                                                         \
-  (seg ? CST_GEMM_LAYOUT(T, true, CfgSmall)                                                           \
-       : (no_glds ? (large ? CST_GEMM_LAYOUT(T, false, CfgLarge) : CST_GEMM_LAYOUT(T, false, CfgSmall)) \
-                  : (large ? CST_GLDS_LAYOUT(T, CfgLarge, 2) : CST_GLDS_LAYOUT(T, CfgSmall, 2))))
-  // bf16 problems that fill the chip with 256 x 256 tiles take the 8-phase DMA-pipelined kernel (gemm8p.hip)
-  static const bool no_8p = getenv("CST_GEMM_NO_8P") != nullptr, force_8p = getenv("CST_GEMM_FORCE_8P") != nullptr;
-  // (A k-major only: with an mn-major A the register-staged 16-wave kernel measured 20-30 % faster on the dW shapes; and not
-  //  with an act'(aux_in) epilogue, whose 128 KiB-per-tile operand read is exposed at one workgroup per CU: 0.49 vs 0.42 ms)
-  static const bool all_8p = getenv("CST_GEMM_8P_ALL") != nullptr;
-  // act'(aux_in) epilogues: taken since the operand vectors are requested in one burst ahead of the epilogue passes (gemm8p.hip)
-  static const bool dact_8p = getenv("CST_GEMM_8P_NO_DACT") == nullptr;
-  static const bool no_skinny = getenv("CST_GEMM_NO_SKINNY") != nullptr;
-  // (256: -0.3 ms per update, 512 no better than 0.  400 looked better in back-to-back launches with the two-stage ring (4064 x 1536 x 512
-  //  17.4 -> 15.9 us) and was worse inside the update, where the operands are not L2-warm: 21.5 -> 24.4 us.)
-  static const int64_t skinny_tiles = getenv("CST_GEMM_SKINNY_TILES") ? atoll(getenv("CST_GEMM_SKINNY_TILES")) : 256;
-  static const bool skinny_ns4 = getenv("CST_GEMM_SKINNY_NS4") != nullptr;   // A/B switches
-  static const bool no_mid8p = getenv("CST_GEMM_NO_MID8P") != nullptr;
-  // k/k problems of 150-199 tiles of 256 x 256 (7901 x 1536 x 512: 186): the persistent kernel on 3/4 of the CUs still beats 744
-  // workgroups of 128 x 128 (19.5 vs 28.4 us)
-  const bool mid8p = !no_mid8p && ak && bk && !seg && nbatch == 1 && p.splits == 1 && d->M >= 256 && d->N >= 256 &&
-                     cst_ceil_div(d->M, 256) * cst_ceil_div(d->N, 256) >= 150;
-  static const bool no_narrow = getenv("CST_GEMM_NO_NARROW") != nullptr;
-  // gemm4w.hip (four waves, pinned issue order, three A stages): the N = 768 long-K launches of the step, same bits as the 8-wave
-  // kernel, 3-8 % faster inside the update (CST_GEMM_NO_4W=1: the 8-wave kernel everywhere, for A/B runs)
-  static const bool no_4w = getenv("CST_GEMM_NO_4W") != nullptr;
-  static const bool experiment = getenv("CST_GEMM_EXPERIMENT") != nullptr;
-  const char* force_cfg = experiment ? getenv("CST_GEMM_FORCE_CFG") : nullptr;
-  if (force_cfg && !*force_cfg) force_cfg = nullptr;
-  if (!no_narrow && !seg && !large && ak && bk && d->N <= 64 && d->M > 256) {
-    rc = d->dtype == CST_BF16 ? launch_glds<bf16_t, true, true, CfgNarrowN, 2>(p, d->M, d->N, nbatch, s)
-                              : launch_glds<float, true, true, CfgNarrowN, 2>(p, d->M, d->N, nbatch, s);
-  } else if (!no_narrow && !seg && !large && !ak && !bk && d->M <= 64 && d->N > 256) {
-    rc = d->dtype == CST_BF16 ? launch<bf16_t, false, false, false, CfgNarrowM>(p, d->M, d->N, nbatch, s)
-                              : launch<float, false, false, false, CfgNarrowM>(p, d->M, d->N, nbatch, s);
-  } else if (force_cfg && !ak && !bk && !seg && nbatch == 1 && d->dtype == CST_BF16) {
-    // (dW layouts: both operands mn-major; the split count comes from the caller's split_k.  tools/bench_gemm_cfg_dw.py — its
-    //  back-to-back launches keep the operands in L2 / Infinity Cache: 64 x 64 tiles with a quarter of the K slices won there
-    //  (512 x 512 x 4064: 19.9 -> 16.2 us) and LOST inside the update, where the operands come from HBM and the longer K loop per
-    //  workgroup is exposed (22.4 -> 24.6 us; x 7901: 24.8 -> 35.2): not adopted.)
-    const std::string f(force_cfg);
-    if (f == "small") rc = launch<bf16_t, false, false, false, CfgSmall>(p, d->M, d->N, nbatch, s);
-    else if (f == "narrowm") rc = launch<bf16_t, false, false, false, CfgNarrowM>(p, d->M, d->N, nbatch, s);
-    else if (f == "narrown") rc = launch<bf16_t, false, false, false, CfgNarrowN>(p, d->M, d->N, nbatch, s);
-    else if (f == "skinny") rc = launch<bf16_t, false, false, false, CfgSkinny>(p, d->M, d->N, nbatch, s);
-    else if (f == "large") rc = launch<bf16_t, false, false, false, CfgLarge>(p, d->M, d->N, nbatch, s);
-    else if (f == "big4r") rc = launch<bf16_t, false, false, false, Cfg<256, 256, 2, 2>>(p, d->M, d->N, nbatch, s);  // 4 waves x (128 x 128), register-staged
-    else { cst_set_error("cst_gemm: unknown CST_GEMM_FORCE_CFG %s", force_cfg); return CST_ERR_BAD_ARG; }
-  } else if (force_cfg && ak && bk && !seg && nbatch == 1 && p.splits == 1 && d->dtype == CST_BF16) {
-    // tools/bench_gemm_cfg.py: one shape through every k/k configuration (CST_GEMM_EXPERIMENT=1, CST_GEMM_FORCE_CFG read per call)
-    const std::string f(force_cfg);
-    if (f == "skinny4") rc = launch_glds<bf16_t, true, true, CfgSkinny, 4>(p, d->M, d->N, nbatch, s);
-    else if (f == "skinny2") rc = launch_glds<bf16_t, true, true, CfgSkinny, 2>(p, d->M, d->N, nbatch, s);
-    else if (f == "small2") rc = launch_glds<bf16_t, true, true, CfgSmall, 2>(p, d->M, d->N, nbatch, s);
-    else if (f == "small3") rc = launch_glds<bf16_t, true, true, CfgSmall, 3>(p, d->M, d->N, nbatch, s);
-    else if (f == "big4") rc = launch_glds<bf16_t, true, true, Cfg<256, 256, 2, 2>, 2>(p, d->M, d->N, nbatch, s);  // 4 waves x (128 x 128): see tools/bench_gemm_big4.py
-    else if (f == "big4n") rc = launch_glds<bf16_t, true, true, Cfg<256, 192, 2, 2>, 2>(p, d->M, d->N, nbatch, s);  // 128 x 96 wave tiles: N = 768 is 4 tiles
-    else if (f == "big4r") rc = launch<bf16_t, true, true, false, Cfg<256, 256, 2, 2>>(p, d->M, d->N, nbatch, s);          // the same, register-staged
-    else if (f == "large") rc = launch<bf16_t, true, true, false, CfgLarge>(p, d->M, d->N, nbatch, s);
-    else if (f == "8p" && cst_gemm8p_supported(p, ak, bk, nbatch)) rc = cst_gemm8p_launch(p, ak, bk, nbatch, s);
-    else if (f == "4w" && cst_gemm4w_supported(p, ak, bk, nbatch)) rc = cst_gemm4w_launch(p, s);
-    else { cst_set_error("cst_gemm: unknown CST_GEMM_FORCE_CFG %s", force_cfg); return CST_ERR_BAD_ARG; }
-  } else if (!no_skinny && ak && bk && !seg && nbatch == 1 && p.splits == 1 &&
-             (d->M <= 256 || (!large && !mid8p && cst_ceil_div(d->M, 128) * cst_ceil_div(d->N, 128) < skinny_tiles))) {
-    // (mid-size problems too — the Linear layers of the 512-wide encoder / decoder: few 128 x 128 tiles per CU leave CUs idle; 64 x 64
-    //  tiles quadruple the workgroups.)  Ring depth: four stages keep 48 KB per workgroup in flight, which is what a decode-step
-    //  projection (<= 256 rows, a few dozen workgroups, long K) is bound by; with more workgroups than fit two per CU the LDS they
-    //  hold is the limit instead — two stages let five of them share a CU (tools/bench_gemm_cfg.py: 7901 x 512 x 512 14.9 -> 12.1 us,
-    //  7901 x 512 x 2048 33.7 -> 28.7, 12000 x 512 x 512 17.1 -> 15.3; same bits: the K order per output element does not change).
-    const bool two_stage = d->M > 256 && cst_ceil_div(d->M, 64) * cst_ceil_div(d->N, 64) > 512 && !skinny_ns4;
-    if (two_stage) rc = d->dtype == CST_BF16 ? launch_glds<bf16_t, true, true, CfgSkinny, 2>(p, d->M, d->N, nbatch, s)
-                                             : launch_glds<float, true, true, CfgSkinny, 2>(p, d->M, d->N, nbatch, s);
-    else rc = d->dtype == CST_BF16 ? launch_glds<bf16_t, true, true, CfgSkinny, 4>(p, d->M, d->N, nbatch, s)
-                                   : launch_glds<float, true, true, CfgSkinny, 4>(p, d->M, d->N, nbatch, s);
-  } else if (d->dtype == CST_BF16 && !seg && !no_4w && !d->colsum && cst_gemm4w_supported(p, ak, bk, nbatch)) {
-    rc = cst_gemm4w_launch(p, s);  // long K, N a multiple of 192 (the N = 768 family): four waves, pinned issue order (gemm4w.hip)
-  } else if (d->dtype == CST_BF16 && !seg && !no_8p && !d->colsum && (ak || all_8p || force_8p) && (!d->dact || (dact_8p && !d->resid && !d->aux_out) || all_8p || force_8p) && (large || mid8p || force_8p) && cst_gemm8p_supported(p, ak, bk, nbatch))
-    rc = cst_gemm8p_launch(p, ak, bk, nbatch, s);
-  else if (d->dtype == CST_BF16) rc = CST_GEMM_DISPATCH(bf16_t);
-  else rc = CST_GEMM_DISPATCH(float);
-#undef CST_GEMM_DISPATCH
-#undef CST_GEMM_LAYOUT
-#undef CST_GLDS_LAYOUT
-  if (cst_prof_is_on())
-    prof.tag("M=%lld N=%lld K=%lld b=%lld a%c b%c split=%d%s%s%s%s%s%s%s", (long long)d->M, (long long)d->N, (long long)d->K, (long long)nbatch, ak ? 'k' : 'm',
-             bk ? 'k' : 'm', p.splits, d->bias ? " bias" : "", d->act ? " act" : "", d->aux_out ? " aux_out" : "", d->dact ? " dact" : "",
-             d->resid ? " resid" : "", d->drop_p > 0 ? " drop" : "", (d->k_live || d->m_live || d->k_len || d->m_len) ? " live" : "");
-  if (rc != CST_OK) return rc;
+  const double nbatch = (double)(d->batch0 * d->batch1), esz = (double)cst_dtype_size(d->dtype);
+  return {2.0 * (double)d->M * (double)d->N * (double)d->K * nbatch * frac,
+          ((double)d->M * d->K + (double)d->N * d->K) * esz * nbatch * frac + (double)d->M * d->N * cst_dtype_size(d->c_dtype) * nbatch};
+}
+
+// The two routes without a kernel; only the experiment hook can ask for them.
+int unlaunchable(const GemmRoute& r, const GemmSwitches& sw) {
+  if (r.tile == Tile::Unknown) {
+    cst_set_error("cst_gemm: unknown CST_GEMM_FORCE_CFG %s", sw.force_cfg ? sw.force_cfg : "");
+    return CST_ERR_BAD_ARG;
+  }
+  if (r.family == Family::Reg && r.colsum == Colsum::Fused && kTileDims[(int)r.tile].nt > 256) {  // (launch<> says the same)
+    cst_set_error("cst_gemm: internal: column sums requested from a configuration that does not build them");
+    return CST_ERR_UNSUPPORTED;
+  }
+  return CST_OK;
+}
+
+// register-staged kernel of one configuration, any layout
+template <typename T, bool SEG, typename C>
+int launch_reg(const GemmRoute& r, const GemmParams& p, int64_t nbatch, hipStream_t s) {
+  return r.ak ? (r.bk ? launch<T, true, true, SEG, C>(p, p.M, p.N, nbatch, s) : launch<T, true, false, SEG, C>(p, p.M, p.N, nbatch, s))
+              : (r.bk ? launch<T, false, true, SEG, C>(p, p.M, p.N, nbatch, s) : launch<T, false, false, SEG, C>(p, p.M, p.N, nbatch, s));
+}
+
+constexpr int arm(Family f, Tile t, int stages = 0) { return ((int)f << 8) | ((int)t << 4) | stages; }
+
+// The launch of a route.  gemm_route sends only k/k problems to the DMA ring, only m/m ones to NarrowM, and the configurations of the
+// experiment hook (bf16 only) to k/k or m/m: an arm instantiates what can reach it.
+template <typename T>
+int launch_route(const GemmRoute& r, const GemmParams& p, int64_t nbatch, hipStream_t s, const GemmSwitches& sw) {
+  constexpr bool HOOK = std::is_same<T, bf16_t>::value;
+  const int64_t M = p.M, N = p.N;
+  switch (arm(r.family, r.tile, r.family == Family::Dma ? r.stages : 0)) {
+    case arm(Family::Persistent8, Tile::Large): return cst_gemm8p_launch(p, r.ak, r.bk, nbatch, s);
+    case arm(Family::FourWave, Tile::Big4N): return cst_gemm4w_launch(p, s);
+    case arm(Family::Reg, Tile::Small): return r.seg ? launch_reg<T, true, CfgSmall>(r, p, nbatch, s) : launch_reg<T, false, CfgSmall>(r, p, nbatch, s);
+    case arm(Family::Reg, Tile::Large): return launch_reg<T, false, CfgLarge>(r, p, nbatch, s);
+    case arm(Family::Reg, Tile::NarrowM): return launch<T, false, false, false, CfgNarrowM>(p, M, N, nbatch, s);
+    case arm(Family::Dma, Tile::Small, 2): return launch_glds<T, true, true, CfgSmall, 2>(p, M, N, nbatch, s);
+    case arm(Family::Dma, Tile::Large, 2): return launch_glds<T, true, true, CfgLarge, 2>(p, M, N, nbatch, s);
+    case arm(Family::Dma, Tile::NarrowN, 2): return launch_glds<T, true, true, CfgNarrowN, 2>(p, M, N, nbatch, s);
+    case arm(Family::Dma, Tile::Skinny, 2): return launch_glds<T, true, true, CfgSkinny, 2>(p, M, N, nbatch, s);
+    case arm(Family::Dma, Tile::Skinny, 4): return launch_glds<T, true, true, CfgSkinny, 4>(p, M, N, nbatch, s);
+    // ---- the experiment hook only ----
+    case arm(Family::Reg, Tile::NarrowN): if constexpr (HOOK) return launch<T, false, false, false, CfgNarrowN>(p, M, N, nbatch, s); break;
+    case arm(Family::Reg, Tile::Skinny): if constexpr (HOOK) return launch<T, false, false, false, CfgSkinny>(p, M, N, nbatch, s); break;
+    case arm(Family::Reg, Tile::Big4):
+      if constexpr (HOOK) return r.ak ? launch<T, true, true, false, CfgBig4>(p, M, N, nbatch, s) : launch<T, false, false, false, CfgBig4>(p, M, N, nbatch, s);
+      break;
+    case arm(Family::Dma, Tile::Small, 3): if constexpr (HOOK) return launch_glds<T, true, true, CfgSmall, 3>(p, M, N, nbatch, s); break;
+    case arm(Family::Dma, Tile::Big4, 2): if constexpr (HOOK) return launch_glds<T, true, true, CfgBig4, 2>(p, M, N, nbatch, s); break;
+    case arm(Family::Dma, Tile::Big4N, 2): if constexpr (HOOK) return launch_glds<T, true, true, CfgBig4N, 2>(p, M, N, nbatch, s); break;
+    default: break;
+  }
+  const int rc = unlaunchable(r, sw);  // Tile::Unknown: nothing else leaves gemm_route without an arm
+  if (rc == CST_OK) cst_set_error("cst_gemm: internal: a route without a launch arm");
+  return rc == CST_OK ? CST_ERR_UNSUPPORTED : rc;
+}
+
+// Behind the launch: the split-K reduce (unless the caller finishes the slabs itself) and the separate column sum.
+int finish(const cst_gemm_desc* d, const GemmRoute& r, const GemmParams& p, cst_stream stream) {
+  const int64_t nbatch = d->batch0 * d->batch1;
   if (p.splits > 1 && d->defer_reduce) {
     // the slabs stay in the caller's workspace for cst_reduce_multi: only epilogues that are a plain conversion can be finished there
     CST_REQUIRE((nbatch == 1 || !d->colsum) && d->alpha == 1.0f && !d->bias && !d->act && !d->dact && !d->aux_out && !d->resid && d->drop_p == 0.0f && d->ldc == d->N &&
-                    d->N % 8 == 0 && (!d->colsum || cs_fused),
+                    d->N % 8 == 0 && r.colsum != Colsum::Separate,
                 "cst_gemm: defer_reduce needs a plain epilogue and a dense C (batched: no colsum; the slabs are [batch][split][M][N])");
-    return rc;
+    return CST_OK;
   }
+  int rc = CST_OK;
   if (p.splits > 1) {
     const int64_t total = d->M * d->N;
     const int64_t work = (p.vec_epi && d->N % 8 == 0) ? total / 8 : total;  // items the reduce kernel's threads walk
     int blocks = (int)(cst_ceil_div(work, 256) < 2048 ? cst_ceil_div(work, 256) : 2048);
     dim3 grid(blocks, (unsigned)nbatch);
-    if (d->dtype == CST_BF16) hipLaunchKernelGGL(splitk_reduce_kernel<bf16_t>, grid, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL(splitk_reduce_kernel<float>, grid, dim3(256), 0, s, p);
+    if (d->dtype == CST_BF16) hipLaunchKernelGGL(splitk_reduce_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL(splitk_reduce_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, p);
     rc = cst_check_launch("cst_gemm split-k reduce");
   }
-  if (rc == CST_OK && d->colsum && !cs_fused) {
+  if (rc == CST_OK && r.colsum == Colsum::Separate) {
     // the 16-wave / DMA configurations do not build the by-product: two-launch column sum over A [K rows, M columns], its row-chunk
     // partials behind the split-K slabs of the caller's workspace; the live K stamps are the same 64-row blocks
     void* cws = (char*)d->workspace + (p.splits > 1 ? (int64_t)p.splits * d->M * d->N * (int64_t)sizeof(float) : 0);
@@ -1220,9 +1337,57 @@ static int gemm_one(const cst_gemm_desc* d, cst_stream stream, int64_t drop_row0
   return rc;
 }
 
+int gemm_one(const cst_gemm_desc* d, cst_stream stream) {
+  int rc = validate(d);
+  if (rc != CST_OK) return rc;
+  const GemmSwitches sw = gemm_switches();
+  GemmParams p = fill_params(d, sw);
+  GemmRoute r;
+  if ((rc = take_route(d, sw, p, r)) != CST_OK) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t nbatch = d->batch0 * d->batch1;
+  const Work w = credited_work(d, p, s);
+  CstProfScope prof(CST_K_GEMM, s, w.flops, w.bytes);
+  rc = r.bf16 ? launch_route<bf16_t>(r, p, nbatch, s, sw) : launch_route<float>(r, p, nbatch, s, sw);
+  if (cst_prof_is_on())
+    prof.tag("M=%lld N=%lld K=%lld b=%lld a%c b%c split=%d%s%s%s%s%s%s%s", (long long)d->M, (long long)d->N, (long long)d->K, (long long)nbatch, r.ak ? 'k' : 'm',
+             r.bk ? 'k' : 'm', p.splits, d->bias ? " bias" : "", d->act ? " act" : "", d->aux_out ? " aux_out" : "", d->dact ? " dact" : "",
+             d->resid ? " resid" : "", d->drop_p > 0 ? " drop" : "", (d->k_live || d->m_live || d->k_len || d->m_len) ? " live" : "");
+  return rc != CST_OK ? rc : finish(d, r, p, stream);
+}
+
+// The queries describe the launch cst_gemm would make; they validate nothing (callers ask with operands still unset).
+GemmRoute query_route(const cst_gemm_desc* d) {
+  const GemmSwitches sw = gemm_switches();
+  return gemm_route(d, fill_params(d, sw), sw);
+}
+
+}  // namespace
+
+extern "C" int cst_gemm_splits(const cst_gemm_desc* d) { return d ? query_route(d).splits : 0; }
+
+extern "C" int cst_gemm_colsum_is_fused(const cst_gemm_desc* d) { return d && query_route(d).colsum == Colsum::Fused ? 1 : 0; }
+
+extern "C" int64_t cst_gemm_workspace(const cst_gemm_desc* d) { return route_workspace(d, query_route(d)); }
+
+extern "C" int cst_gemm_route(const cst_gemm_desc* d, char* out, int64_t out_bytes) {
+  if (out && out_bytes > 0) out[0] = 0;
+  int rc = validate(d);
+  if (rc != CST_OK) return rc;
+  CST_REQUIRE(out && out_bytes > 0, "cst_gemm_route: no room for the text");
+  const GemmSwitches sw = gemm_switches();
+  GemmParams p = fill_params(d, sw);
+  GemmRoute r;
+  if ((rc = take_route(d, sw, p, r)) != CST_OK) return rc;
+  if ((rc = unlaunchable(r, sw)) != CST_OK) return rc;
+  route_text(r, out, out_bytes);
+  return CST_OK;
+}
+
 // (A row-split dispatch — whole rounds of 256 x 256 tiles to the persistent kernel, the remaining row slab to the 128 x 128
 // configurations — was measured for the N = 768 family (564 tiles = 2.2 rounds): 0.241 vs 0.244 ms, no gain; not kept.
 // Second attempt, the slab kept on the persistent kernel as a split-K (x3-4) launch + reduce epilogue: fc2 fwd 0.275 vs 0.278 ms,
 // out_proj 0.105 vs 0.093, qkv dX 0.215 vs 0.189 — the 20 %-occupied last round is not a full round's cost (the 52 busy CUs run
 // with the whole chip's bandwidth and clock budget), and the slabs + reduce launch cost more than it saves; not kept.)
-extern "C" int cst_gemm(const cst_gemm_desc* d, cst_stream stream) { return gemm_one(d, stream, 0); }
+extern "C" int cst_gemm(const cst_gemm_desc* d, cst_stream stream) { return gemm_one(d, stream); }
+

@@ -266,8 +266,7 @@ int cst_gemm4w_launch(cstg::GemmParams p, hipStream_t s) {
   }
   p.tiles_m = (int)cst_ceil_div(p.M, BM);
   p.tiles_n = (int)(p.N / BN);
-  static const int group_m = [] { const char* e = getenv("CST_GEMM_4W_GROUP_M"); const int g = e ? atoi(e) : 8; return g > 0 ? g : 8; }();
-  p.group_m = group_m;  // m tiles per group of the tile walk (an XCD's concurrent workgroups cover group_m x tiles_n tiles)
+  p.group_m = 8;  // m tiles per group of the tile walk (an XCD's concurrent workgroups cover group_m x tiles_n tiles)
   hipLaunchKernelGGL(gemm4w_kernel, dim3((unsigned)(p.tiles_m * p.tiles_n)), dim3(NT), LDS_BYTES, s, p);
   return cst_check_launch("cst_gemm (4-wave)");
 }

@@ -829,11 +829,10 @@ int launch8p(GemmParams p, int64_t nbatch, hipStream_t s) {
     for (int sft = 0; sft < 16; ++sft)
       if ((1 << sft) == p.group_m) p.group_shift = sft;
     // round-robin deal of the m-tile groups over the XCDs (setup()): launches with per-batch row limits whose batches have at
-    // least two full groups per XCD; CST_GEMM8P_NO_GPERM=1 keeps the contiguous runs (A/B runs)
-    static const bool no_gperm = getenv("CST_GEMM8P_NO_GPERM") != nullptr;
+    // least two full groups per XCD (same bits as the contiguous runs)
     const int gfull = p.tiles_m / p.group_m;
-    p.gperm_full = (!no_gperm && p.m_len && gfull >= 16) ? gfull : 0;
-    p.mrot = (!no_gperm && p.m_len && p.gperm_full == 0 && ntl >= 2) ? (int)(ntl / 8 > 0 ? ntl / 8 : 1) : 0;
+    p.gperm_full = (p.m_len && gfull >= 16) ? gfull : 0;
+    p.mrot = (p.m_len && p.gperm_full == 0 && ntl >= 2) ? (int)(ntl / 8 > 0 ? ntl / 8 : 1) : 0;
     p.gperm_q = gfull / 8;
     p.gperm_r = gfull % 8;
     p.magic_gq = p.gperm_q > 0 ? ((1ull << 40) / (unsigned long long)p.gperm_q) + 1ull : 0ull;
@@ -843,7 +842,6 @@ int launch8p(GemmParams p, int64_t nbatch, hipStream_t s) {
     int dev = 0, n = 256;
     (void)hipGetDevice(&dev);
     (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-    if (const char* e = getenv("CST_GEMM8P_CUS")) n = atoi(e);  // experiments: persistent workgroups on a part of the chip only
     return n > 0 ? n : 256;
   }();
   // CUs left to a concurrent stream (the gradient all-reduce of a data-parallel backward: cst_gemm_reserve_cus / CST_GEMM_RESERVE_CUS):

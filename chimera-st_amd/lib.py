@@ -147,6 +147,7 @@ SYMBOLS = [
     ("cst_gemm_workspace", c_i64, [ctypes.POINTER(GemmDesc)]),
     ("cst_gemm_colsum_is_fused", c_int, [ctypes.POINTER(GemmDesc)]),
     ("cst_gemm_splits", c_int, [ctypes.POINTER(GemmDesc)]),
+    ("cst_gemm_route", c_int, [ctypes.POINTER(GemmDesc), ctypes.c_char_p, c_i64]),
     ("cst_reduce_multi", c_int, [ctypes.POINTER(ReduceItem), c_int, c_p]),
     ("cst_gemm", c_int, [ctypes.POINTER(GemmDesc), c_p]),
     ("cst_posconv_fwd", c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_p]),

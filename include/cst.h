@@ -39,7 +39,8 @@ extern "C" {
  * without a bump: no existing signature or layout changed, and a library without the symbol fails at symbol lookup.  The same holds for
  * cst_lex_desc, cst_lex_workspace, cst_lex_init and cst_beam_step_lex (lexical constraints), added later at 13, and for cst_ctc_fwd,
  * cst_ctc_bwd, cst_ctc_greedy and cst_edit_distance (CTC fine-tuning), and for cst_w2v_negatives, cst_infonce_fwd, cst_infonce_bwd_x and
- * cst_infonce_bwd_y, cst_gumbel_vq_workspace, cst_gumbel_vq_fwd and cst_gumbel_vq_bwd (the head of wav2vec2 pre-training).
+ * cst_infonce_bwd_y, cst_gumbel_vq_workspace, cst_gumbel_vq_fwd and cst_gumbel_vq_bwd (the head of wav2vec2 pre-training), and for the
+ * host-only query cst_gemm_route.
  * cst_version() returns the value the library was built with; chimera-st_amd/lib.py refuses a mismatch. */
 #define CST_ABI_VERSION 13
 
@@ -188,6 +189,15 @@ int64_t cst_gemm_workspace(const cst_gemm_desc* d);
 int cst_gemm_colsum_is_fused(const cst_gemm_desc* d);
 /* The number of K slices cst_gemm will use for this descriptor (1 = no split, no workspace slabs). */
 int cst_gemm_splits(const cst_gemm_desc* d);
+/* Which kernel cst_gemm would launch for this descriptor, as text (host only: no HIP call, no operand is read).  Runs cst_gemm's
+ * validation: a descriptor cst_gemm rejects gets the same code and cst_last_error text.  out receives one of
+ *   "reg <bf16|f32> <a><b>[ seg] <BM>x<BN> nt<threads>[ colsum] split<s>"   register-staged kernel
+ *   "glds <bf16|f32> <a><b> <BM>x<BN> nt<threads> ns<stages> split<s>"      DMA-ring kernel
+ *   "8p <a><b>"                                                             persistent 8-wave kernel
+ *   "4w"                                                                    four-wave 256 x 192 kernel
+ * <a>/<b>: k or m, a k-major or mn-major operand; " seg": the segmented-K instantiation; " colsum": the column sums are the launch's own
+ * by-product; <s>: K slices.  The three queries above are views of the same decision. */
+int cst_gemm_route(const cst_gemm_desc* d, char* out, int64_t out_bytes);
 /* Persistent GEMM launches use (CUs - n) workgroups from now on (n < 0: query only); returns the previous value.  The data-parallel
  * reducer sets it while bucket all-reduces are in flight under the backward pass, so that the RCCL kernels on the side stream find free
  * CUs instead of waiting for a launch boundary (legacy_distributed_data_parallel.py has no overlap to protect).  Initial value:

@@ -1296,6 +1296,39 @@ def test_gemm_colsum_is_the_bias_gradient_next_to_dw(K, dt, n_out, k_in, tokens)
         check(dw2, dy.float().t() @ x.float(), dt, "dW with stamps")
 
 
+@pytest.mark.parametrize("spec,route", [
+    ("160 512 512 kk", "glds bf16 kk 64x64 nt256 ns4 split1"),
+    ("7901 512 512 kk", "glds bf16 kk 64x64 nt256 ns2 split1"),
+    ("4064 1536 512 kk", "glds bf16 kk 128x128 nt256 ns2 split1"),
+    ("257 64 768 kk", "glds bf16 kk 128x64 nt256 ns2 split1"),
+    ("7901 1536 512 kk", "8p kk"),
+    ("4064 512 10000 km", "8p km"),
+    ("24000 768 1536 kk", "4w"),
+    ("512 512 7901 mm colsum", "reg bf16 mm 128x128 nt256 colsum split15"),
+    ("1536 512 7901 mm", "reg bf16 mm 128x128 nt256 split5"),
+    ("768 768 31760 mm colsum", "reg bf16 mm 256x256 nt1024 split28"),
+    ("1000 768 512 kk f32", "glds f32 kk 128x128 nt256 ns2 split2"),
+])
+def test_gemm_default_routes_name_their_kernel_and_give_the_product(K, spec, route):
+    """One launch per arm of the dispatcher (gemm.hip: gemm_route), at shapes of the training step and of decoding, nothing forced:
+    cst_gemm_route names the kernel recorded for the shape (tests/test_gemm_route_cpu.py, whose row notation this uses), and the
+    launch gives the fp32 product (and the column sums of A where they are asked for)."""
+    from test_gemm_route_cpu import parse, route_of
+    k, L = K
+    assert route_of(L, L.load(), spec) == route
+    M, N, K_, lay, flags, _ = parse(spec)
+    dt = torch.float32 if "f32" in flags else torch.bfloat16
+    ak, bk = lay[0] == "k", lay[1] == "k"
+    A = rnd(M, K_, dt=dt, seed=91) if ak else rnd(K_, M, dt=dt, seed=91)
+    B = rnd(N, K_, dt=dt, seed=92, scale=K_ ** -0.5) if bk else rnd(K_, N, dt=dt, seed=92, scale=K_ ** -0.5)
+    C = torch.full((M, N), float("nan"), dtype=dt, device="cuda")
+    db = torch.full((M,), float("nan"), dtype=dt, device="cuda") if "colsum" in flags else None
+    k.gemm(A, B, C, M, N, K_, a_kmajor=int(ak), b_kmajor=int(bk), lda=A.stride(0), ldb=B.stride(0), ldc=N, colsum=db)
+    check(C, (A.float() if ak else A.float().t()) @ (B.float().t() if bk else B.float()), dt, spec)
+    if db is not None:
+        check(db, A.float().sum(0), dt, spec + ": column sums")
+
+
 def test_reduce_multi_finishes_many_reductions_in_one_launch(K):
     """cst_reduce_multi: dst[i] = sum_p src[p * stride + i] for a table of items of different lengths, partial counts, strides and
     output types in ONE launch (more than 64 items: two launches), against fp64 sums; run twice: the same bits."""

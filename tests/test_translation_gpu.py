@@ -374,4 +374,7 @@ def test_the_st_stage_starts_from_the_mt_checkpoint(mt_run, tmp_path, capsys):
     sd = tr.get_model().state_dict()  # (learning rate 0: the parameters are still the MT stage's)
     assert set(sd) == set(mt["model"])
     for k, v in mt["model"].items():
-        assert torch.equal(sd[k].float().cpu(), v.float().to(sd[k].dtype).float()), k
+        a, b = sd[k].float().cpu(), v.float().to(sd[k].dtype).float()
+        # (`_float_tensor` of the sinusoidal tables is the reference's one-element placeholder buffer, never written: where the
+        #  allocator hands out a NaN, the loaded NaN is the same value and still not `equal`)
+        assert torch.equal(a, b) or (k.endswith("._float_tensor") and torch.allclose(a, b, rtol=0, atol=0, equal_nan=True)), k
