@@ -122,7 +122,7 @@ def _register_embedded_w2v(args):
 
 def load_model_ensemble_and_task(filenames, arg_overrides=None, task=None, strict=True):
     """checkpoint_utils.py:269-309: [(model built from the checkpoint's args, state loaded)], args, task."""
-    from . import criterions, s2t_transformer, tasks, w2v2_transformer, w2v2_transformer_interlingua, wav2vec2  # noqa: F401 (registries)
+    from . import criterions, s2t_transformer, tasks, transformer_lm, w2v2_transformer, w2v2_transformer_interlingua, wav2vec2  # noqa: F401 (registries)
     ensemble, args = [], None
     filenames = list(filenames)
     for filename in filenames:

@@ -16,7 +16,7 @@ import time
 
 import torch
 
-from . import checkpoint_utils, criterions, fbank, registry, s2t_transformer, tasks, w2v2_transformer, w2v2_transformer_interlingua, wav2vec2_asr  # noqa: F401
+from . import checkpoint_utils, criterions, fbank, registry, s2t_transformer, tasks, transformer_lm, w2v2_transformer, w2v2_transformer_interlingua, wav2vec2_asr  # noqa: F401
 from .distributed import distributed_init, launch_ranks, needs_self_launch
 from .hostcfg import limit_host_threads
 from .trainer import Trainer
@@ -181,8 +181,9 @@ def train_main(argv=None):
             for k, v in (out or {}).items():
                 agg[k] = agg.get(k, 0.0) + (v if k not in ("lr", "gnorm") else 0.0)
         ss = max(agg.get("sample_size", 1.0), 1.0)
+        derived = trainer.criterion.derived_metrics(agg) if getattr(trainer.criterion, "derives_from_train_log", False) else {}  # (cross_entropy: ppl)
         _log(rank, event="train", epoch=epoch, num_updates=trainer.num_updates, loss=agg.get("loss", 0.0) / ss / math.log(2),
-             wall=time.time() - t0, nsentences=agg.get("nsentences"))
+             wall=time.time() - t0, nsentences=agg.get("nsentences"), **derived)
         val = None
         if not args.disable_validation and epoch % args.validate_interval == 0:
             stats = validate(trainer, task, args, args.valid_subset.split(",")[0], rank, world)
@@ -370,6 +371,9 @@ def generate_main(argv=None):
     overrides = {"data": args.data, "config_yaml": args.config_yaml, "max_source_positions": args.max_source_positions,
                  "max_target_positions": args.max_target_positions}
     models, margs, task = checkpoint_utils.load_model_ensemble_and_task(args.path.split(":"), arg_overrides=overrides)
+    if getattr(margs, "task", None) == "language_modeling":
+        raise NotImplementedError("generation from a language model (fairseq-generate --task language_modeling) is not built: score it with "
+                                  "fairseq_eval_lm.py, or fuse it into a translation model's decode with --lm-path")
     dtype = torch.bfloat16 if (args.fp16 or args.bf16) else torch.float32
     models = [m.to("cuda", dtype).eval() for m in models]
     ds = task.load_dataset(args.gen_subset)
@@ -468,4 +472,157 @@ def generate_main(argv=None):
     if out is not sys.stdout:
         out.close()
         print(json.dumps(summary))
+    return summary
+
+
+# --------------------------------------------------------------------------------------------------------------------
+def eval_lm_parser():
+    """The options of fairseq_eval_lm.py (a subset of fairseq-eval-lm's, same names and defaults)."""
+    p = argparse.ArgumentParser(allow_abbrev=False)
+    p.add_argument("data")
+    p.add_argument("--path", required=True, help="the language model's checkpoint")
+    p.add_argument("--task", default="language_modeling")
+    p.add_argument("--gen-subset", default="test")
+    p.add_argument("--max-tokens", type=int, default=None)
+    p.add_argument("--max-sentences", "--batch-size", type=int, default=None, dest="batch_size")
+    p.add_argument("--tokens-per-sample", type=int, default=None, help="(default: the checkpoint's)")
+    p.add_argument("--sample-break-mode", default=None, choices=["none", "complete", "complete_doc", "eos"], help="(default: the checkpoint's)")
+    p.add_argument("--remove-bpe", "--post-process", nargs="?", const="@@ ", default=None, dest="post_process")
+    p.add_argument("--output-word-probs", action="store_true", help="if set, outputs words and their predicted log probabilities")
+    p.add_argument("--output-word-stats", action="store_true", help="if set, outputs word statistics such as word count, average probability, etc")
+    p.add_argument("--context-window", type=int, default=0, help="(values above 0 are not built)")
+    p.add_argument("--softmax-batch", type=int, default=sys.maxsize, help="accepted, without effect: no fp32 [B, T, V] tensor is materialised")
+    p.add_argument("--fp16", action="store_true")
+    p.add_argument("--bf16", action="store_true")
+    p.add_argument("--seed", type=int, default=1)
+    p.add_argument("--quiet", action="store_true")
+    return p
+
+
+def check_eval_lm_args(args):
+    if args.context_window > 0:
+        raise NotImplementedError("--context-window %d is not built: every block is scored from its own first token" % args.context_window)
+    if args.post_process == "sentencepiece":  # (fairseq_cli/eval_lm.py:163-164 refuses it too)
+        raise NotImplementedError("--post-process sentencepiece (--remove-bpe sentencepiece) is not built: the reference's eval-lm "
+                                  "raises on it as well; pass the continuation marker itself, e.g. --remove-bpe '@@ '")
+    return args
+
+
+def bpe_continuation_tokens(dictionary, post_process):
+    """(ids of the symbols that end in the continuation marker, the marker's length) — fairseq_cli/eval_lm.py:162-175."""
+    if post_process is None:
+        return None, 0
+    bpe_cont = post_process.rstrip()
+    return {i for i in range(len(dictionary)) if dictionary[i].endswith(bpe_cont)}, len(bpe_cont)
+
+
+def lm_score_stats(tokens, pos_scores, bpe_toks=None):
+    """One sample's share of eval-lm's totals (fairseq_cli/eval_lm.py:195-220): a BPE continuation token's score moves onto the next
+    token and is not counted; +-inf scores are dropped.  tokens: the ids [n]; pos_scores: float [n] natural-log scores.
+    -> (score sum, count, the merged scores [n] before the infinite ones are dropped, the number of infinite scores)."""
+    tokens = [int(t) for t in (tokens.tolist() if torch.is_tensor(tokens) else tokens)]
+    pos = torch.as_tensor(pos_scores).detach().float().cpu().clone()
+    skipped = 0
+    if bpe_toks is not None:
+        for i in range(len(tokens) - 1):
+            if tokens[i] in bpe_toks:
+                skipped += 1
+                pos[i + 1] += pos[i]
+                pos[i] = 0
+    inf = torch.isinf(pos)
+    kept = pos[~inf]
+    return float(kept.sum()), int(kept.numel()) - skipped, pos, int(inf.sum())
+
+
+class WordStat:
+    """fairseq_cli/eval_lm.py:37-66."""
+
+    def __init__(self, word, is_bpe):
+        self.word, self.is_bpe = word, is_bpe
+        self.log_prob, self.next_word_prob, self.count, self.missing_next_words = 0, 0, 0, 0
+
+    def add(self, log_prob, next_word_prob):
+        if next_word_prob is not None:
+            self.next_word_prob += next_word_prob
+        else:
+            self.missing_next_words += 1
+        self.log_prob += log_prob
+        self.count += 1
+
+    def __str__(self):
+        return "{}\t{}\t{}\t{}\t{}\t{}".format(self.word, self.count, self.log_prob, self.is_bpe, self.next_word_prob,
+                                               self.count - self.missing_next_words)
+
+
+def eval_lm_main(argv=None):
+    """fairseq_cli/eval_lm.py:69-276: the perplexity of a language model on a binarised split.  Every batch is scored by the
+    SequenceScorer (cst_score_tokens: no fp32 [B, T, V] tensor, one transfer of the scores per batch)."""
+    from .sequence_scorer import SequenceScorer
+    argv = list(sys.argv[1:] if argv is None else argv)
+    args, ignored = eval_lm_parser().parse_known_args(argv)
+    check_eval_lm_args(args)
+    limit_host_threads()
+    overrides = {"data": args.data}
+    if args.tokens_per_sample is not None:
+        overrides["tokens_per_sample"] = args.tokens_per_sample
+    if args.sample_break_mode is not None:
+        overrides["sample_break_mode"] = args.sample_break_mode
+    models, margs, task = checkpoint_utils.load_model_ensemble_and_task([args.path], arg_overrides=overrides)
+    if not hasattr(task, "dictionary") or getattr(margs, "task", None) != "language_modeling":
+        raise ValueError("%s was trained by task %r: eval-lm scores a language_modeling checkpoint" % (args.path, getattr(margs, "task", None)))
+    dtype = torch.bfloat16 if (args.fp16 or args.bf16) else torch.float32
+    models = [m.to("cuda", dtype).eval() for m in models]
+    ds = task.load_dataset(args.gen_subset)
+    limits = [task.max_positions()] + [m.max_positions() for m in models]
+    itr = task.get_batch_iterator(ds, max_tokens=args.max_tokens or 36000, max_sentences=args.batch_size,
+                                  max_positions=min(int(v) for v in limits if v is not None), ignore_invalid_inputs=True, seed=args.seed)
+    d = task.target_dictionary
+    scorer = SequenceScorer(d)
+    bpe_toks, bpe_len = bpe_continuation_tokens(task.source_dictionary, args.post_process)
+    score_sum, count, ntokens, word_stats, t0 = 0.0, 0, 0, {}, time.time()
+    for sample in itr.next_epoch_itr(shuffle=False):
+        if not sample or "net_input" not in sample:
+            continue
+        ni = sample["net_input"]
+        if "block_idx" in ni:  # device-resident corpus (monolingual_dataset.py): the batch from its block indices, one launch
+            dev = ni["block_corpus"].materialize(sample)
+        else:
+            dev = {"net_input": {k: v.cuda() for k, v in ni.items()}, "target": sample["target"].cuda()}
+        hypos = scorer.generate(models, {"net_input": dev["net_input"], "target": dev["target"]})
+        ntokens += sample["ntokens"]
+        for i, sid in enumerate(sample["id"].tolist()):
+            hypo = hypos[i][0]
+            tokens = hypo["tokens"].tolist()
+            s, c, pos, n_inf = lm_score_stats(tokens, hypo["positional_scores"], bpe_toks)
+            if n_inf:
+                print("skipping tokens with inf scores: " + d.string(torch.tensor([t for t, x in zip(tokens, pos.tolist()) if math.isinf(x)])))
+            score_sum += s
+            count += c
+            if args.output_word_probs or args.output_word_stats:  # :222-257
+                w, word_prob, is_bpe = "", [], False
+                for k, w_ind in enumerate(tokens):
+                    w += task.source_dictionary[w_ind]
+                    if bpe_toks is not None and w_ind in bpe_toks:
+                        w, is_bpe = w[:-bpe_len], True
+                        continue
+                    word_prob.append((w, float(pos[k])))
+                    next_prob = next((float(pos[j]) for j in range(k + 1, len(tokens)) if float(pos[j]) != 0), None)
+                    word_stats.setdefault(w, WordStat(w, is_bpe)).add(float(pos[k]), next_prob)
+                    w, is_bpe = "", False
+                if args.output_word_probs:
+                    print(str(int(sid)) + " " + "\t".join("{} [{:2f}]".format(x[0], x[1]) for x in word_prob))
+    torch.cuda.synchronize()
+    dt = time.time() - t0
+    if count <= 0:
+        raise ValueError("subset %s of %s holds no token to score" % (args.gen_subset, args.data))
+    loss = -score_sum / count / math.log(2)  # base 2
+    print("Evaluated {} tokens in {:.1f}s ({:.2f} tokens/s)".format(ntokens, dt, ntokens / max(dt, 1e-9)))
+    print("Loss (base 2): {:.4f}, Perplexity: {:.2f}".format(loss, 2 ** loss))
+    if args.output_word_stats:
+        for ws in sorted(word_stats.values(), key=lambda x: x.count, reverse=True):
+            print(ws)
+    summary = {"event": "eval_lm", "subset": args.gen_subset, "tokens": ntokens, "count": count, "score_sum": score_sum, "loss": loss,
+               "ppl": 2 ** loss, "seconds": dt, "sample_break_mode": getattr(margs, "sample_break_mode", None),
+               "tokens_per_sample": getattr(margs, "tokens_per_sample", None), "ignored_flags": ignored}
+    print(json.dumps(summary), flush=True)
     return summary

@@ -428,3 +428,55 @@ class Wav2vecCriterion(FairseqCriterion):
     @staticmethod
     def logging_outputs_can_be_summed() -> bool:
         return False
+
+
+@register_criterion("cross_entropy")
+class CrossEntropyCriterion(FairseqCriterion):
+    """criterions/cross_entropy.py:21-89 — the language_modeling task's loss: the summed negative log-likelihood of the non-pad
+    targets.  The log-softmax and the gather run in the fused cst_ls_ce kernels at smoothing 0 (no fp32 [B*T, V] log-prob tensor)."""
+    single_pass = True  # one forward pass per sample (trainer.py)
+    derives_from_train_log = True  # derived_metrics reads only keys of the training log: the epoch's train line carries `ppl` too
+
+    def __init__(self, task, sentence_avg):
+        super().__init__(task)
+        self.sentence_avg = sentence_avg
+
+    @classmethod
+    def build_criterion(cls, args, task):
+        return cls(task, getattr(args, "sentence_avg", False))
+
+    def forward(self, model, sample, reduce=True):
+        """:27-46."""
+        net_output = model(**sample["net_input"])
+        loss, _ = self.compute_loss(model, net_output, sample, reduce=reduce)
+        sample_size = sample["target"].size(0) if self.sentence_avg else sample["ntokens"]
+        logging_output = {"loss": loss.data, "ntokens": sample["ntokens"], "nsentences": sample["target"].size(0), "sample_size": sample_size}
+        return loss, sample_size, logging_output
+
+    def compute_loss(self, model, net_output, sample, reduce=True):
+        assert reduce, "reduce=False is not built"
+        loss, _ = CF.label_smoothed_nll_loss(net_output[0], model.get_targets(sample, net_output), 0.0, self.padding_idx)
+        return loss, loss
+
+    @staticmethod
+    def derived_metrics(summed):
+        """:60-80: ppl = 2^(the base-2 loss per token) — of nll_loss = loss / ntokens under --sentence-avg, else of loss."""
+        ntokens, ss = summed.get("ntokens", 0.0), summed.get("sample_size", 0.0)
+        if "loss" not in summed or ntokens <= 0:
+            return {}
+        out = {}
+        if ss != ntokens:
+            out["nll_loss"] = summed["loss"] / ntokens / math.log(2)
+        try:
+            out["ppl"] = round(2 ** (summed["loss"] / ntokens / math.log(2)), 2)
+        except OverflowError:
+            out["ppl"] = float("inf")
+        return out
+
+    @staticmethod
+    def logging_outputs_can_be_summed() -> bool:
+        return True
+
+    @staticmethod
+    def logging_keys():
+        return ("loss", "ntokens", "nsentences", "sample_size")

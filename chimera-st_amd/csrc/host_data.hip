@@ -5,6 +5,9 @@
 //                       (fairseq/data/audio/audio_utils.py:7-55): 16-bit PCM samples / 32768.
 //   cst_edit_distance : Levenshtein distance of two id sequences — editdistance.eval in the CTC criterion's validation
 //                       (fairseq/criterions/ctc.py:150-170)
+//   cst_token_block_slices / cst_token_block_index : the block cuts of the language_modeling task and their sentence index — the
+//                       reference's Cython token_block_utils_fast (_get_slice_indices_fast, _get_block_to_dataset_index_fast;
+//                       fairseq/data/token_block_dataset.py:78-100)
 #include "cst_common.h"
 #include <stdio.h>
 #include <stdlib.h>
@@ -148,6 +151,84 @@ int64_t cst_edit_distance(const int64_t* a, int64_t na, const int64_t* b, int64_
   const int64_t d = row[nb];
   free(row);
   return d;
+}
+
+int64_t cst_token_block_slices(const int64_t* sizes, int64_t n, int break_mode, int64_t block_size, int64_t document_sep_len,
+                               int64_t* slices_out, int64_t capacity) {
+  if (!sizes || n < 1 || break_mode < CST_BREAK_NONE || break_mode > CST_BREAK_EOS || (break_mode != CST_BREAK_EOS && block_size < 1)) {
+    cst_set_error("cst_token_block_slices: bad argument (n %lld mode %d block_size %lld)", (long long)n, break_mode, (long long)block_size);
+    return CST_ERR_BAD_ARG;
+  }
+  for (int64_t i = 0; i < n; ++i)
+    if (sizes[i] < 0) { cst_set_error("cst_token_block_slices: sentence %lld has a negative size", (long long)i); return CST_ERR_BAD_ARG; }
+  int64_t nb = 0;
+  bool full = false;
+  auto emit = [&](int64_t s, int64_t e) {
+    if (slices_out) {
+      if (nb < capacity) { slices_out[2 * nb] = s; slices_out[2 * nb + 1] = e; } else full = true;
+    }
+    ++nb;
+  };
+  if (break_mode == CST_BREAK_NONE) {
+    int64_t total = 0;
+    for (int64_t i = 0; i < n; ++i) total += sizes[i];
+    for (int64_t s = 0; s < total; s += block_size) emit(s, s + block_size < total ? s + block_size : total);
+  } else if (break_mode == CST_BREAK_EOS) {
+    int64_t s = 0;
+    for (int64_t i = 0; i < n; ++i) { emit(s, s + sizes[i]); s += sizes[i]; }
+  } else {
+    // a block is open from `start` with `cur` tokens; a sentence joins it while it fits (always, into an empty block)
+    const bool doc = break_mode == CST_BREAK_COMPLETE_DOC;
+    const int64_t keep_above = doc ? 1 : 0;  // complete_doc keeps documents of more than one token only
+    int64_t start = 0, cur = 0;
+    for (int64_t i = 0; i < n; ++i) {
+      const int64_t sz = sizes[i];
+      if (doc && sz == document_sep_len) {  // the document ends: close the block; the separator's tokens belong to no block
+        if (cur > keep_above) emit(start, start + cur);
+        start += cur + sz;
+        cur = 0;
+        continue;
+      }
+      if (cur != 0 && cur + sz > block_size) {
+        if (cur > keep_above) emit(start, start + cur);
+        start += cur;
+        cur = 0;
+      }
+      cur += sz;
+    }
+    if (cur > keep_above) emit(start, start + cur);
+  }
+  if (full) { cst_set_error("cst_token_block_slices: %lld blocks, capacity %lld", (long long)nb, (long long)capacity); return CST_ERR_WORKSPACE; }
+  return nb;
+}
+
+int cst_token_block_index(const int64_t* sizes, int64_t n, const int64_t* slices, int64_t n_blocks, int64_t* out) {
+  if (!sizes || !slices || !out || n < 1 || n_blocks < 0) { cst_set_error("cst_token_block_index: bad argument"); return CST_ERR_BAD_ARG; }
+  int64_t total = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    if (sizes[i] < 1) { cst_set_error("cst_token_block_index: sentence %lld has %lld tokens", (long long)i, (long long)sizes[i]); return CST_ERR_BAD_ARG; }
+    total += sizes[i];
+  }
+  // sentence `k` covers the stream elements [base, base + sizes[k]); blocks rise, so the cursor moves forward and restarts only
+  // when a slice begins before it
+  int64_t k = 0, base = 0;
+  auto seek = [&](int64_t pos) {
+    if (pos < base) { k = 0; base = 0; }
+    while (pos >= base + sizes[k]) { base += sizes[k]; ++k; }
+  };
+  for (int64_t b = 0; b < n_blocks; ++b) {
+    const int64_t s = slices[2 * b], e = slices[2 * b + 1];
+    if (s < 0 || s >= total || e > total) {
+      cst_set_error("cst_token_block_index: block %lld [%lld, %lld) is outside the %lld tokens", (long long)b, (long long)s, (long long)e, (long long)total);
+      return CST_ERR_BAD_ARG;
+    }
+    seek(s);
+    out[3 * b] = k;
+    out[3 * b + 1] = s - base;
+    if (e > s) seek(e - 1);
+    out[3 * b + 2] = k;
+  }
+  return CST_OK;
 }
 
 }  // extern "C"

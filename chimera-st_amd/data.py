@@ -579,8 +579,8 @@ class EpochBatchIterator:
             for b in batches:
                 sample = self.dataset.collater([self.dataset[i] for i in b])
                 # (a record of the resident translation route holds indices only and is staged by the trainer's thread:
-                # language_pair_dataset.ResidentPairs — no HIP call is made for it here)
-                if self.pin_memory and sample and "pair_idx" not in (sample.get("net_input") or {}):
+                # language_pair_dataset.ResidentPairs, monolingual_dataset.ResidentBlocks — no HIP call is made for it here)
+                if self.pin_memory and sample and not {"pair_idx", "block_idx"} & set(sample.get("net_input") or {}):
                     sample = _pin(sample)
                 yield sample
         return _buffered(gen(), buffer_size) if buffer_size > 0 else gen()

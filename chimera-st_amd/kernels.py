@@ -1175,3 +1175,28 @@ def collate_pairs(src_stream, tgt_stream, tok_dtype, src_off, tgt_off, idx, S, T
                                        L.ptr(out), L.stream_ptr()), "cst_collate_pairs")
     a, b = B * S, B * S + B * T
     return out[:a].view(B, S), out[b + B * T:], out[a:b].view(B, T), out[b:b + B * T].view(B, T), out
+
+
+def collate_blocks(stream, tok_dtype, blocks, idx, T, pad, eos, out=None):
+    """One language_modeling batch from a device-resident binarised corpus (cst_collate_blocks).  stream: a uint8 tensor holding the
+    token stream's BYTES as stored (`tok_dtype` names the element type); blocks int64 [n_blocks, 3] = (start element, length, prev:
+    the element before the block in its source row, negative = the dictionary's eos); idx int64 [B] block indices in row order.
+    Returns (src_tokens [B, T], src_lengths [B], target [B, T], buffer): int64 views of ONE buffer (`out`, int64 [2*B*T + B],
+    allocated when not given); every word is written."""
+    B = idx.numel()
+    for t in (blocks, idx):
+        if t.dtype != torch.int64 or not t.is_contiguous():
+            raise ValueError("collate_blocks: blocks and indices must be contiguous int64 tensors")
+    if blocks.dim() != 2 or blocks.size(1) != 3:
+        raise ValueError("collate_blocks: blocks must be [n_blocks, 3], got %s" % (tuple(blocks.shape),))
+    if stream.dtype != torch.uint8:
+        raise ValueError("collate_blocks: the token stream is passed as its bytes (a uint8 tensor)")
+    total = 2 * B * T + B
+    if out is None:
+        out = torch.empty(total, dtype=torch.int64, device=idx.device)
+    elif out.dtype != torch.int64 or out.numel() != total or not out.is_contiguous():
+        raise ValueError("collate_blocks: out must be a contiguous int64 tensor of %d words" % total)
+    L.check(L.load().cst_collate_blocks(L.ptr(stream), int(tok_dtype), L.ptr(blocks), blocks.size(0), L.ptr(idx), B, int(T), int(pad),
+                                        int(eos), L.ptr(out), L.stream_ptr()), "cst_collate_blocks")
+    a = B * T
+    return out[:a].view(B, T), out[2 * a:], out[a:2 * a].view(B, T), out

@@ -232,6 +232,9 @@ SYMBOLS = [
     ("cst_attn_avg_probs", c_int, [c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_f, c_f,
                                    c_int, c_int, c_p]),
     ("cst_collate_pairs", c_int, [c_p, c_p, c_int, c_p, c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_int, c_int, c_p, c_p]),
+    ("cst_token_block_slices", c_i64, [c_p, c_i64, c_int, c_i64, c_i64, c_p, c_i64]),
+    ("cst_token_block_index", c_int, [c_p, c_i64, c_p, c_i64, c_p]),
+    ("cst_collate_blocks", c_int, [c_p, c_int, c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_p]),
 ]
 
 _lib = None

@@ -8,8 +8,9 @@ An ensemble averages the members' probabilities of the target token: score = log
 probabilities and takes the log (:96-111) — the same number wherever that is finite; the log-domain form does not turn into -inf when
 every member's probability underflows fp32.
 
-Out of scope: `softmax_batch` (chunked softmax) and `sample["start_indices"]` — both serve the language-model tasks, which this
-package does not have.  The speech decoders return no attention (TransformerDecoderScriptable.extract_features returns x, None), so
+A language model is scored the same way (fairseq_eval_lm.py: its net_input is src_tokens / src_lengths, its logits the next-token
+distributions).  Not built: `softmax_batch` (chunked softmax — nothing of size [B, T, V] is materialised in fp32 here, so there is
+nothing to chunk) and `sample["start_indices"]` (--context-window).  The speech decoders return no attention (TransformerDecoderScriptable.extract_features returns x, None), so
 `attention` and `alignment` are None, as they are from SequenceGenerator."""
 import math
 

@@ -1,7 +1,8 @@
 """Mirror of the task surface the hot path is called through: fairseq/tasks/fairseq_task.py (build_model :265-281,
 build_criterion :283-298, train_step :414-445, valid_step :447-451, inference_step :453-459, build_generator
-:309-412), fairseq/tasks/speech_to_text.py (:27-154), fairseq/tasks/triplet.py (:23-241) and fairseq/tasks/translation.py (:164-475:
-the MT pre-training stage on binarised parallel text, with BLEU during validation).
+:309-412), fairseq/tasks/speech_to_text.py (:27-154), fairseq/tasks/triplet.py (:23-241), fairseq/tasks/translation.py (:164-475:
+the MT pre-training stage on binarised parallel text, with BLEU during validation) and fairseq/tasks/language_modeling.py (:96-328: the
+fusion language model on binarised monolingual text).
 
 Datasets / TSV manifests / audio decoding are a "next" row; this build provides the collater's
 `sample` dict layout (data/audio/triplet_dataset.py:220-234) through `synthetic_sample`, the same shapes the
@@ -498,3 +499,114 @@ class AudioPretrainingTask(FairseqTask):
     def max_positions(self):
         import sys
         return sys.maxsize, sys.maxsize
+
+
+@register_task("language_modeling")
+class LanguageModelingTask(FairseqTask):
+    """tasks/language_modeling.py:96-328 — a left-to-right language model on a binarised monolingual corpus (indexed_dataset.py,
+    monolingual_dataset.py): `<data>/dict.txt`, `<data>/<split>.{bin,idx}`.  Trains the model `fairseq_generate.py --lm-path` fuses
+    and fairseq_eval_lm.py scores.  Refused by name: what a fusion LM does not use."""
+    BREAK_MODES = ("none", "complete", "complete_doc", "eos")
+    # (args attribute, the flag to name, the value that is built)
+    _REFUSED = (("output_dictionary_size", "--output-dictionary-size", -1), ("self_target", "--self-target", False),
+                ("past_target", "--past-target", False), ("add_bos_token", "--add-bos-token", False),
+                ("shorten_method", "--shorten-method", "none"))
+
+    @staticmethod
+    def add_args(parser):
+        """language_modeling.py:40-93, with the dataset option the reference keeps among its common ones."""
+        parser.add_argument("data", help="path to the binarised data directory")
+        parser.add_argument("--sample-break-mode", default="none", choices=list(LanguageModelingTask.BREAK_MODES),
+                            help="none: blocks of --tokens-per-sample tokens; complete: whole sentences up to that many tokens; "
+                            "complete_doc: the same within documents (blank lines separate them); eos: one sentence per block")
+        parser.add_argument("--tokens-per-sample", default=1024, type=int, help="max number of tokens per sample for LM dataset")
+        parser.add_argument("--output-dictionary-size", default=-1, type=int, help="(not built)")
+        parser.add_argument("--self-target", action="store_true", help="(not built)")
+        parser.add_argument("--future-target", action="store_true", help="include future target (what this build always does)")
+        parser.add_argument("--past-target", action="store_true", help="(not built)")
+        parser.add_argument("--add-bos-token", action="store_true", help="(not built)")
+        parser.add_argument("--max-target-positions", default=None, type=int, metavar="N", help="max number of tokens in the target sequence")
+        parser.add_argument("--shorten-method", default="none", help="(values other than none are not built)")
+        parser.add_argument("--shorten-data-split-list", default="")
+        parser.add_argument("--dataset-impl", default=None, metavar="FORMAT", help="mmap (the other implementations are not built)")
+
+    def __init__(self, args, dictionary):
+        super().__init__(args)
+        self.dictionary = dictionary
+        self.targets = ["future"]
+        self.datasets = {}
+
+    @classmethod
+    def check_args(cls, args):
+        for attr, flag, built in cls._REFUSED:
+            v = getattr(args, attr, built)
+            if v is None or v == built or (attr == "output_dictionary_size" and v < 0):
+                continue
+            raise NotImplementedError("language_modeling: %s%s is not built: the model predicts the next token over the whole "
+                                      "dictionary from the tokens before it" % (flag, "" if v is True else " %s" % v))
+        if getattr(args, "exclude_self_target", True) is False:  # (an old checkpoint's spelling of --self-target)
+            raise NotImplementedError("language_modeling: --self-target is not built")
+        mode = getattr(args, "sample_break_mode", "none") or "none"
+        if mode not in cls.BREAK_MODES:
+            raise ValueError("--sample-break-mode %r: one of %s" % (mode, ", ".join(cls.BREAK_MODES)))
+        from . import indexed_dataset as ID
+        ID.check_dataset_impl(getattr(args, "dataset_impl", None))
+
+    @classmethod
+    def setup_task(cls, args, **kwargs):
+        """language_modeling.py:135-175."""
+        cls.check_args(args)
+        dictionary = kwargs.pop("dictionary", None)
+        data = getattr(args, "data", None)
+        if dictionary is None and not data:  # a checkpoint whose data directory is not reachable: ids only
+            dictionary = Dictionary.synthetic(getattr(args, "synthetic_vocab_size", 10000))
+        if dictionary is None:
+            from . import language_pair_dataset as P
+            paths = P.split_paths(data)
+            if len(paths) > 1:
+                raise NotImplementedError("several colon-separated data paths (%d given) are not built: the round-robin over data "
+                                          "shards of the reference's language_modeling task; pass one directory" % len(paths))
+            dictionary = Dictionary.load(os.path.join(paths[0], "dict.txt"))
+        return cls(args, dictionary)
+
+    def load_dataset(self, split, epoch=1, combine=False, **kwargs):
+        """language_modeling.py:188-241: split -> indexed dataset -> token blocks -> MonolingualDataset.  The split's route of batch
+        assembly (device-resident corpus or host collater) is decided here."""
+        from . import indexed_dataset as ID
+        from . import monolingual_dataset as M
+        a = self.args
+        prefix = os.path.join(a.data, split)
+        if not ID.dataset_exists(prefix):
+            if os.path.exists(prefix + ".txt"):
+                raise NotImplementedError("%s.txt: the `raw` dataset implementation is not built; binarise with --dataset-impl mmap" % prefix)
+            raise FileNotFoundError("Dataset not found: {} ({})".format(split, prefix))
+        if ID.dataset_exists(prefix + "1"):
+            raise NotImplementedError("%s1: sharded splits (train, train1, ...) are not built; binarise the corpus as one split" % prefix)
+        corpus = ID.MMapIndexedDataset(prefix)
+        blocks = M.TokenBlockDataset(corpus, corpus.sizes, getattr(a, "tokens_per_sample", 1024), pad=self.dictionary.pad(),
+                                     eos=self.dictionary.eos(), break_mode=getattr(a, "sample_break_mode", "none"), include_targets=True)
+        ds = M.MonolingualDataset(blocks, blocks.sizes, self.dictionary, shuffle=True)
+        ds.enable_resident()
+        self.datasets[split] = ds
+        return ds
+
+    def build_model(self, args):
+        """:177-186."""
+        model = super().build_model(args)
+        for target in self.targets:
+            if target not in model.supported_targets:
+                raise ValueError("Unsupported language modeling target: {}".format(target))
+        return model
+
+    def max_positions(self):
+        """The target limit: --max-target-positions, else --tokens-per-sample (what the model is built with)."""
+        v = getattr(self.args, "max_target_positions", None)
+        return v if v is not None else getattr(self.args, "tokens_per_sample", 1024)
+
+    @property
+    def source_dictionary(self):
+        return self.dictionary
+
+    @property
+    def target_dictionary(self):
+        return self.dictionary

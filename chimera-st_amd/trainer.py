@@ -125,7 +125,8 @@ class Trainer:
     def _prepare_sample(self, sample):
         """trainer.py:896-932: H2D; the waveform stays fp32 (conv0 reads it directly), token tensors stay int64.  A batch of the
         fbank route (net_input["src_audio"], data.py) gets its filter banks computed on the device here (fbank.materialize); a
-        translation batch of a device-resident corpus arrives as indices and is assembled here (language_pair_dataset.ResidentPairs)."""
+        translation batch of a device-resident corpus arrives as indices and is assembled here (language_pair_dataset.ResidentPairs), and
+        so does a language_modeling batch (monolingual_dataset.ResidentBlocks)."""
         def mv(x):
             if torch.is_tensor(x):
                 return x.to(self.device, non_blocking=True)
@@ -136,6 +137,8 @@ class Trainer:
         ni = sample.get("net_input") if isinstance(sample, dict) else None
         if ni and "pair_idx" in ni:  # a record of the resident translation route: the batch is assembled on the device, one launch
             return ni["pair_corpus"].materialize(sample, self.device)
+        if ni and "block_idx" in ni:  # a record of the resident language_modeling route: likewise (cst_collate_blocks)
+            return ni["block_corpus"].materialize(sample, self.device)
         out = mv(sample)
         if ni and "src_audio" in ni:
             out["net_input"] = fbank.materialize(out["net_input"], max_frames=int(ni["src_lengths"].max()))

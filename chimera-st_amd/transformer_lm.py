@@ -1,13 +1,13 @@
-"""Target-side Transformer language model for shallow fusion in decoding (`--lm-path`, `--lm-weight`) — mirror of
+"""Target-side Transformer language model: trained by the `language_modeling` task (tasks.py, criterion `cross_entropy`), scored by
+fairseq_eval_lm.py and used for shallow fusion in decoding (`--lm-path`, `--lm-weight`) — mirror of
 fairseq/models/transformer_lm.py (TransformerLanguageModel :165-246, base_lm_architecture :250-306 and the named architectures)
 and fairseq/models/fairseq_model.py FairseqLanguageModel: a TransformerDecoder WITHOUT encoder attention over the target dictionary.
 
 The state_dict keys are the reference's (`decoder.embed_tokens.weight`, `decoder.layers.<i>.self_attn.*`, `decoder.layers.<i>.fc1.*`,
-`decoder.layer_norm.*`, `decoder.output_projection.weight`, ...), so a reference LM checkpoint loads strictly.  The model is used for
-inference only: sequence_generator.py adds lm_weight x its next-token log-softmax to the translation model's log-probabilities
-(reference sequence_generator.py:318-324); on the device engine it is one more decoder of the step (decode_engine.py).  Training an LM
-is out of scope: there is no language_modeling task.  Adaptive input / softmax, character embeddings and learned positions are refused
-by name."""
+`decoder.layer_norm.*`, `decoder.output_projection.weight`, ...), so a reference LM checkpoint loads strictly, and one written here
+loads in the reference.  In decoding, sequence_generator.py adds lm_weight x its next-token log-softmax to the translation model's
+log-probabilities (reference sequence_generator.py:318-324); on the device engine it is one more decoder of the step
+(decode_engine.py).  Adaptive input / softmax, character embeddings and learned positions are refused by name."""
 from .fairseq_model import BaseFairseqModel
 from .registry import register_model, register_model_architecture
 from .s2t_transformer import TransformerDecoder, build_embedding
@@ -43,7 +43,8 @@ class TransformerLanguageModel(BaseFairseqModel):
         parser.add_argument("--no-token-positional-embeddings", action="store_true")
         parser.add_argument("--share-decoder-input-output-embed", action="store_true")
         parser.add_argument("--no-scale-embedding", action="store_true")
-        parser.add_argument("--tokens-per-sample", type=int)
+        # (--tokens-per-sample and --max-target-positions are the language_modeling task's flags, as in the reference, where the
+        # model reads them from the task's configuration; build_model below takes the position limit from them)
 
     @classmethod
     def build_model(cls, args, task):

@@ -1015,6 +1015,51 @@ int cst_collate_pairs(const void* src_stream, const void* tgt_stream, int tok_dt
                       const int64_t* tgt_offsets, int64_t n_sentences, const int64_t* idx, int64_t B, int64_t S, int64_t T, int64_t pad,
                       int64_t eos, int left_pad_source, int left_pad_target, int64_t* out, cst_stream stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Token blocks of the `language_modeling` task (added at ABI 13 without a bump: pure additions).
+ *
+ * Host natives (no device work, no stream) — they replace the reference's Cython token_block_utils_fast
+ * (_get_slice_indices_fast and _get_block_to_dataset_index_fast, called by TokenBlockDataset.__init__,
+ * fairseq/data/token_block_dataset.py:78-100):
+ * cst_token_block_slices cuts a corpus of n sentences of sizes[i] tokens into blocks; slices_out (capacity `capacity` blocks,
+ *   int64 [.., 2]) receives per block (first stream element, one past the last); returns the block count or a negative cst_status.
+ *   slices_out = NULL returns the count only.  break_mode:
+ *     CST_BREAK_NONE          ceil(total / block_size) equal blocks of block_size tokens, the last one short;
+ *     CST_BREAK_COMPLETE      whole sentences, greedily, up to block_size; a sentence longer than block_size is a block of its own;
+ *     CST_BREAK_COMPLETE_DOC  as COMPLETE, and a sentence of exactly document_sep_len tokens ends the document: the block before it
+ *                             is closed, its own tokens belong to no block; blocks of <= 1 token are dropped;
+ *     CST_BREAK_EOS           one block per sentence (block_size is not read).
+ *   sizes NULL, n < 1, a negative size, block_size < 1 in a mode that reads it, an unknown mode: CST_ERR_BAD_ARG; more blocks than
+ *   `capacity`: CST_ERR_WORKSPACE.
+ * cst_token_block_index writes, per block, out[3 i ..] = (index of the sentence holding the block's first token, the offset of that
+ *   token inside the sentence, index of the sentence holding the block's last token); an empty block ends in its first sentence.
+ *   Slices must lie inside the corpus and sentences must not be empty (the reference asserts the same): CST_ERR_BAD_ARG otherwise.
+ *
+ * cst_collate_blocks replaces MonolingualDataset.collater over TokenBlockDataset.__getitem__ on a device-resident binarised corpus
+ * (fairseq/data/monolingual_dataset.py:12-53 collate, data_utils.py collate_tokens :34-64, token_block_dataset.py:121-149: the
+ * "future" target and its right-shifted source):
+ *   stream: the split's ONE token stream as stored, of type tok_dtype.
+ *   blocks: int64 [n_blocks, 3] = (first stream element, length, prev).  prev is the stream element whose token precedes the block in
+ *     its source row — start - 1 when the block begins inside a sentence — or negative when the block begins at a sentence's first
+ *     token: the source row then starts with `eos`, the DICTIONARY's, whatever token ends the sentence before
+ *     (token_block_dataset.py:137-138).  The caller guarantees that start, start + length and prev lie inside the stream.
+ *   idx: int64 [B] block indices in row order.
+ *   out: int64 [2*B*T + B], 16-byte aligned = src_tokens [B, T] | target [B, T] | src_lengths [B].  With n = min(length, T):
+ *     target[b, j] = stream[start + j] for j < n;  src_tokens[b, 0] = eos or stream[prev];  src_tokens[b, j] = stream[start + j - 1]
+ *     for 1 <= j < n;  pad beyond n (right padding only);  src_lengths[b] = n.  Every word is written.
+ *   An idx outside [0, n_blocks) gives an all-pad row and length 0 and reads no token.
+ * One launch, no atomics, every word a pure function of its index: bit-reproducible.  Token loads are one element wide; stores are
+ * 16 bytes, the lone last word of an odd total is stored alone.
+ * A null operand, a bad tok_dtype, B / T / n_blocks < 1, B * (2T + 1) > 2^31, a misaligned out or stream: CST_ERR_BAD_ARG, nothing
+ * is launched.
+ * ------------------------------------------------------------------------------------------ */
+typedef enum { CST_BREAK_NONE = 0, CST_BREAK_COMPLETE = 1, CST_BREAK_COMPLETE_DOC = 2, CST_BREAK_EOS = 3 } cst_break_mode;
+int64_t cst_token_block_slices(const int64_t* sizes, int64_t n, int break_mode, int64_t block_size, int64_t document_sep_len,
+                               int64_t* slices_out, int64_t capacity);
+int cst_token_block_index(const int64_t* sizes, int64_t n, const int64_t* slices, int64_t n_blocks, int64_t* out);
+int cst_collate_blocks(const void* stream_tokens, int tok_dtype, const int64_t* blocks, int64_t n_blocks, const int64_t* idx, int64_t B,
+                       int64_t T, int64_t pad, int64_t eos, int64_t* out, cst_stream stream);
+
 #ifdef __cplusplus
 }
 #endif
