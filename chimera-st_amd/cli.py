@@ -4,6 +4,8 @@ drive this build unchanged:
 
   python fairseq_train.py <data> --task triplet --arch s2t_transformer_w2v2_interlingua_base --config-yaml config_wave.yaml ...
   python fairseq_generate.py <data> --task triplet --path ckpt.pt --gen-subset tst-COMMON_wave --beam 10 --lenpen 1.5 ...
+  python fairseq_interactive.py <data> --task triplet --config-yaml config_wave.yaml --path ckpt.pt   (fairseq_cli/interactive.py:42-307,
+                                chimera/scripts/interactive-en2any-ST.sh: typed audio paths; sentences and LM prompts on those checkpoints)
 
 `--fp16` selects the reduced-precision path of this hardware: bf16 storage with fp32 accumulation (no loss scaling).  One
 process per GPU (torchrun-style env: RANK / WORLD_SIZE / LOCAL_RANK); each rank reads its own shard of the epoch's batches."""
@@ -625,4 +627,258 @@ def eval_lm_main(argv=None):
                "ppl": 2 ** loss, "seconds": dt, "sample_break_mode": getattr(margs, "sample_break_mode", None),
                "tokens_per_sample": getattr(margs, "tokens_per_sample", None), "ignored_flags": ignored}
     print(json.dumps(summary), flush=True)
+    return summary
+
+
+# --------------------------------------------------------------------------------------------------------------------
+def buffered_read(input, buffer_size):
+    """fairseq_cli/interactive.py:42-52: the stripped lines of `input` ("-": stdin) in lists of buffer_size; the last may be shorter."""
+    buffer = []
+    h = sys.stdin if input == "-" else open(input, encoding="utf-8")
+    try:
+        for src_str in h:
+            buffer.append(src_str.strip())
+            if len(buffer) >= buffer_size:
+                yield buffer
+                buffer = []
+    finally:
+        if h is not sys.stdin:
+            h.close()
+    if len(buffer) > 0:
+        yield buffer
+
+
+def interactive_parser():
+    """The options of fairseq_interactive.py: the decoding flags of generate_parser() under the same names and defaults, and
+    fairseq-interactive's own.  --max-source-positions / --max-target-positions default to the checkpoint's here: the limits of a
+    language model are its training run's."""
+    p = generate_parser()
+    p.set_defaults(max_source_positions=None, max_target_positions=None)
+    p.add_argument("--buffer-size", type=int, default=0, help="read this many sentences before processing them")
+    p.add_argument("--input", default="-", help="file to read from; use - for stdin")
+    p.add_argument("--bpe", default=None, help="the BPE of a text task's lines (sentencepiece); the speech tasks take theirs from the config YAML")
+    p.add_argument("--sentencepiece-model", default=None, help="path to the sentencepiece model (--bpe sentencepiece)")
+    p.add_argument("--tokenizer", default=None, help="the pre-tokenizer of a text task's lines")
+    p.add_argument("--skip-invalid-size-inputs-valid-test", action="store_true", help="ignore lines beyond the model's positions")
+    return p
+
+
+def check_interactive_args(args):
+    """fairseq_cli/interactive.py:117-128 and what this driver refuses by name — before any checkpoint is read."""
+    if args.buffer_size < 1:
+        args.buffer_size = 1
+    if args.max_tokens is None and args.batch_size is None:
+        args.batch_size = 1
+    assert not args.sampling or args.nbest == args.beam, "--sampling requires --nbest to be equal to --beam"
+    assert not args.batch_size or args.batch_size <= args.buffer_size, "--batch-size cannot be larger than --buffer-size"
+    if args.score_reference:
+        raise NotImplementedError("--score-reference is not built for typed input: a typed line has no reference (fairseq_generate.py scores a subset's)")
+    if args.prefix_size > 0:
+        raise NotImplementedError("--prefix-size %d is not built for typed input: a typed line has no reference to take a prefix from" % args.prefix_size)
+    if args.constraints_file is not None:
+        raise ValueError("--constraints-file belongs to fairseq_generate.py: here the phrases follow the source on its line, after a tab")
+    from . import data as D
+    D.build_tokenizer({"tokenizer": args.tokenizer})  # (refuses by name what is not built)
+    if args.bpe not in (None, "none", "sentencepiece"):
+        D.build_bpe({"bpe": args.bpe})
+    if args.bpe == "sentencepiece" and not args.sentencepiece_model:
+        raise ValueError("--bpe sentencepiece needs --sentencepiece-model")
+    generic = argparse.Namespace(**vars(args))
+    generic.constraints_file = "-" if args.constraints is not None else None  # (the pairing rule of fairseq_generate.py does not apply)
+    check_generate_args(generic)
+    return args
+
+
+def resolve_max_positions(*limits):
+    """utils.resolve_max_positions for ints and (source, target) pairs: the element-wise minimum, None = no limit."""
+    out = None
+    for v in limits:
+        if v is None:
+            continue
+        if out is None:
+            out = v
+        elif isinstance(v, (int, float)) and isinstance(out, (int, float)):
+            out = min(out, v)
+        else:
+            a = out if isinstance(out, (tuple, list)) else (out, out)
+            b = v if isinstance(v, (tuple, list)) else (v, v)
+            out = tuple(x if y is None else y if x is None else min(x, y) for x, y in zip(a, b))
+    return out
+
+
+def split_constraints(lines, tgt_dict, encode_fn):
+    """fairseq_cli/interactive.py:59-76: (the sources, per line its constraints as lists of token ids) of lines
+    `source<TAB>phrase<TAB>phrase...`; a phrase is encoded like target text, without new symbols and without eos."""
+    sources, lists = [], []
+    for line in lines:
+        src, *phrases = line.split("\t") if "\t" in line else [line]
+        sources.append(src)
+        lists.append([tgt_dict.encode_line(encode_fn(ph), append_eos=False, add_if_not_exist=False).long().tolist() for ph in phrases])
+    return sources, lists
+
+
+def lm_prompt_limit(n, max_len_a, max_len_b, max_decoder_positions):
+    """Whether a prompt of n tokens fits the generator's step limit in ANY batch: max_len of a batch is computed from its width, at least
+    this prompt's own 1 + n (sequence_generator.py:228-232), and the forced prefix may be exactly max_len wide."""
+    return n <= min(int(max_len_a * (n + 1) + max_len_b), max_decoder_positions - 1)
+
+
+def make_batches(lines, args, task, max_positions, encode_fn, start_id=0, err=None, prompt_ok=None):
+    """fairseq_cli/interactive.py:55-105 — yields (ids, the collated batch, its constraints as lists or None): the task's
+    get_interactive_tokens_and_lengths, build_dataset_for_inference and get_batch_iterator(shuffle=False); ids are positions in `lines`.
+    DIFFERENCES to the reference: a line the task cannot read (a missing, unreadable or non-PCM audio file) is named on `err` with its id
+    and left out instead of ending the session; prompt_ok (language models): a predicate on a prompt's token count — a prompt that fails
+    it is reported the same way, and EMPTY prompts (eos alone) are batched apart from the others: they decode without a prefix."""
+    err = sys.stderr if err is None else err
+    lists = None
+    if args.constraints:
+        lines, lists = split_constraints(lines, task.target_dictionary, encode_fn)
+    groups = {}
+    for pos, line in enumerate(lines):
+        try:
+            tokens, lengths = task.get_interactive_tokens_and_lengths([line], encode_fn)
+        except (FileNotFoundError, ValueError, OSError) as e:
+            print("input %d skipped: %s" % (start_id + pos, e), file=err, flush=True)
+            continue
+        key = 0
+        beyond = isinstance(max_positions, (int, float)) and lengths[0] > max_positions  # (the iterator raises on it, or skips it)
+        if prompt_ok is not None and not beyond:
+            n = int(lengths[0]) - 1  # (without the eos encode_line appended)
+            if not prompt_ok(n):
+                print("input %d skipped: a prompt of %d tokens exceeds the step limit max_len (--max-len-a, --max-len-b, the model's "
+                      "positions)" % (start_id + pos, n), file=err, flush=True)
+                continue
+            key = int(n == 0)
+        g = groups.setdefault(key, ([], [], []))
+        g[0].append(pos), g[1].append(tokens[0]), g[2].append(lengths[0])
+    for key in sorted(groups):
+        positions, tokens, lengths = groups[key]
+        itr = task.get_batch_iterator(dataset=task.build_dataset_for_inference(tokens, lengths), max_tokens=args.max_tokens,
+                                      max_sentences=args.batch_size, max_positions=max_positions,
+                                      ignore_invalid_inputs=args.skip_invalid_size_inputs_valid_test).next_epoch_itr(shuffle=False)
+        for batch in itr:
+            if not batch:
+                continue
+            ids = [positions[i] for i in batch["id"].tolist()]
+            yield ids, batch, (None if lists is None else [lists[i] for i in ids])
+
+
+def print_translations(results, args, src_dict, tgt_dict, decode_fn, strip=(), out=None):
+    """fairseq_cli/interactive.py:250-298, the lines of one buffer in input order.  results: (id, src_tokens or None, hypos, info) with
+    info = {"constraints": lists of token ids, "time": seconds}; src_tokens None (a float source: audio) prints no S-/W-/C- line.  Scores
+    are divided by ln 2 in fp32 on the host, as the reference's tensors are, and printed with `{}`; P- with %.4f."""
+    out = sys.stdout if out is None else out
+    ntok = 0
+    for id_, src_tokens, hypos, info in sorted(results, key=lambda x: x[0]):
+        if src_dict is not None and src_tokens is not None:
+            print("S-{}\t{}".format(id_, src_dict.string(src_tokens, args.post_process)), file=out)
+            print("W-{}\t{:.3f}\tseconds".format(id_, info["time"]), file=out)
+            for constraint in info["constraints"]:
+                print("C-{}\t{}".format(id_, tgt_dict.string(constraint, args.post_process)), file=out)
+        for j, hypo in enumerate(hypos[:min(len(hypos), args.nbest)]):
+            tokens = torch.as_tensor(hypo["tokens"]).int().cpu()
+            hypo_str = tgt_dict.string(tokens, args.post_process, extra_symbols_to_ignore=strip)
+            detok_hypo_str = decode_fn(hypo_str).replace("<unk>", " ")
+            score = torch.as_tensor(hypo["score"]).detach().float().cpu() / math.log(2)  # convert to base 2
+            print("H-{}\t{}\t{}".format(id_, score, hypo_str), file=out)
+            print("D-{}\t{}\t{}".format(id_, score, detok_hypo_str), file=out)
+            pos = torch.as_tensor(hypo["positional_scores"]).detach().float().cpu().div(math.log(2)).tolist()
+            print("P-{}\t{}".format(id_, " ".join(map(lambda x: "{:.4f}".format(x), pos))), file=out)
+            if args.print_alignment:
+                pairs = hard_alignment(hypo["attention"], hypo["tokens"], tgt_dict.pad(), tgt_dict.eos())
+                print("A-{}\t{}".format(id_, " ".join("{}-{}".format(s, t) for s, t in pairs)), file=out)
+            if j == 0:
+                ntok += len(tokens)
+    out.flush()
+    return ntok
+
+
+def interactive_main(argv=None):
+    """fairseq_cli/interactive.py:108-307: translate typed audio paths (tasks speech_to_text / triplet), sentences (translation) or
+    language-model prompts (language_modeling), one buffer at a time.  Stdout carries the S-/W-/C-/H-/D-/P-/A- lines and nothing else;
+    skipped lines and the closing JSON summary go to stderr."""
+    argv = list(sys.argv[1:] if argv is None else argv)
+    args, ignored = interactive_parser().parse_known_args(argv)
+    check_interactive_args(args)
+    limit_host_threads()
+    start_time, total_translate_time = time.time(), 0.0
+    overrides = {"data": args.data, "config_yaml": args.config_yaml}
+    if args.max_source_positions is not None:
+        overrides["max_source_positions"] = args.max_source_positions
+    if args.max_target_positions is not None:
+        overrides["max_target_positions"] = args.max_target_positions
+    models, margs, task = checkpoint_utils.load_model_ensemble_and_task(args.path.split(":"), arg_overrides=overrides)
+    kind = getattr(margs, "task", None)
+    is_lm, is_speech = kind == "language_modeling", hasattr(task, "data_cfg")
+    if args.constraints is not None and (is_lm or is_speech):
+        raise NotImplementedError("--constraints is not built for task %s: a typed line is an audio path or a prompt, and the phrases "
+                                  "of --constraints follow a source SENTENCE after a tab" % kind)
+    if is_lm and args.print_alignment:
+        raise ValueError("--print-alignment needs cross attention: the model of %s is a language model" % args.path)
+    if is_lm and args.lm_path is not None:
+        raise ValueError("--lm-path: the model of %s is itself a language model; decode the two as an ensemble (--path a.pt:b.pt)" % args.path)
+    dtype = torch.bfloat16 if (args.fp16 or args.bf16) else torch.float32
+    models = [m.to("cuda", dtype).eval() for m in models]
+    src_dict, tgt_dict = task.source_dictionary, task.target_dictionary
+    lm = None
+    if args.lm_path is not None:
+        lm = checkpoint_utils.load_language_model(args.lm_path, tgt_dict).to("cuda", dtype).eval()
+    generator = task.build_generator(models, args, extra_gen_cls_kwargs={"lm_model": lm, "lm_weight": args.lm_weight})
+    tokenizer, bpe = task.build_tokenizer(args), task.build_bpe(args)
+
+    def encode_fn(x):
+        if tokenizer is not None:
+            x = tokenizer.encode(x)
+        if bpe is not None:
+            x = bpe.encode(x)
+        return x
+
+    def decode_fn(x):
+        if bpe is not None:
+            x = bpe.decode(x)
+        if tokenizer is not None:
+            x = tokenizer.decode(x)
+        return x
+
+    max_positions = resolve_max_positions(task.max_positions(), *[m.max_positions() for m in models])
+    prompt_ok = None
+    if is_lm:
+        limit = min(m.max_decoder_positions() for m in models)
+        prompt_ok = lambda n: lm_prompt_limit(n, args.max_len_a, args.max_len_b, limit)
+    strip = ()
+    if is_speech:  # speech_to_text.py:130-135: language tags are not printed
+        from .data import SpeechToTextDataset
+        strip = {i for s, i in tgt_dict.indices.items() if SpeechToTextDataset.is_lang_tag(s)}
+    start_id, nsent, ntok = 0, 0, 0
+    for inputs in buffered_read(args.input, args.buffer_size):
+        results = []
+        for ids, batch, lists in make_batches(inputs, args, task, max_positions, encode_fn, start_id, sys.stderr, prompt_ok):
+            ni = batch["net_input"]
+            if "src_audio" in ni:  # fbank route (data.py): filter banks of the audio batch, computed on the device
+                ni = fbank.materialize({k: (v.cuda() if torch.is_tensor(v) else v) for k, v in ni.items()},
+                                       max_frames=int(ni["src_lengths"].max()))
+            src = ni["src_tokens"]
+            text = not src.is_floating_point()
+            src_host = src.cpu() if text else None
+            src = src.to("cuda", dtype) if (src.dim() == 3 and src.is_floating_point()) else src.cuda()
+            sample = {"net_input": {"src_tokens": src, "src_lengths": ni["src_lengths"].cuda()}}
+            packed = None
+            if lists is not None:
+                from .lexical_constraints import pack_constraints
+                packed = pack_constraints(lists, pad=tgt_dict.pad(), eos=tgt_dict.eos())
+            t0 = time.time()
+            translations = task.inference_step(generator, models, sample, constraints=packed)
+            torch.cuda.synchronize()
+            translate_time = time.time() - t0
+            total_translate_time += translate_time
+            for i, (pos, hypos) in enumerate(zip(ids, translations)):
+                src_i = src_host[i][src_host[i].ne(tgt_dict.pad())] if text else None  # utils.strip_pad
+                results.append((start_id + pos, src_i, hypos, {"constraints": lists[i] if lists is not None else [],
+                                                                "time": translate_time / len(translations)}))
+        ntok += print_translations(results, args, src_dict, tgt_dict, decode_fn, strip)
+        nsent += len(results)
+        start_id += len(inputs)
+    summary = {"event": "interactive", "sentences": nsent, "tokens": ntok, "seconds": time.time() - start_time,
+               "translate_seconds": total_translate_time, "beam": args.beam, "models": len(models), "ignored_flags": ignored}
+    print(json.dumps(summary), file=sys.stderr, flush=True)
     return summary

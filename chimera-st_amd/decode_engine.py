@@ -12,6 +12,7 @@ input is a device-side counter:
     the encoder K/V are neither replicated nor reordered), out-proj GEMM (+residual), LN, fc1 GEMM (+bias+act), fc2 GEMM
     (+bias+residual)] -> LN -> vocabulary GEMM -> cst_beam_step (log-softmax, masks, top-2*beam, finalisation, next rows)
 
+(decoder-only members — language models decoded from prompts — have no cross block: their layers are the LM member's of shallow fusion.)
 The sequence is captured once per (batch, encoder length) in a HIP graph and replayed; the host reads one int32
 (`num_remaining`) every `poll` steps.  Results are the reference's: same candidates, same finalisation order, same
 scores (tests/test_decode_engine_gpu.py checks token ids bit-exactly against the reference's SequenceGenerator fixtures
@@ -142,6 +143,20 @@ class BeamDecodeEngine:
         self.lexical = lexical
         self.decs, self.lm = list(decoders), lm_decoder
         assert 1 <= len(self.decs) <= 8, "cst_beam_step combines at most 8 ensemble members"
+        # DECODER-ONLY: every model is itself a language model (lm_supported: no cross block in any layer) — generation from LM prompts
+        # (fairseq_interactive.py --task language_modeling).  Such members have no encoder K/V, no cross launches and no per-call
+        # projection (_begin_member); the state key carries no source length.  The step is otherwise the same sequence: every member's
+        # layers up to its logits, then cst_beam_step over them (an ensemble of LMs is averaged like any other).
+        n_lm = sum(1 for d in self.decs if all(getattr(l, "encoder_attn", None) is None for l in d.layers))
+        if n_lm not in (0, len(self.decs)):
+            raise ValueError("an ensemble mixes %d decoder-only language models with %d encoder-decoder models: the members must be of "
+                             "one kind" % (n_lm, len(self.decs) - n_lm))
+        self.decoder_only = n_lm > 0
+        assert not self.decoder_only or all(self.lm_supported(d) for d in self.decs), "a language model's decoder is outside lm_supported()"
+        if self.decoder_only and lm_decoder is not None:
+            raise ValueError("shallow fusion (lm_decoder) into a model that is itself a language model is not built: decode the two as an ensemble")
+        if self.decoder_only and attention:
+            raise ValueError("attention (--print-alignment) needs cross attention: a decoder-only language model has none")
         assert self.lm is None or self.lm_supported(self.lm), "the language model's decoder is outside lm_supported()"
         assert self.lm is None or self.lm.output_projection.weight.shape[0] == len(tgt_dict), "the LM's vocabulary must be the target dictionary"
         self.members = self.decs + ([self.lm] if self.lm is not None else [])
@@ -342,7 +357,10 @@ class BeamDecodeEngine:
             # attn_hist[row, s, :]: the head-averaged cross attention row `row` computed at step s (append-only like the K/V caches: a
             # hypothesis' column j is attn_hist[anc[j], j, :]); fin_anc: the ancestry row of every finalised hypothesis (cst_beam_desc)
             st.update(attn_hist=z(bbsz, L1, S[0], dt=torch.float32), fin_anc=z(bsz, beam, L1, dt=torch.int32))
-        ms = [self._alloc_member(dec, bsz, s, dtype, device, hm) for dec, s, hm in zip(self.decs, S, has_mask)]
+        if self.decoder_only:  # (S and has_mask are None)
+            ms = [self._alloc_member(dec, bsz, 0, dtype, device, False) for dec in self.decs]
+        else:
+            ms = [self._alloc_member(dec, bsz, s, dtype, device, hm) for dec, s, hm in zip(self.decs, S, has_mask)]
         if self.lm is not None:
             ms.append(self._alloc_member(self.lm, bsz, 0, dtype, device, False))
             f = L.LmFusionDesc()
@@ -514,7 +532,8 @@ class BeamDecodeEngine:
     @torch.no_grad()
     def generate(self, encoder_outs, bsz, prefix_tokens=None, sample_key=0, constraints=None):
         """encoder_outs: one EncoderOut per model, each with encoder_out [S, B, C] (T x B x C view) and encoder_padding_mask [B, S] or
-        None (each model's own encoder; lengths S and widths may differ).
+        None (each model's own encoder; lengths S and widths may differ).  A decoder-only engine takes None: dtype and device are the
+        first member's embedding table's.
         prefix_tokens: None or int64 [bsz, K] padded with pad, K <= max_len: the tokens forced at the first K steps (--prefix-size);
         it is copied into the engine's own buffer (the caller's tensor is never captured).
         sample_key: the 32-bit key of this call's draws (sampling only), written into the state's buffer before the first step: the
@@ -525,20 +544,26 @@ class BeamDecodeEngine:
         Returns the reference's `finalized` structure (list over sentences of hypothesis dicts, best first)."""
         prefix_len = 0 if prefix_tokens is None else int(prefix_tokens.shape[1])
         assert prefix_tokens is None or (prefix_tokens.dim() == 2 and prefix_tokens.shape[0] == bsz and prefix_len <= self.opt.max_len)
-        assert len(encoder_outs) == len(self.decs), "one encoder output per ensemble member"
+        assert (encoder_outs is None) if self.decoder_only else (len(encoder_outs) == len(self.decs)), \
+            "one encoder output per ensemble member; none for decoder-only members"
         lex = None
         if constraints is not None:
             assert self.lexical is not None, "constraints need an engine built with lexical=\"ordered\" | \"unordered\""
             assert prefix_len == 0, "lexical constraints cannot be combined with prefix_tokens"
             assert constraints.dim() == 2 and constraints.shape[0] == bsz and self.lexical_supported(constraints, self.opt.beam)
             lex = (self.lexical, int(constraints.shape[1]))
-        encs = [e.encoder_out for e in encoder_outs]
-        assert all(e.shape[1] == bsz for e in encs)
-        dtype, device = encs[0].dtype, encs[0].device
-        assert all(e.dtype == dtype for e in encs), "ensemble members must share the storage dtype"
-        masks = [e.encoder_padding_mask for e in encoder_outs]
-        masks = [m if (m is not None and m.dim() == 2) else None for m in masks]
-        S, has_mask = tuple(e.shape[0] for e in encs), tuple(m is not None for m in masks)
+        if self.decoder_only:
+            w = [d.embed_tokens.weight for d in self.decs]
+            encs, masks, S, has_mask, dtype, device = [], [], None, None, w[0].dtype, w[0].device
+            assert all(x.dtype == dtype and x.device == device for x in w), "ensemble members must share the storage dtype and the device"
+        else:
+            encs = [e.encoder_out for e in encoder_outs]
+            assert all(e.shape[1] == bsz for e in encs)
+            dtype, device = encs[0].dtype, encs[0].device
+            assert all(e.dtype == dtype for e in encs), "ensemble members must share the storage dtype"
+            masks = [e.encoder_padding_mask for e in encoder_outs]
+            masks = [m if (m is not None and m.dim() == 2) else None for m in masks]
+            S, has_mask = tuple(e.shape[0] for e in encs), tuple(m is not None for m in masks)
         if self.attention and len(set(S)) > 1:  # (the reference's avg_attn.add_ cannot add them either)
             raise ValueError("attention of an ensemble needs members of one encoder length, got %s" % (S,))
         pk = self._pack(dtype, device)
@@ -621,7 +646,8 @@ class BeamDecodeEngine:
         """Queues the per-call work of one lane on the current stream: every model's static cross-attention K/V of its sentences, the beam
         state, and — first call of a configuration — the eager step 0 and the capture of the step graph.  Returns the number of
         decode steps already taken (1 after that eager step, else 0)."""
-        for dec, m, e, mk in zip(self.decs, st["members"], encb, mask):  # (the LM, last of the members, has no encoder: zip stops before it)
+        # (the LM, last of the members, has no encoder: zip stops before it; decoder-only members have none either: encb is empty)
+        for dec, m, e, mk in zip(self.decs, st["members"], encb, mask):
             self._begin_member(dec, m, e, mk, bsz)
         L.check(L.load().cst_beam_init(ctypes.byref(st["desc"]), L.stream_ptr()), "cst_beam_init")
         if st["lex_desc"] is not None:  # tables and root states from the call's constraints (outside the captured step)

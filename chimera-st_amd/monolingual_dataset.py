@@ -265,3 +265,48 @@ class MonolingualDataset(torch.utils.data.Dataset):
         from . import data as D
         return D.batch_by_size(indices, None, max_tokens, max_sentences, required_batch_size_multiple,
                                sizes=self.sizes[np.asarray(indices, dtype=np.int64)])
+
+
+class PromptDataset(torch.utils.data.Dataset):
+    """The inference dataset of the `language_modeling` task (language_modeling.py:246-289: TokenBlockDataset in "eos" mode, eos stripped,
+    eos prepended; NestedDictionaryDataset with sizes = [src_lengths]) over typed prompts.  src_tokens: one int64 tensor per prompt as
+    encode_line returns it (its final eos included), src_lengths: their lengths.  A batch is {"id", "net_input": {"src_tokens":
+    [B, 1 + longest prompt] = eos + prompt, right-padded, "src_lengths"}, "target": prompt + pad, right-padded}, rows in the given order
+    (this collater does not sort, and the items keep input order: fairseq_dataset.py ordered_indices)."""
+
+    def __init__(self, src_tokens, src_lengths, vocab):
+        assert len(src_tokens) == len(src_lengths)
+        pad, eos = vocab.pad(), vocab.eos()
+        self.vocab = vocab
+        self.prompts = [torch.as_tensor(t, dtype=torch.long) for t in src_tokens]
+        self.prompts = [t[t.ne(eos)] for t in self.prompts]  # (StripTokenDataset: every eos, not just the last)
+        self.sizes = np.array(src_lengths, dtype=np.int64)
+        self.pad, self.eos = pad, eos
+
+    def __len__(self):
+        return len(self.prompts)
+
+    def __getitem__(self, index):
+        p = self.prompts[index]
+        return {"id": index, "source": torch.cat([p.new_tensor([self.eos]), p]), "target": torch.cat([p, p.new_tensor([self.pad])])}
+
+    def collater(self, samples):
+        if len(samples) == 0:
+            return {}
+        src = [s["source"] for s in samples]
+        return {"id": torch.tensor([s["id"] for s in samples]),
+                "net_input": {"src_tokens": collate_tokens(src, self.pad, self.eos, left_pad=False),
+                              "src_lengths": torch.LongTensor([s.numel() for s in src])},
+                "target": collate_tokens([s["target"] for s in samples], self.pad, self.eos, left_pad=False)}
+
+    def num_tokens(self, index):
+        return self.sizes[index]
+
+    def size(self, index):
+        return self.sizes[index]
+
+    def ordered_indices(self):
+        return np.arange(len(self), dtype=np.int64)
+
+    filter_indices_by_size = MonolingualDataset.filter_indices_by_size
+    batch_by_size = MonolingualDataset.batch_by_size

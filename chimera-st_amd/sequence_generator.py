@@ -18,6 +18,10 @@ step), like the dropout masks of rng.py — so the engine and the host loop belo
 (lexical_constraints.py) and shapes each sentence's candidate list by them; the engine runs it as the third selection rule of the merge
 kernel (cst_beam_step_lex), the class below is the host loop's form of the same rule.
 
+Models without an encoder (a `transformer_lm`: EnsembleModel.has_encoder :790-803) are generated from too: the batch size and the source
+length of max_len come from `src_tokens` — the prompt batch of tasks.LanguageModelingTask, which hands the prompts over as prefix_tokens —
+nothing is encoded or reordered, and the engine runs such members as decoders without a cross block (decode_engine.py).
+
 Differences that do not change results: finished sentences are masked out instead of being removed from the batch
 (the reference shrinks the batch, :427-463 — an optimisation only; every sentence's search is independent)."""
 import dataclasses
@@ -286,6 +290,17 @@ class SequenceGenerator:
             if n != len(tgt_dict):
                 raise ValueError("ensemble member %d has a target vocabulary of %d symbols, the dictionary has %d: the members of an "
                                  "ensemble must share the target dictionary" % (i, n, len(tgt_dict)))
+        # decoder-only members (sequence_generator.py:790-803 has_encoder): language models, decoded from prompts given as prefix_tokens
+        n_enc = sum(1 for m in self.models if getattr(m, "encoder", None) is not None)
+        if n_enc not in (0, len(self.models)):
+            raise ValueError("an ensemble mixes %d encoder-decoder models with %d decoder-only language models: the members must be "
+                             "of one kind" % (n_enc, len(self.models) - n_enc))
+        self.has_encoder = n_enc > 0
+        if not self.has_encoder and lm_model is not None:
+            raise ValueError("shallow fusion (lm_model, --lm-path) into a model that is itself a language model is not built: decode "
+                             "the two as an ensemble (--path a.pt:b.pt)")
+        if not self.has_encoder and return_attention:
+            raise ValueError("return_attention (--print-alignment) needs cross attention: a decoder-only language model has none")
         self.pad, self.unk = tgt_dict.pad(), tgt_dict.unk()
         self.eos = tgt_dict.eos() if eos is None else eos
         self.vocab_size = len(tgt_dict)
@@ -352,10 +367,13 @@ class SequenceGenerator:
             m.eval()
 
     @torch.no_grad()
-    def generate(self, models, sample, prefix_tokens=None, sample_key=None, constraints=None, **kwargs):
+    def generate(self, models, sample, prefix_tokens=None, sample_key=None, constraints=None, bos_token=None, **kwargs):
         """sample_key: the 32-bit key of this call's draws (sampling only); default: the next key of the generator's own stream.
         constraints: the packed lexical constraints of the batch, int64 [bsz, W] (lexical_constraints.pack_constraints); needs a
-        LexicallyConstrainedBeamSearch as the search strategy.  None: the search without them."""
+        LexicallyConstrainedBeamSearch as the search strategy.  None: the search without them.
+        bos_token: the token every hypothesis starts from (sequence_generator.py:256); only eos, what the kernels start from, is built."""
+        if bos_token is not None and int(bos_token) != self.eos:
+            raise NotImplementedError("bos_token %d: hypotheses start from eos (%d); --add-bos-token is not built" % (int(bos_token), self.eos))
         return self._generate(sample, prefix_tokens=prefix_tokens, sample_key=sample_key, constraints=constraints)
 
     def _check_constraints(self, constraints, prefix_tokens, bsz):
@@ -455,14 +473,19 @@ class SequenceGenerator:
             if prefix_tokens.size(1) == 0:
                 prefix_tokens = None
         if constraints is not None:
+            if not self.has_encoder:  # (language_modeling.py:301-304)
+                raise NotImplementedError("constrained decoding with a decoder-only language model is not supported")
             constraints = self._check_constraints(constraints, prefix_tokens, bsz)
-        encoder_outs = [m.encoder.forward_torchscript(net_input) for m in self.models]
+        # decoder-only members (:801-803, :883-884): bsz and src_len are the prompt batch's, there is nothing to encode or to reorder
+        encoder_outs = [m.encoder.forward_torchscript(net_input) for m in self.models] if self.has_encoder else None
         if self.fused:
-            ok = len(self.models) <= 8 and all(BeamDecodeEngine.supported(m.decoder) for m in self.models)  # else the whole ensemble takes the host loop
+            member_ok = BeamDecodeEngine.supported if self.has_encoder else BeamDecodeEngine.lm_supported
+            ok = len(self.models) <= 8 and all(member_ok(m.decoder) for m in self.models)  # else the whole ensemble takes the host loop
             if self.lm_model is not None:  # (an LM the engine cannot take sends the whole decode to the host loop)
                 ok = ok and BeamDecodeEngine.lm_supported(self.lm_model.decoder)
             if self.sampling:  # (the wide-vocabulary row kernel only selects: such vocabularies are sampled by the host loop)
-                ok = ok and BeamDecodeEngine.sampling_supported(self.vocab_size, encoder_outs[0].encoder_out.dtype)
+                store = encoder_outs[0].encoder_out.dtype if self.has_encoder else self.model.decoder.embed_tokens.weight.dtype
+                ok = ok and BeamDecodeEngine.sampling_supported(self.vocab_size, store)
             if constraints is not None:  # (more constraint tokens or next tokens than cst_lex_init holds: the host loop)
                 ok = ok and BeamDecodeEngine.lexical_supported(constraints, beam_size)
             if ok:
@@ -477,8 +500,11 @@ class SequenceGenerator:
             self.search.constraint_states = []
             if constraints is not None:
                 self.search.init_constraints(constraints, beam_size)
-        new_order = torch.arange(bsz, device=device).view(-1, 1).repeat(1, beam_size).view(-1)
-        encoder_outs = [m.encoder.reorder_encoder_out(e, new_order) for m, e in zip(self.models, encoder_outs)]
+        if self.has_encoder:
+            new_order = torch.arange(bsz, device=device).view(-1, 1).repeat(1, beam_size).view(-1)
+            encoder_outs = [m.encoder.reorder_encoder_out(e, new_order) for m, e in zip(self.models, encoder_outs)]
+        else:
+            encoder_outs = [None] * len(self.models)
         incremental_states: List[Dict[str, Dict[str, Optional[Tensor]]]] = [{} for _ in self.models]
         lm_state: Dict[str, Dict[str, Optional[Tensor]]] = {}
 
@@ -499,7 +525,8 @@ class SequenceGenerator:
             if reorder_state is not None:
                 for m, inc in zip(self.models, incremental_states):
                     m.decoder.reorder_incremental_state_scripting(inc, reorder_state)
-                encoder_outs = [m.encoder.reorder_encoder_out(e, reorder_state) for m, e in zip(self.models, encoder_outs)]
+                if self.has_encoder:
+                    encoder_outs = [m.encoder.reorder_encoder_out(e, reorder_state) for m, e in zip(self.models, encoder_outs)]
                 if self.lm_model is not None:
                     self.lm_model.decoder.reorder_incremental_state_scripting(lm_state, reorder_state)
             lprobs, avg_attn = self._forward_decoder(tokens[:, :step + 1], encoder_outs, incremental_states)

@@ -85,6 +85,25 @@ class FairseqTask:
                 return generator.generate(models, sample, prefix_tokens=prefix_tokens)
             return generator.generate(models, sample, prefix_tokens=prefix_tokens, constraints=constraints)
 
+    # ---- typed input (fairseq_interactive.py; tasks/fairseq_task.py:289-307, :530-550) -----------------------------
+    def get_interactive_tokens_and_lengths(self, lines, encode_fn):
+        """fairseq_task.py:542-550: every line encoded, then looked up in the source dictionary (eos appended, no new symbols)."""
+        tokens = [self.source_dictionary.encode_line(encode_fn(src_str), add_if_not_exist=False).long() for src_str in lines]
+        return tokens, [t.numel() for t in tokens]
+
+    def build_dataset_for_inference(self, src_tokens, src_lengths, **kwargs):
+        raise NotImplementedError("task %s has no dataset for typed input" % type(self).__name__)
+
+    def build_tokenizer(self, args):
+        """fairseq_task.py:530-532 (--tokenizer): what data.build_tokenizer builds, and refuses."""
+        from . import data as D
+        return D.build_tokenizer({"tokenizer": getattr(args, "tokenizer", None)})
+
+    def build_bpe(self, args):
+        """fairseq_task.py:534-537 (--bpe, --sentencepiece-model)."""
+        from . import data as D
+        return D.build_bpe({"bpe": getattr(args, "bpe", None), "sentencepiece_model": getattr(args, "sentencepiece_model", None)})
+
     # ---- datasets (data.py; tasks/fairseq_task.py:162-275) --------------------------------------------------------
     def dataset(self, split):
         if split not in getattr(self, "datasets", {}):
@@ -198,6 +217,38 @@ class SpeechToTextTask(FairseqTask):
             epoch=epoch, seed=getattr(self.args, "seed", 1), normalize=getattr(self.args, "normalize", False),
             sample_rate=getattr(self.args, "sample_rate", 16000), triplet=self.TRIPLET)
         return self.datasets[split]
+
+    # ---- typed input: the lines are audio paths (speech_to_text.py:140-154, triplet.py:173-188, :234-241) ----------------------
+    def build_tokenizer(self, args):
+        from . import data as D
+        assert self.data_cfg is not None, "typed input needs --data <manifest root> with the --config-yaml file in it"
+        return D.build_tokenizer(self.data_cfg.pre_tokenizer)
+
+    def build_bpe(self, args):
+        from . import data as D
+        assert self.data_cfg is not None, "typed input needs --data <manifest root> with the --config-yaml file in it"
+        return D.build_bpe(self.data_cfg.bpe_tokenizer)
+
+    def get_interactive_tokens_and_lengths(self, lines, encode_fn):
+        """(the paths, per path what the dataset's loader will count for it): waveform samples with use_audio_input, filter-bank
+        frames of a .wav on the device fbank route, rows of a stored feature matrix.  A missing file raises FileNotFoundError, an
+        unreadable or non-PCM one ValueError."""
+        from . import data as D
+        from . import fbank as FB
+        assert self.data_cfg is not None, "typed input needs --data <manifest root> with the --config-yaml file in it"
+        wave, rate = self.data_cfg.use_audio_input, getattr(self.args, "sample_rate", 16000)
+        n_frames = []
+        for p in lines:
+            if not wave and D.fbank_audio_entry(p) is not None:
+                n_frames.append(FB.num_frames(len(D.get_fbank_audio(p, rate))))
+            else:
+                n_frames.append(int(D.get_features_or_waveform(p, need_waveform=wave, sample_rate=rate).shape[0]))
+        return lines, n_frames
+
+    def build_dataset_for_inference(self, src_tokens, src_lengths, **kwargs):
+        from . import data as D
+        cls = D.TripletDataset if self.TRIPLET else D.SpeechToTextDataset
+        return cls("interactive", False, self.data_cfg, list(src_tokens), list(src_lengths))
 
     def build_model(self, args):
         if self.data_cfg is not None:  # speech_to_text.py:119-122
@@ -360,6 +411,13 @@ class TranslationTask(FairseqTask):
         ds.enable_resident()
         self.datasets[split] = ds
         return ds
+
+    def build_dataset_for_inference(self, src_tokens, src_lengths, constraints=None):
+        """translation.py:324-331: the typed sentences as a pair dataset without targets, with the task's padding sides.  (The batch's
+        constraints are packed by the driver, per batch, in the batch's row order: no `constraints` member of the dataset.)"""
+        from . import language_pair_dataset as P
+        return P.LanguagePairDataset(src_tokens, src_lengths, self.source_dictionary, tgt_dict=self.target_dictionary,
+                                     left_pad_source=self.args.left_pad_source, left_pad_target=self.args.left_pad_target)
 
     def build_model(self, args):
         """translation.py:333-362: with --eval-bleu also the detokeniser, the BPE and the generator of --eval-bleu-args."""
@@ -597,6 +655,26 @@ class LanguageModelingTask(FairseqTask):
             if target not in model.supported_targets:
                 raise ValueError("Unsupported language modeling target: {}".format(target))
         return model
+
+    def build_dataset_for_inference(self, src_tokens, src_lengths, **kwargs):
+        """language_modeling.py:246-289: typed prompts, each prefixed with eos and right-padded (monolingual_dataset.PromptDataset)."""
+        from . import monolingual_dataset as M
+        return M.PromptDataset(src_tokens, src_lengths, self.source_dictionary)
+
+    def inference_step(self, generator, models, sample, prefix_tokens=None, constraints=None):
+        """language_modeling.py:291-315: the generator does not read src_tokens of a decoder-only model; the prompt batch becomes
+        prefix_tokens, without its leading eos column (the token every hypothesis starts from)."""
+        with torch.no_grad():
+            bos_token = self.source_dictionary.eos()  # (--add-bos-token is refused by check_args)
+            if constraints is not None:
+                raise NotImplementedError("Constrained decoding with the language_modeling task is not supported")
+            if prefix_tokens is None and sample["net_input"]["src_tokens"].nelement():
+                prefix_tokens = sample["net_input"]["src_tokens"]
+                if prefix_tokens[:, 0].eq(bos_token).all():
+                    prefix_tokens = prefix_tokens[:, 1:]
+                if prefix_tokens.size(1) == 0:  # a batch of empty prompts: nothing is forced
+                    prefix_tokens = None
+            return generator.generate(models, sample, prefix_tokens=prefix_tokens, bos_token=bos_token)
 
     def max_positions(self):
         """The target limit: --max-target-positions, else --tokens-per-sample (what the model is built with)."""
