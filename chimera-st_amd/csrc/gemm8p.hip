@@ -890,6 +890,8 @@ bool cst_gemm8p_supported(const cstg::GemmParams& p, bool ak, bool bk, int64_t n
 
 int cst_gemm8p_launch(cstg::GemmParams p, bool ak, bool bk, int64_t nbatch, hipStream_t s) {
   // the one-extra-operand epilogue instantiation (see EXF): same conditions as the kernel's bf16 image path + exactly one operand
+  // (tests/gemm_ref.py: fast8p / mode8p restate `fast`, `exf` and `plainf` — the route text does not carry the mode — to know which cases
+  //  round the pre-activation into the bf16 image and that modes 0 / 1 / 2 are all reached: a change here is repeated there)
   const bool fast = !p.c_f32 && p.splits == 1 && p.vec_epi && (p.N % 8) == 0 && p.bias_mode != CST_BIAS_ROW &&
                     (p.bias_mode == CST_BIAS_NONE || p.alpha == 1.0f);
   const bool exf = fast && !p.aux_out && ((p.dact != 0) != (p.resid != nullptr)) && (!p.dact || p.aux_in);

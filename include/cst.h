@@ -121,6 +121,10 @@ int cst_layernorm_bwd_tiles(const void* dy, const void* s, const void* gamma, co
  * lda/ldb may be SMALLER than the contiguous extent (overlapping rows = implicit-GEMM conv1d).
  * Epilogue, in order:  v = alpha*acc;  v += bias;  [aux_out = v];  v = act(v);
  *                      [v *= act'(aux_in)];  v += resid;  C = v
+ * One rounding, at the store — except on the bf16 image path of the persistent kernels (gemm8p.hip's fast epilogue, gemm4w.hip: bf16
+ * C, unsplit, 16-byte aligned operands, column bias only with alpha == 1), where the pre-activation v = alpha*acc + bias is rounded to
+ * bf16 once (the reference's bf16 F.linear output; aux_out is that value) before act / dropout / act' / resid act on it.
+ * tests/gemm_ref.py states both forms; tests/test_gemm_parity_gpu.py pins them bit for bit.
  * Batching: two batch levels (e.g. utterance x group); offsets in elements.
  * split_k > 1: partial sums go through `workspace` (cst_gemm_workspace bytes) and are reduced
  * into C by a second kernel (bias/act/resid are applied there).

@@ -323,10 +323,15 @@ def _affine_bound(D, ev, b_mean, rstd, b_rstd, gamma, z):
                     + U32 * (3.0 * (D * rstd[:, None]).abs() * ga + z.abs())) + ETA
 
 
+def _gelu_arg_bound(z, b_z, dt):
+    """GELU(z') against GELU(z), |z' - z| <= b_z, BEFORE any store: (|GELU'(z)| + max|GELU''| b_z) b_z and the approximation."""
+    return (dgelu64(z).abs() + 0.8 * b_z) * b_z + a_gelu(z, dt)
+
+
 def _gelu_out_bound(z, b_z, dt):
-    """GELU(z') against GELU(z), |z' - z| <= b_z: (|GELU'(z)| + max|GELU''| b_z) b_z, the approximation, the bf16 store."""
+    """_gelu_arg_bound and the bf16 store."""
     y = gelu64(z)
-    b = (dgelu64(z).abs() + 0.8 * b_z) * b_z + a_gelu(z, dt)
+    b = _gelu_arg_bound(z, b_z, dt)
     uo = out_u(dt)
     return b * (1.0 + uo) + uo * y.abs() + ETA
 
