@@ -773,10 +773,16 @@ def unpack_rows(y, seq, broadcast=True):
 # ------------------------------------------------------------------------------------------------
 # wav2vec2 conv layer 0 + GroupNorm + GELU
 # ------------------------------------------------------------------------------------------------
+def no_mlen():
+    """CST_NO_MLEN (A/B switch of the tests, read per call): the frame limits are off, every conv computes the frames past each
+    utterance's end as well.  Same bits."""
+    return bool(_os.environ.get("CST_NO_MLEN"))
+
+
 def _conv0_args(wav, w, write_limit, grad_limit):
     """-> (fp32 contiguous wav, w as [C, k], k, the frame limits) of the two layer-0 Functions."""
     C, _, k = w.shape
-    if _os.environ.get("CST_NO_MLEN") or _os.environ.get("CST_GEMM_NO_KLIVE"):
+    if no_mlen() or _os.environ.get("CST_GEMM_NO_KLIVE"):
         write_limit = grad_limit = None  # (with the GEMM-side skipping off, every frame of this layer is read)
     return wav.float().contiguous(), w.reshape(C, k).contiguous(), k, write_limit, grad_limit
 
@@ -837,7 +843,7 @@ class _LnGeluFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, u, gamma, beta, conv_bias, eps, row_limit):
-        if _os.environ.get("CST_NO_MLEN"):
+        if no_mlen():
             row_limit = None
         u = u.contiguous()
         y, mean, rstd = K.ln_gelu_fwd(u, gamma, beta, eps, row_limit)
@@ -872,21 +878,43 @@ def _padded_base(t, L, C):
     return None
 
 
+def _row_padded(B, L, C, dtype, device, zero_edges):
+    """-> (allocation [B, L+2, C], its interior view [B, L, C], uninitialised): the layout _padded_base recognises.  zero_edges: the
+    spare row before and the one after every utterance are zero-filled (the windowed dX GEMMs read them at utterance boundaries)."""
+    full = torch.empty(B, L + 2, C, dtype=dtype, device=device)
+    if zero_edges:
+        full[:, 0].zero_()
+        full[:, L + 1].zero_()
+    return full, full[:, 1:1 + L]
+
+
+def _zero_edged(shape, dim, at, src):
+    """An uninitialised tensor of `shape` whose rows [at, at + n) along `dim` are `src` (n rows there) and whose rows before and
+    behind them are zero: only those edge rows are zero-filled, not the whole buffer."""
+    n = src.shape[dim]
+    out = torch.empty(shape, dtype=src.dtype, device=src.device)
+    out.narrow(dim, 0, at).zero_()
+    out.narrow(dim, at + n, shape[dim] - at - n).zero_()
+    out.narrow(dim, at, n).copy_(src)
+    return out
+
+
 class _Conv1dCLFn(torch.autograd.Function):
     """Channels-last conv1d as implicit GEMMs.
     forward : y[b,t,:] = act(W . x[b, t*s : t*s+k, :])            one GEMM, A rows overlap (lda = s*Cin < K = k*Cin)
     dW      : per-utterance [Cout, k*Cin] partials (both operands mn-major, B rows overlap), summed over the batch
-    dX      : pad == 0, k <= 2s (the wav2vec2 CNN): for every residue r of l mod s one GEMM
+    dX      : pad == 0 and k <= s + 1 (the wav2vec2 CNN): for every residue r of l mod s one GEMM
                  dx[b, s*u + r, :] = sum_i dz[b, u - i, :] . W[:, :, r + s*i]
               whose A rows are again overlapping windows of the (row-padded) dz and whose C rows are written with ldc = s*Cin
               straight into dx — no [B, Lout, k*Cin] column buffer and no col2im pass; GELU'(prev_z) is the epilogue.
+              (k <= s + 1: i <= 1, and s*u + r < Lin <= s*(Lout - 1) + k + s - 1 gives u <= Lout: dz rows -1 .. Lout, one spare row each side.)
               otherwise (padded subsampler convs): column-gradient GEMM + cst_col2im1d.
-    Layers whose incoming gradient is already d/dz (grad_is_dz) keep y / z / dx in a [B, L+2, C] allocation (interior views)
-    so the zero rows the dX windows need at utterance boundaries exist without copying."""
+    Layers whose incoming gradient is already d/dz (grad_is_dz) keep y / z / dx in a [B, L+2, C] allocation (_row_padded: interior
+    views) so the zero rows the dX windows need at utterance boundaries exist without copying."""
 
     @staticmethod
     def forward(ctx, x, w_cl, bias, k, stride, pad, act, prev_z, grad_is_dz, nz_out=None, nz_in=None, unread_ok=False):
-        if _os.environ.get("CST_NO_MLEN"):  # A/B switch of the tests: compute the frames past each utterance's end as well
+        if no_mlen():
             nz_in = None
             fwd_len = None
         else:
@@ -897,10 +925,7 @@ class _Conv1dCLFn(torch.autograd.Function):
         B, Lin, Cin = x.shape
         Cout = w_cl.shape[0]
         if pad:
-            xp = torch.empty(B, Lin + 2 * pad, Cin, dtype=x.dtype, device=x.device)  # (only the pad rows are zero-filled, not the whole buffer)
-            xp[:, :pad].zero_()
-            xp[:, pad + Lin:].zero_()
-            xp[:, pad:pad + Lin] = x
+            xp = _zero_edged((B, Lin + 2 * pad, Cin), 1, pad, x)
         elif x.stride(2) == 1 and x.stride(1) == Cin:
             xp = x  # contiguous or an interior view of a row-padded allocation: only the batch stride differs
         else:
@@ -908,15 +933,15 @@ class _Conv1dCLFn(torch.autograd.Function):
         Lp = Lin + 2 * pad
         Lout = (Lp - k) // stride + 1
         padded_out = bool(grad_is_dz) and act != L.ACT_NONE
-        rows = Lout + 2 if padded_out else Lout
-        y_full = torch.empty(B, rows, Cout, dtype=x.dtype, device=x.device)
-        z_full = torch.empty_like(y_full) if act != L.ACT_NONE else None
-        coff = Cout if padded_out else 0
+        if padded_out:  # (the spare rows of y and z are read by nobody: not zeroed)
+            y_full, y = _row_padded(B, Lout, Cout, x.dtype, x.device, zero_edges=False)
+            z_full, z = _row_padded(B, Lout, Cout, x.dtype, x.device, zero_edges=False)
+        else:
+            y_full = y = torch.empty(B, Lout, Cout, dtype=x.dtype, device=x.device)
+            z_full = z = torch.empty_like(y) if act != L.ACT_NONE else None
         K.gemm(xp, w_cl, y_full, Lout, Cout, k * Cin, a_kmajor=1, b_kmajor=1, lda=stride * Cin, ldb=k * Cin, ldc=Cout, bias=bias,
-               act=act, aux_out=z_full, ld_aux_out=Cout, batch0=B, sa=(xp.stride(0), 0), sc=(rows * Cout, 0), split_k=1,
-               a_off=0, c_off=coff, m_len=fwd_len)  # frames past an utterance's end: unread, left at act(0) = 0
-        y = y_full[:, 1:1 + Lout] if padded_out else y_full
-        z = (z_full[:, 1:1 + Lout] if padded_out else z_full) if z_full is not None else None
+               act=act, aux_out=z_full, ld_aux_out=Cout, batch0=B, sa=(xp.stride(0), 0), sc=(y_full.stride(0), 0), split_k=1,
+               a_off=0, c_off=Cout if padded_out else 0, m_len=fwd_len)  # frames past an utterance's end: unread, left at act(0) = 0
         ctx.save_for_backward(xp, w_cl, z, prev_z)
         ctx.cfg = (B, Lin, Cin, Cout, k, stride, pad, Lout, act, bias is not None, grad_is_dz)
         ctx.set_materialize_grads(False)  # the pre-activation output never carries a gradient
@@ -929,71 +954,98 @@ class _Conv1dCLFn(torch.autograd.Function):
     def backward(ctx, dy, _dz_unused):
         xp, w_cl, z, prev_z = ctx.saved_tensors
         B, Lin, Cin, Cout, k, stride, pad, Lout, act, has_bias, grad_is_dz = ctx.cfg
-        fast = pad == 0 and k <= stride + 1  # every dX window then stays inside the row-padded dz
-        # ---- dz, in a row-padded allocation when the windowed dX GEMMs will read it ----
-        dzp = _padded_base(dy, Lout, Cout) if (act == L.ACT_NONE or grad_is_dz) else None
-        if dzp is None:
-            dyc = dy.contiguous()
-            dzc = K.act_bwd(dyc, z.contiguous(), act) if (act != L.ACT_NONE and not grad_is_dz) else dyc
-            if fast:
-                dzp = torch.empty(B, Lout + 2, Cout, dtype=dy.dtype, device=dy.device)
-                dzp[:, 0].zero_()
-                dzp[:, Lout + 1].zero_()
-                dzp[:, 1:1 + Lout] = dzc
-            dz_rows, dz_bs, dz_off = dzc, Lout * Cout, 0
-        else:
-            dz_rows, dz_bs, dz_off = dzp, (Lout + 2) * Cout, Cout
+        windowed = pad == 0 and k <= stride + 1  # every dX window then stays inside the row-padded dz
+        need_dx, need_dw, need_db = ctx.needs_input_grad[0], ctx.needs_input_grad[1], has_bias and ctx.needs_input_grad[2]
+        dzc, dzp = _conv_dz(dy, z, act, grad_is_dz, windowed)
+        dz2 = None
+        if (need_dx and not windowed) or need_db:  # dz as [B * Lout, Cout] (a view of dzc; a copy of the interior of a padded dy)
+            dz2 = (dzc if dzc is not None else dzp[:, 1:1 + Lout]).reshape(B * Lout, Cout)
         dx = dw = db = None
-        if ctx.needs_input_grad[0]:
-            if fast:
-                dx_padded = prev_z is not None and _padded_base(prev_z, Lin, Cin) is not None
-                rows = Lin + 2 if dx_padded else Lin
-                dx_full = torch.empty(B, rows, Cin, dtype=dy.dtype, device=dy.device)
-                if dx_padded:
-                    dx_full[:, 0].zero_()
-                    dx_full[:, Lin + 1].zero_()
-                pz = prev_z if prev_z is None or dx_padded else prev_z.contiguous()
-                pz_base = _padded_base(prev_z, Lin, Cin) if dx_padded else pz
-                w3 = w_cl.view(Cout, k, Cin)
-                for r in range(stride):
-                    taps = list(range(r, k, stride))
-                    n = len(taps)
-                    U = (Lin - r + stride - 1) // stride
-                    if n == 0 or U <= 0:
-                        continue
-                    # B_r[ci][q*Cout + co] = W[co][ci][r + s*(n-1-q)]   (window position q <-> dz[u - (n-1) + q])
-                    # (taps r, r + s, ... in reverse order by a strided slice and a flip: indexing with a Python list would build the
-                    #  index tensor on the host — a pageable copy, i.e. a stream synchronisation in the middle of the backward pass)
-                    wr = w3[:, r::stride, :].flip(1).permute(2, 1, 0).reshape(Cin, n * Cout).contiguous()
-                    # rows u with stride * u + r >= nz_in[b] read only dz rows that are exactly zero: their K loop is skipped
-                    ml = ctx.nz_in[r] if ctx.nz_in is not None else None
-                    K.gemm(dzp, wr, dx_full, U, Cin, n * Cout, a_kmajor=1, b_kmajor=1, lda=Cout, ldb=n * Cout, ldc=stride * Cin,
-                           batch0=B, sa=((Lout + 2) * Cout, 0), sc=(rows * Cin, 0), a_off=(2 - n) * Cout,
-                           c_off=(Cin if dx_padded else 0) + r * Cin, dact=L.ACT_GELU if prev_z is not None else L.ACT_NONE,
-                           aux_in=pz_base, ld_aux_in=stride * Cin, split_k=1, m_len=ml)
-                dx = dx_full[:, 1:1 + Lin] if dx_padded else dx_full
-            else:
-                dz2 = dz_rows.reshape(B * Lout, Cout) if dzp is None else dzp[:, 1:1 + Lout].reshape(B * Lout, Cout)
-                dcol = torch.empty(B * Lout, k * Cin, dtype=dy.dtype, device=dy.device)
-                K.gemm(dz2, w_cl, dcol, B * Lout, k * Cin, Cout, a_kmajor=1, b_kmajor=0, lda=Cout, ldb=k * Cin, ldc=k * Cin, split_k=1)
-                pzc = prev_z if prev_z is None else prev_z.contiguous()
-                dx = K.col2im1d(dcol, pzc, B, Lin, Lout, Cin, k, stride, pad, L.ACT_GELU if prev_z is not None else 0)
-        if ctx.needs_input_grad[1]:
-            part = torch.empty(B, Cout, k * Cin, dtype=torch.float32, device=dy.device)
-            # one 256 x 256 workgroup per CU: B x tiles workgroups should fill whole rounds of 256 (B = 32, k = 3: 384 = 1.5
-            # rounds -> a 2-way split of the frame axis gives 768 = 3 rounds of half the length)
-            wgs = B * ((Cout + 255) // 256) * ((k * Cin + 255) // 256)
-            rem = wgs % 256
-            sk = 2 if (wgs >= 256 and 0 < rem < 192 and Lout >= 2048) else 1
-            # the sum over the utterances (and over the K slices) is ONE fixed-order pass of cst_reduce_multi over the fp32 partials,
-            # written in the parameter dtype (before: split-K reduce launch + torch sum over the batch + dtype conversion)
-            dw = torch.empty(Cout, k * Cin, dtype=w_cl.dtype, device=dy.device)
-            K.gemm(dz_rows, xp, part, Cout, k * Cin, Lout, a_kmajor=0, b_kmajor=0, lda=Cout, ldb=stride * Cin, ldc=k * Cin, batch0=B,
-                   sa=(dz_bs, 0), sb=(xp.stride(0), 0), sc=(Cout * k * Cin, 0), a_off=dz_off, split_k=sk, k_len=ctx.nz_out, reduce_to=dw)
-            # (not deferred: autograd re-lays this gradient out — permute / reshape back to [Cout, Cin, k] — as soon as it is returned)
-        if has_bias and ctx.needs_input_grad[2]:
-            db = K.colsum(dz_rows.reshape(B * Lout, Cout) if dzp is None else dzp[:, 1:1 + Lout].reshape(B * Lout, Cout), w_cl.dtype)
+        if need_dx and windowed:
+            dx = _conv_dx_windowed(dzp, w_cl, prev_z, ctx.nz_in, Lin, Cin, k, stride)
+        elif need_dx:
+            dx = _conv_dx_col2im(dz2, w_cl, prev_z, B, Lin, Lout, Cin, k, stride, pad)
+        if need_dw:
+            dw = _conv_dw(dzc, dzp, xp, w_cl, ctx.nz_out, Lout, k, stride)
+        if need_db:
+            db = K.colsum(dz2, w_cl.dtype)
         return dx, dw, db, None, None, None, None, None, None, None, None, None
+
+
+def _conv_dz(dy, z, act, grad_is_dz, windowed):
+    """The gradient at the conv's pre-activation output, as the backward GEMMs of _Conv1dCLFn read it -> (dzc, dzp):
+    dzc  contiguous [B, Lout, Cout]; None when dy arrived as the interior of a row-padded allocation and is dz already (no copy)
+    dzp  dz in a [B, Lout+2, Cout] allocation with zero spare rows (_row_padded); None when no windowed dX GEMM will read it"""
+    B, Lout, Cout = dy.shape
+    dzp = _padded_base(dy, Lout, Cout) if (act == L.ACT_NONE or grad_is_dz) else None
+    if dzp is not None:
+        return None, dzp
+    dyc = dy.contiguous()
+    dzc = K.act_bwd(dyc, z.contiguous(), act) if (act != L.ACT_NONE and not grad_is_dz) else dyc
+    if windowed:
+        dzp, interior = _row_padded(B, Lout, Cout, dy.dtype, dy.device, zero_edges=True)
+        interior.copy_(dzc)
+    return dzc, dzp
+
+
+def _conv_dx_windowed(dzp, w_cl, prev_z, nz_in, Lin, Cin, k, stride):
+    """dx [B, Lin, Cin] (pad == 0, k <= stride + 1) from the row-padded dz [B, Lout+2, Cout]: one windowed GEMM per residue of l mod
+    stride with GELU'(prev_z) as its epilogue.  A row-padded prev_z makes dx the interior of a row-padded allocation too."""
+    B, Lout, Cout = dzp.shape[0], dzp.shape[1] - 2, dzp.shape[2]
+    pz_base = _padded_base(prev_z, Lin, Cin) if prev_z is not None else None
+    dx_padded = pz_base is not None
+    if dx_padded:
+        dx_full, dx = _row_padded(B, Lin, Cin, dzp.dtype, dzp.device, zero_edges=True)
+    else:
+        dx_full = dx = torch.empty(B, Lin, Cin, dtype=dzp.dtype, device=dzp.device)
+        pz_base = prev_z if prev_z is None else prev_z.contiguous()
+    w3 = w_cl.view(Cout, k, Cin)
+    for r in range(stride):
+        n = len(range(r, k, stride))  # taps r, r + s, ...
+        U = (Lin - r + stride - 1) // stride
+        if n == 0 or U <= 0:
+            continue
+        # B_r[ci][q*Cout + co] = W[co][ci][r + s*(n-1-q)]   (window position q <-> dz[u - (n-1) + q])
+        # (taps r, r + s, ... in reverse order by a strided slice and a flip: indexing with a Python list would build the
+        #  index tensor on the host — a pageable copy, i.e. a stream synchronisation in the middle of the backward pass)
+        wr = w3[:, r::stride, :].flip(1).permute(2, 1, 0).reshape(Cin, n * Cout).contiguous()
+        # rows u with stride * u + r >= nz_in[b] read only dz rows that are exactly zero: their K loop is skipped
+        ml = nz_in[r] if nz_in is not None else None
+        K.gemm(dzp, wr, dx_full, U, Cin, n * Cout, a_kmajor=1, b_kmajor=1, lda=Cout, ldb=n * Cout, ldc=stride * Cin,
+               batch0=B, sa=((Lout + 2) * Cout, 0), sc=(dx_full.stride(0), 0), a_off=(2 - n) * Cout,
+               c_off=(Cin if dx_padded else 0) + r * Cin, dact=L.ACT_GELU if prev_z is not None else L.ACT_NONE,
+               aux_in=pz_base, ld_aux_in=stride * Cin, split_k=1, m_len=ml)
+    return dx
+
+
+def _conv_dx_col2im(dz2, w_cl, prev_z, B, Lin, Lout, Cin, k, stride, pad):
+    """dx [B, Lin, Cin] of any other conv (the padded subsampler convs) from dz2 [B * Lout, Cout]: the column-gradient GEMM and
+    cst_col2im1d, which multiplies by GELU'(prev_z) on its way if prev_z is given."""
+    Cout = w_cl.shape[0]
+    dcol = torch.empty(B * Lout, k * Cin, dtype=dz2.dtype, device=dz2.device)
+    K.gemm(dz2, w_cl, dcol, B * Lout, k * Cin, Cout, a_kmajor=1, b_kmajor=0, lda=Cout, ldb=k * Cin, ldc=k * Cin, split_k=1)
+    pzc = prev_z if prev_z is None else prev_z.contiguous()
+    return K.col2im1d(dcol, pzc, B, Lin, Lout, Cin, k, stride, pad, L.ACT_GELU if prev_z is not None else 0)
+
+
+def _conv_dw(dzc, dzp, xp, w_cl, nz_out, Lout, k, stride):
+    """dW [Cout, k*Cin] in the parameter dtype from dz (dzc, else the interior of the row-padded dzp: _conv_dz) and the saved input xp
+    [B, Lp, Cin]: per-utterance partials, summed over the batch.  nz_out (int32 [B] or None): dz rows t >= nz_out[b] are zero."""
+    B, Cin, Cout = xp.shape[0], xp.shape[2], w_cl.shape[0]
+    dz_rows, dz_bs, dz_off = (dzc, Lout * Cout, 0) if dzc is not None else (dzp, (Lout + 2) * Cout, Cout)
+    part = torch.empty(B, Cout, k * Cin, dtype=torch.float32, device=xp.device)
+    # one 256 x 256 workgroup per CU: B x tiles workgroups should fill whole rounds of 256 (B = 32, k = 3: 384 = 1.5
+    # rounds -> a 2-way split of the frame axis gives 768 = 3 rounds of half the length)
+    wgs = B * ((Cout + 255) // 256) * ((k * Cin + 255) // 256)
+    rem = wgs % 256
+    sk = 2 if (wgs >= 256 and 0 < rem < 192 and Lout >= 2048) else 1
+    # the sum over the utterances (and over the K slices) is ONE fixed-order pass of cst_reduce_multi over the fp32 partials,
+    # written in the parameter dtype (before: split-K reduce launch + torch sum over the batch + dtype conversion)
+    dw = torch.empty(Cout, k * Cin, dtype=w_cl.dtype, device=xp.device)
+    K.gemm(dz_rows, xp, part, Cout, k * Cin, Lout, a_kmajor=0, b_kmajor=0, lda=Cout, ldb=stride * Cin, ldc=k * Cin, batch0=B,
+           sa=(dz_bs, 0), sb=(xp.stride(0), 0), sc=(Cout * k * Cin, 0), a_off=dz_off, split_k=sk, k_len=nz_out, reduce_to=dw)
+    # (not deferred: autograd re-lays this gradient out — permute / reshape back to [Cout, Cin, k] — as soon as it is returned)
+    return dw
 
 
 def conv1d_cl(x, weight, bias, stride, pad=0, act=None, prev_z=None, grad_is_dz=False, nz_out=None, nz_in=None, unread_ok=False):
@@ -1012,57 +1064,138 @@ def conv1d_cl(x, weight, bias, stride, pad=0, act=None, prev_z=None, grad_is_dz=
 # ------------------------------------------------------------------------------------------------
 # grouped positional conv of wav2vec2 (k taps, `groups` groups, pad k//2, SamePad, GELU, + residual)
 # ------------------------------------------------------------------------------------------------
-# K slices of the positional convolution's weight-gradient GEMM (16 groups x 48 column tiles = 768 workgroups of the 64 x 128 configuration,
-# 1.5 rounds of the 512 that fit the chip): 2 or 3 slices measured the same as 1 inside the update (64.5-65.8 ms per update in all
-# three settings on one box) — a switch for the tools, default 1
-_POSCONV_DW_SPLIT = int(_os.environ.get("CST_POSCONV_DW_SPLIT", 1))
 # the sliding-window kernels (posconv.hip) are built for 48 channels per group and up to 128 taps
 _POSCONV_WINDOW_CG, _POSCONV_WINDOW_KMAX = 48, 128
 
 
-class _PosConvFn(torch.autograd.Function):
-    """Grouped conv, two routes with the same bits.
-    bf16 with 48 channels per group (wav2vec2: 768 / 16) and k <= 128: the sliding-window kernels of posconv.hip, which read x / dz
-    in their channels-last layout, keep a workgroup's frame window in LDS and write dw in the parameter's layout — no staging tensors.
-    Everything else, and every call while CST_POSCONV_GEMM is set (read per call: A/B runs and parity tests): a batched implicit GEMM.
-    For it the input is re-staged GROUP-MAJOR ([G, B, T+k, C/G]: a permuting copy of x plus two zero fills, and the same again for
-    dz in the backward pass — 136 us of copies and 22 us of fills per call at B=32, profiles/posconv_before.txt) so that for one
-    (utterance, group) the im2col row of frame t is the contiguous window starting at frame t: a plain k-major operand with
-    lda = C/G < K (overlapping rows) — no segmented addressing in the inner loop."""
+def _posconv_window_route(x_dtype, w_dtype, bias_dtype, cg, k, gemm_forced):
+    """bf16 with 48 channels per group (wav2vec2: 768 / 16) and k <= 128 takes the window kernels; everything else, and every call
+    while CST_POSCONV_GEMM is set (gemm_forced; read per call: A/B runs and parity tests), the batched implicit GEMM."""
+    return (x_dtype == torch.bfloat16 and w_dtype == x_dtype and cg == _POSCONV_WINDOW_CG and k <= _POSCONV_WINDOW_KMAX
+            and (bias_dtype is None or bias_dtype == x_dtype) and not gemm_forced)
+
+
+def _posconv_geometry(B, T, k):
+    """-> zero frames in front of an utterance's x (padl) / dz (lp), frames per padded utterance Tp, rows Kr of dW's axis kappa = b Tp + t"""
+    padl = k // 2
+    Tp = T + k - 1 + (1 if k % 2 == 0 else 0)  # even k: torch pads k//2 both sides, SamePad drops the last output
+    return padl, k - 1 - padl, Tp, B * Tp - (k - 1)
+
+
+def _posconv_limit(lim, offset, T):
+    """Frames from lim[b] on are zero, so the windows of output frames >= lim[b] + offset are: cst_gemm_desc.m_len (int32 [B]) or None."""
+    return None if lim is None else torch.clamp(lim.to(torch.int32) + offset, max=T).contiguous()
+
+
+def _posconv_w_fwd(weight, groups):
+    """[C, C/g, k] -> [g][co][j][ci]"""
+    cg, k = weight.shape[1], weight.shape[2]
+    return weight.view(groups, cg, cg, k).permute(0, 1, 3, 2).contiguous()
+
+
+def _posconv_w_dx(weight, groups):
+    """[C, C/g, k] -> the flipped [g][ci][j'][co]:
+    dx[m] = dy[m] + sum_j dz[m + padl - j] w_j  = dy[m] + sum_j' dzp[m + j'] wflip[j'],  dzp[(k-1-padl) + t] = dz[t]"""
+    cg, k = weight.shape[1], weight.shape[2]
+    return weight.view(groups, cg, cg, k).flip(3).permute(0, 2, 3, 1).contiguous()
+
+
+def _posconv_group_major(v, groups, Tp, at):
+    """Channels-last v [B, T, C] -> [G, B, Tp, C/G] with v's frames at rows [at, at + T) and zero rows around them.  Group-major OUTSIDE
+    the batch, so that one group's frames of all utterances are one [B * Tp, C/G] matrix (the weight-gradient GEMM runs over it with
+    K = every frame of the batch)."""
+    B, T, C = v.shape
+    cg = C // groups
+    return _zero_edged((groups, B, Tp, cg), 2, at, v.view(B, T, groups, cg).permute(2, 0, 1, 3))
+
+
+def posconv_k_block_stamps(rows, B, Tp, Kr):
+    """The live-block stamps of the weight gradient's K axis kappa = b Tp + t (cst_gemm_desc.k_live: 1 = live): dz is zero from frame
+    rows[b] of utterance b on, and 64-row block kb is live if it starts inside utterance b's live frames, or runs past Tp into a live
+    utterance b + 1.  rows: host integers (list / numpy) -> numpy int32, or a torch tensor -> torch int32 on its device; one rule."""
+    import numpy as np
+    nkb = (Kr + 63) // 64
+    if isinstance(rows, torch.Tensor):
+        n, ks = rows.to(torch.int64), torch.arange(nkb, device=rows.device, dtype=torch.int64) * 64
+    else:
+        n, ks = np.asarray(rows, dtype=np.int64), np.arange(nkb, dtype=np.int64) * 64
+    b0 = ks // Tp
+    t0 = ks - b0 * Tp
+    nxt = (b0 + 1).clip(max=B - 1)
+    live = (t0 < n[b0]) | ((t0 + 64 > Tp) & (b0 + 1 < B) & (n[nxt] > 0))
+    return live.to(torch.int32) if isinstance(rows, torch.Tensor) else live.astype(np.int32)
+
+
+def _posconv_k_live(grad_rows, grad_rows_host, B, Tp, Kr):
+    """cst_gemm_desc.k_live of the weight-gradient reduction, (stamps, epoch 1), or None.  dz is zero from frame grad_rows[b] of
+    utterance b on: the 64-row K blocks of A that lie in those stretches (a third of them at the bench's lengths) are skipped.
+    Row kappa = b Tp + t; a block may run from one utterance's tail into the head of the next."""
+    if grad_rows is None or _os.environ.get("CST_GEMM_NO_KLIVE"):
+        return None
+    if grad_rows_host is None:
+        return posconv_k_block_stamps(grad_rows, B, Tp, Kr), 1
+    # the plan's row counts are host integers already (its one host read): the stamps are a few hundred numbers of
+    # numpy arithmetic and ONE asynchronous copy from a pinned buffer instead of a dozen small launches
+    st = posconv_k_block_stamps(grad_rows_host, B, Tp, Kr)
+    # (a fresh pinned block per call: torch's host allocator does not hand it out again before the copy has run, which
+    #  a buffer kept here could not promise across the micro-batches of an accumulated update)
+    return torch.from_numpy(st).pin_memory().to(grad_rows.device, non_blocking=True), 1
+
+
+class _PosConvWindowFn(torch.autograd.Function):
+    """x + GELU(conv(x) + bias) by the sliding-window kernels of posconv.hip, which read x / dz in their channels-last layout, keep a
+    workgroup's frame window in LDS and write dw in the parameter's layout — no staging tensors."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, groups, lens=None, grad_rows=None, grad_rows_host=None):
-        """x [B,T,C]; weight [C, C/g, k] -> x + GELU(conv(x) + bias)   (one fused GEMM launch).
-        lens (int32 [B], device): frames of x from lens[b] on are ZERO (wav2vec2.py:820-821 zeroes the padding in front of this
-        convolution).  The window of output frame t >= lens[b] + k // 2 then holds nothing but zeros, so its row of the implicit
-        GEMM's A operand is zero: cst_gemm_desc.m_len = lens + k // 2 lets the tiles behind it skip their K loop, and their epilogue
-        on zero accumulators — GELU(bias) + x — IS the value of those frames: every output frame keeps its bits.
-        grad_rows (int32 [B], device): the gradient of the output is exactly zero from frame grad_rows[b] on (the rows a packing plan
-        keeps: pack_rows' backward writes zeros behind them); the windows of dx frames >= grad_rows[b] + k - 1 - k // 2 are zero."""
+    def forward(ctx, x, weight, bias, groups, lens, grad_rows, grad_rows_host):
+        B, T, C = x.shape
+        padl = _posconv_geometry(B, T, weight.shape[2])[0]
+        ml = _posconv_limit(lens, padl, T)
+        xc = x.contiguous()
+        y, z = K.posconv_fwd(xc, _posconv_w_fwd(weight, groups), bias, groups, ml)
+        ctx.save_for_backward(xc, weight, z)
+        ctx.groups, ctx.grad_rows, ctx.grad_rows_host = groups, grad_rows, grad_rows_host
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        xc, weight, z = ctx.saved_tensors
+        B, T, C = xc.shape
+        k, groups = weight.shape[2], ctx.groups
+        padl, lp, Tp, Kr = _posconv_geometry(B, T, k)
+        dy = dy.contiguous()
+        dz = K.act_bwd(dy, z, L.ACT_GELU)
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            wflip = _posconv_w_dx(weight, groups)
+            ml = _posconv_limit(ctx.grad_rows, lp, T)  # (dead tiles: dx = 0 + dy = dy, exactly)
+            dx = K.posconv_dx(dz, wflip, dy, groups, ml)
+        if ctx.needs_input_grad[1]:
+            # the GEMM route's sums in the same order (_PosConvGemmFn.backward), from the channels-last dz and the saved channels-last
+            # input, written as [C, C/g, k] in the parameter's dtype; db: as there
+            if ctx.needs_input_grad[2] and not _os.environ.get("CST_NO_GEMM_COLSUM"):
+                db = torch.empty(C, dtype=dy.dtype, device=dy.device)
+            dw = K.posconv_dw(dz, xc, groups, k, db, _posconv_k_live(ctx.grad_rows, ctx.grad_rows_host, B, Tp, Kr))
+        if ctx.needs_input_grad[2] and db is None:
+            db = K.colsum(dz.view(B * T, C), weight.dtype)
+        return dx, dw, db, None, None, None, None
+
+
+class _PosConvGemmFn(torch.autograd.Function):
+    """x + GELU(conv(x) + bias) as a batched implicit GEMM.  The input is re-staged GROUP-MAJOR ([G, B, T+k, C/G]: a permuting copy
+    of x plus two zero fills, and the same again for dz in the backward pass — 136 us of copies and 22 us of fills per call at B=32,
+    profiles/posconv_before.txt) so that for one (utterance, group) the im2col row of frame t is the contiguous window starting at
+    frame t: a plain k-major operand with lda = C/G < K (overlapping rows) — no segmented addressing in the inner loop."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, groups, lens, grad_rows, grad_rows_host):
         B, T, C = x.shape
         k = weight.shape[2]
         cg = C // groups
-        padl = k // 2
-        Tp = T + k - 1 + (1 if k % 2 == 0 else 0)  # even k: torch pads k//2 both sides, SamePad drops the last output
-        ml = None if lens is None else torch.clamp(lens.to(torch.int32) + padl, max=T).contiguous()
-        window = (x.dtype == torch.bfloat16 and weight.dtype == x.dtype and cg == _POSCONV_WINDOW_CG and k <= _POSCONV_WINDOW_KMAX
-                  and (bias is None or bias.dtype == x.dtype) and not _os.environ.get("CST_POSCONV_GEMM"))
-        ctx.window = window
-        if window:
-            xc = x.contiguous()
-            wg = weight.view(groups, cg, cg, k).permute(0, 1, 3, 2).contiguous()  # [g][co][j][ci]
-            y, z = K.posconv_fwd(xc, wg, bias, groups, ml)
-            ctx.save_for_backward(xc, weight, z)
-            ctx.cfg = (B, T, C, k, groups, cg, padl, Tp)
-            ctx.grad_rows, ctx.grad_rows_host = grad_rows, grad_rows_host
-            return y
-        # [G, B, Tp, C/G]: group-major OUTSIDE the batch, so that one group's frames of all utterances are one [B * Tp, C/G] matrix
-        # (the weight-gradient GEMM below runs over it with K = every frame of the batch)
-        xg = torch.empty(groups, B, Tp, cg, dtype=x.dtype, device=x.device)  # (zero rows around the frames: only those are filled)
-        xg[:, :, :padl].zero_()
-        xg[:, :, padl + T:].zero_()
-        xg[:, :, padl:padl + T] = x.view(B, T, groups, cg).permute(2, 0, 1, 3)
-        wg = weight.view(groups, cg, cg, k).permute(0, 1, 3, 2).contiguous()  # [g][co][j][ci]
+        padl, lp, Tp, Kr = _posconv_geometry(B, T, k)
+        ml = _posconv_limit(lens, padl, T)
+        xg = _posconv_group_major(x, groups, Tp, padl)
+        wg = _posconv_w_fwd(weight, groups)
         y = torch.empty(B, T, C, dtype=x.dtype, device=x.device)
         z = torch.empty_like(y)
         xc = x.contiguous()
@@ -1070,90 +1203,44 @@ class _PosConvFn(torch.autograd.Function):
                sa=(Tp * cg, B * Tp * cg), sb=(0, cg * k * cg), sc=(T * C, cg), bias=bias, sbias=(0, cg), act=L.ACT_GELU,
                aux_out=z, ld_aux_out=C, resid=xc, ld_resid=C, split_k=1, m_len=ml)
         ctx.save_for_backward(xg, weight, z)
-        ctx.cfg = (B, T, C, k, groups, cg, padl, Tp)
         ctx.grad_rows, ctx.grad_rows_host = grad_rows, grad_rows_host
         return y
 
     @staticmethod
     def backward(ctx, dy):
         xg, weight, z = ctx.saved_tensors
-        B, T, C, k, groups, cg, padl, Tp = ctx.cfg
+        groups, B, _, cg = xg.shape
+        T, C, k = dy.shape[1], dy.shape[2], weight.shape[2]
+        padl, lp, Tp, Kr = _posconv_geometry(B, T, k)
         dy = dy.contiguous()
         dz = K.act_bwd(dy, z, L.ACT_GELU)
         dx = dw = db = None
-        window = ctx.window and (_POSCONV_DW_SPLIT == 1 or not ctx.needs_input_grad[1])
-        if ctx.window and not window:  # (a split weight gradient is the GEMM route's: rebuild its operand from the saved input)
-            xc = xg
-            xg = torch.zeros(groups, B, Tp, cg, dtype=xc.dtype, device=xc.device)
-            xg[:, :, padl:padl + T] = xc.view(B, T, groups, cg).permute(2, 0, 1, 3)
-        # dzg[g, b, lp + t] = dz[b, t, group g], zero rows around it, in the frame stride Tp of xg: the operand of BOTH gradient GEMMs
-        lp = k - 1 - padl
-        dzg = None
-        if (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]) and not window:
-            dzg = torch.empty(groups, B, Tp, cg, dtype=dy.dtype, device=dy.device)
-            dzg[:, :, :lp].zero_()
-            dzg[:, :, lp + T:].zero_()
-            dzg[:, :, lp:lp + T] = dz.view(B, T, groups, cg).permute(2, 0, 1, 3)
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            # dzg[g, b, lp + t] = dz[b, t, group g], zero rows around it, in the frame stride Tp of xg: the operand of BOTH gradient GEMMs
+            dzg = _posconv_group_major(dz, groups, Tp, lp)
         if ctx.needs_input_grad[0]:
-            # dx[m] = dy[m] + sum_j dz[m + padl - j] w_j  = dy[m] + sum_j' dzp[m + j'] wflip[j'],  dzp[(k-1-padl) + t] = dz[t]
-            wflip = weight.view(groups, cg, cg, k).flip(3).permute(0, 2, 3, 1).contiguous()  # [g][ci][j'][co]
-            gr = ctx.grad_rows
-            ml = None if gr is None else torch.clamp(gr.to(torch.int32) + lp, max=T).contiguous()  # (dead tiles: dx = 0 + dy = dy, exactly)
-            if window:
-                dx = K.posconv_dx(dz, wflip, dy, groups, ml)
-            else:
-                dx = torch.empty(B, T, C, dtype=dy.dtype, device=dy.device)
-                K.gemm(dzg, wflip, dx, T, cg, k * cg, a_kmajor=1, b_kmajor=1, lda=cg, ldb=k * cg, ldc=C, batch0=B, batch1=groups,
-                       sa=(Tp * cg, B * Tp * cg), sb=(0, cg * k * cg), sc=(T * C, cg), resid=dy, ld_resid=C, split_k=1, m_len=ml)
+            wflip = _posconv_w_dx(weight, groups)
+            ml = _posconv_limit(ctx.grad_rows, lp, T)  # (dead tiles: dx = 0 + dy = dy, exactly)
+            dx = torch.empty(B, T, C, dtype=dy.dtype, device=dy.device)
+            K.gemm(dzg, wflip, dx, T, cg, k * cg, a_kmajor=1, b_kmajor=1, lda=cg, ldb=k * cg, ldc=C, batch0=B, batch1=groups,
+                   sa=(Tp * cg, B * Tp * cg), sb=(0, cg * k * cg), sc=(T * C, cg), resid=dy, ld_resid=C, split_k=1, m_len=ml)
         if ctx.needs_input_grad[1]:
             # dw[g][co][(j,ci)] = sum_{b,t} dz[b, t, g, co] xg[g, b, t + j, ci]: ONE reduction over the frames of the whole batch per
             # group.  Row kappa = b Tp + t of A is dzg's row kappa + lp (zero for t >= T: the windows that would run from one
             # utterance into the next contribute nothing); row kappa of B is the k-frame window of xg starting at frame kappa
             # (overlapping mn-major rows, ldb = cg).  (Before: one [cg, k cg] product per (utterance, group) — 600 MB of fp32
             # partial sums written and read back by a sum over the batch.)
-            Kr = B * Tp - (k - 1)
             if ctx.needs_input_grad[2] and not _os.environ.get("CST_NO_GEMM_COLSUM"):
                 # the bias gradient = column sums of this GEMM's A operand (every dz row is inside its K range, the rest are zeros):
                 # [groups][cg] = channel order (cst_gemm_desc.colsum)
                 db = torch.empty(C, dtype=dy.dtype, device=dy.device)
-            live = None
-            if ctx.grad_rows is not None and not _os.environ.get("CST_GEMM_NO_KLIVE"):
-                # dz is zero from frame grad_rows[b] of utterance b on: the 64-row K blocks of A that lie in those stretches (a third
-                # of them at the bench's lengths) are skipped (cst_gemm_desc.k_live: a block is live iff its stamp equals the epoch, 1).
-                # Row kappa = b Tp + t; a block may run from one utterance's tail into the head of the next.
-                if ctx.grad_rows_host is not None:
-                    # the plan's row counts are host integers already (its one host read): the stamps are a few hundred numbers of
-                    # numpy arithmetic and ONE asynchronous copy from a pinned buffer instead of a dozen small launches
-                    import numpy as np
-                    n = np.asarray(ctx.grad_rows_host, dtype=np.int64)
-                    ks = np.arange((Kr + 63) // 64, dtype=np.int64) * 64
-                    b0 = ks // Tp
-                    t0 = ks - b0 * Tp
-                    nxt = np.minimum(b0 + 1, B - 1)
-                    st = ((t0 < n[b0]) | ((t0 + 64 > Tp) & (b0 + 1 < B) & (n[nxt] > 0))).astype(np.int32)
-                    # (a fresh pinned block per call: torch's host allocator does not hand it out again before the copy has run, which
-                    #  a buffer kept here could not promise across the micro-batches of an accumulated update)
-                    stamps = torch.from_numpy(st).pin_memory().to(dy.device, non_blocking=True)
-                else:
-                    n = ctx.grad_rows.to(torch.int64)
-                    ks = torch.arange((Kr + 63) // 64, device=dy.device, dtype=torch.int64) * 64
-                    b0 = torch.div(ks, Tp, rounding_mode="floor")
-                    t0 = ks - b0 * Tp
-                    nxt = torch.clamp(b0 + 1, max=B - 1)
-                    stamps = ((t0 < n[b0]) | ((t0 + 64 > Tp) & (b0 + 1 < B) & (n[nxt] > 0))).to(torch.int32)
-                live = (stamps, 1)
-            if window:
-                # the same sums in the same order, from the channels-last dz and the saved channels-last input (xg here), written as
-                # [C, C/g, k] in the parameter's dtype
-                dw = K.posconv_dw(dz, xg, groups, k, db, live)
-            else:
-                dwg = torch.empty(groups, cg, k * cg, dtype=torch.float32, device=dy.device)
-                K.gemm(dzg, xg, dwg, cg, k * cg, Kr, a_kmajor=0, b_kmajor=0, lda=cg, ldb=cg, ldc=k * cg, batch0=1, batch1=groups,
-                       sa=(0, B * Tp * cg), sb=(0, B * Tp * cg), sc=(0, cg * k * cg), a_off=lp * cg, split_k=_POSCONV_DW_SPLIT, colsum=db,
-                       k_live=live)
-                dw = dwg.view(groups, cg, k, cg).permute(0, 1, 3, 2).reshape(C, cg, k).to(weight.dtype)
-                if db is not None:
-                    db = db.to(weight.dtype)
+            dwg = torch.empty(groups, cg, k * cg, dtype=torch.float32, device=dy.device)
+            K.gemm(dzg, xg, dwg, cg, k * cg, Kr, a_kmajor=0, b_kmajor=0, lda=cg, ldb=cg, ldc=k * cg, batch0=1, batch1=groups,
+                   sa=(0, B * Tp * cg), sb=(0, B * Tp * cg), sc=(0, cg * k * cg), a_off=lp * cg, split_k=1, colsum=db,
+                   k_live=_posconv_k_live(ctx.grad_rows, ctx.grad_rows_host, B, Tp, Kr))
+            dw = dwg.view(groups, cg, k, cg).permute(0, 1, 3, 2).reshape(C, cg, k).to(weight.dtype)
+            if db is not None:
+                db = db.to(weight.dtype)
         if ctx.needs_input_grad[2] and db is None:
             db = K.colsum(dz.view(B * T, C), weight.dtype)
         return dx, dw, db, None, None, None, None
@@ -1182,7 +1269,17 @@ def weight_norm_last_dim(v, g):
 
 
 def pos_conv_gelu_residual(x, weight, bias, groups, lens=None, grad_rows=None, grad_rows_host=None):
-    return _PosConvFn.apply(x, weight, bias, groups, lens, grad_rows, grad_rows_host)
+    """x [B,T,C]; weight [C, C/g, k] -> x + GELU(conv(x) + bias)   (one fused launch on either route).
+    lens (int32 [B], device): frames of x from lens[b] on are ZERO (wav2vec2.py:820-821 zeroes the padding in front of this
+    convolution).  The window of output frame t >= lens[b] + k // 2 then holds nothing but zeros, so its row of the implicit
+    GEMM's A operand is zero: cst_gemm_desc.m_len = lens + k // 2 lets the tiles behind it skip their K loop, and their epilogue
+    on zero accumulators — GELU(bias) + x — IS the value of those frames: every output frame keeps its bits.
+    grad_rows (int32 [B], device): the gradient of the output is exactly zero from frame grad_rows[b] on (the rows a packing plan
+    keeps: pack_rows' backward writes zeros behind them); the windows of dx frames >= grad_rows[b] + k - 1 - k // 2 are zero.
+    Two routes with the same bits, one Function each."""
+    window = _posconv_window_route(x.dtype, weight.dtype, None if bias is None else bias.dtype, x.shape[2] // groups, weight.shape[2],
+                                   bool(_os.environ.get("CST_POSCONV_GEMM")))
+    return (_PosConvWindowFn if window else _PosConvGemmFn).apply(x, weight, bias, groups, lens, grad_rows, grad_rows_host)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -562,7 +562,8 @@ def ln_gelu_fwd(u, gamma, beta, eps=1e-5, row_limit=None):
 
 def ln_gelu_bwd(dy, u, gamma, beta, mean, rstd, row_limit=None, want_colsum=False, padded=False):
     """-> (du, dgamma, dbeta, colsum(du) or None); the three vectors fp32.  padded: du is the interior view of a [B, L+2, C] allocation
-    whose first and last row per utterance are zero (what the windowed dX GEMMs of functional.conv1d_cl read without a copy)."""
+    whose first and last row per utterance are zero (the layout of functional._row_padded, restated here because this module does not
+    import that one: what the windowed dX GEMMs of functional.conv1d_cl read without a copy)."""
     assert dy.is_contiguous() and u.is_contiguous()
     B, Lr, C = u.shape
     lib = L.load()

@@ -4,8 +4,6 @@ fairseq/models/transformer.py:530-903."""
 import math
 from typing import Dict, List, Optional
 
-import os
-
 import torch
 import torch.nn as nn
 
@@ -58,7 +56,7 @@ class Conv1dSubsampler(nn.Module):
         for _ in range(self.n_layers):
             lens.append(((lens[-1].float() - 1) / 2 + 1).floor().long())
         limits = [None] * self.n_layers
-        if padding_unread and not os.environ.get("CST_NO_MLEN"):
+        if padding_unread and not CF.no_mlen():
             need = lens[-1]  # frames of the last layer's output that are read
             for i in reversed(range(self.n_layers)):
                 limits[i] = need.to(torch.int32).contiguous()

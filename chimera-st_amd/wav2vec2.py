@@ -280,11 +280,11 @@ class TransformerEncoder(nn.Module):
             plan = CF.plan_packed_rows(padding_mask, self.packing_margin())
         if plan is not None and plan.rows >= plan.B * plan.T:
             plan = None  # nothing to drop (no padding beyond the margin)
-        # frame limits of the positional convolution (functional._PosConvFn): the input is zero from each utterance's end on (the
+        # frame limits of the positional convolution (functional.pos_conv_gelu_residual): the input is zero from each utterance's end on (the
         # lines above), so the output tiles whose windows lie in the padding skip their products — exact on every frame — and with a
         # packing plan the gradient of the output is zero behind the rows the plan keeps, which bounds the dX GEMM the same way
         lens = grad_rows = grad_rows_host = None
-        if padding_mask is not None and not os.environ.get("CST_NO_POSCONV_LIMITS") and not os.environ.get("CST_NO_MLEN"):  # (CST_NO_MLEN: every frame of every conv)
+        if padding_mask is not None and not os.environ.get("CST_NO_POSCONV_LIMITS") and not CF.no_mlen():
             lens = plan.kv_len if plan is not None else (~padding_mask).sum(dim=1).to(torch.int32)
             if plan is not None:
                 grad_rows = plan.offsets[1:] - plan.offsets[:-1]

@@ -212,7 +212,7 @@ int cst_gemm(const cst_gemm_desc* d, cst_stream stream);
 /* ------------------------------------------------------------------------------------------
  * wav2vec2 positional convolution, sliding-window kernels (posconv.hip): bf16, C = 48 * groups, k <= 128 taps, pad k / 2,
  * SamePad.  x / dz / dy / y / z / dx are channels-last [B, T, C]; the results have the bits of the cst_gemm route
- * (functional._PosConvFn).  m_len (int32 [B], device, or NULL): frame blocks from m_len[b] on keep zero accumulators.
+ * (functional._PosConvGemmFn).  m_len (int32 [B], device, or NULL): frame blocks from m_len[b] on keep zero accumulators.
  *   fwd: z = conv(x) + bias, y = x + GELU(z);              w     = [g][co][j][ci]
  *   dx : dx = dy + sum_j' dz[m - (k - 1 - k / 2) + j'] w;   wflip = [g][ci][j'][co]  (taps reversed)
  *   dw : dw [C][48][k] (the parameter's layout) and db [C] (or NULL) over all frames of the batch; k_live / k_epoch: the

@@ -1,7 +1,7 @@
 """fp64 restatements, counted forward-error bounds and fp32 emulations of the sliding-window kernels of the positional convolution in
 csrc/posconv.hip: cst_posconv_fwd, cst_posconv_dx, cst_posconv_dw.  Plain torch on the CPU; shared by test_posconv_ref_cpu.py (the
 bounds hold for a faithful fp32 evaluation in two summation shapes and reject every listed defect) and test_posconv_gpu.py (the kernels,
-and the implicit-GEMM route of functional._PosConvFn, under the same bounds).  Built like norm_ref.py, whose constants and GELU pieces
+and the implicit-GEMM route of functional._PosConvGemmFn, under the same bounds).  Built like norm_ref.py, whose constants and GELU pieces
 are used here; nothing about the GELU is restated.
 
 The operations (bf16 in, bf16 out, C = 48 G channels, k <= 128 taps, padl = k // 2):
@@ -37,7 +37,7 @@ Rows of the dW axis whose dz is entirely zero are skipped in both: they add exac
 
 Inputs (case): deterministic per name, bf16-exact, no subnormals; the first and the last min(L, 4) live frames of every utterance are
 four times larger in x, dy and dz, so that a frame leaking across an utterance boundary or into the padding is larger than any bound.
-With limits, x, dy and dz are zero from the limit on, as the callers of _PosConvFn guarantee."""
+With limits, x, dy and dz are zero from the limit on, as the callers of functional.pos_conv_gelu_residual guarantee."""
 import functools
 import zlib
 
@@ -128,7 +128,7 @@ def geometry(B, T, G, k):
 
 
 def k_block_stamps(B, T, k, rows):
-    """The K-block stamps _PosConvFn.backward builds from grad_rows (1 = live), restated: block kb covers rows [64 kb, 64 kb + 64) of
+    """The K-block stamps functional.posconv_k_block_stamps builds from grad_rows (1 = live), restated: block kb covers rows [64 kb, 64 kb + 64) of
     the axis kappa = b Tp + t; it is live if it starts inside utterance b's live frames or runs into a live utterance b + 1."""
     g = geometry(B, T, 1, k)
     out = []

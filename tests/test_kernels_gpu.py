@@ -556,6 +556,46 @@ def test_conv_stack_windowed_dx(dt, Lin):
         check(ws[i].grad, wr[i].grad, dt, "conv stack dW%d" % i, scale=float(wr[i].grad.abs().max()) * (1 if dt == torch.float32 else 2))
 
 
+@pytest.mark.parametrize("dt", DT)
+def test_conv1d_cl_subsampler_route(dt):
+    """The S2T subsampler's route through conv1d_cl: k = 5, stride 2, pad = k // 2 (the input is staged between zero rows), a bias, no
+    activation, dX by the column-gradient GEMM + col2im, against torch autograd of conv1d on the same values.  Once without limits
+    and once with nz_out = (300, 20) and unread_ok (dy is zero from nz_out[b] on in both runs): the second 256-row tile of utterance 1
+    lies wholly behind its limit and is skipped in the forward GEMM, the weight-gradient GEMM stops at the limits; the rows in front
+    of the limits keep their bits, and so does dx, whose route reads no limit."""
+    load_pkg()
+    from importlib import import_module
+    CF = import_module("chimera-st_amd.functional")
+    B, Lin, C, k, s = 2, 600, 64, 5, 2
+    Lout, nz = 300, (300, 20)
+    x0, w0, b0 = rnd(B, Lin, C, dt=dt, seed=5), rnd(C, C, k, dt=dt, seed=6, scale=1.0 / math.sqrt(C * k)), rnd(C, dt=dt, seed=7, scale=0.5)
+    g = rnd(B, Lout, C, dt=dt, seed=77)
+    for b, n in enumerate(nz):
+        g[b, n:] = 0
+
+    def run(limits):
+        x, w, bias = (t.clone().requires_grad_(True) for t in (x0, w0, b0))  # (fresh leaves per run)
+        lim = None if limits is None else torch.tensor(limits, dtype=torch.int32, device="cuda")
+        y, z = CF.conv1d_cl(x, w, bias, s, pad=k // 2, act=None, nz_out=lim, unread_ok=limits is not None)
+        assert z is None and y.shape == (B, Lout, C)
+        y.backward(g)
+        return y.detach(), x.grad, w.grad, bias.grad
+
+    xr, wr, br = (t.float().clone().requires_grad_(True) for t in (x0, w0, b0))
+    ref = F.conv1d(xr.transpose(1, 2), wr, br, stride=s, padding=k // 2).transpose(1, 2)
+    ref.backward(g.float())
+    ref = ref.detach()
+    free, lim = run(None), run(nz)
+    check(free[0], ref, dt, "subsampler conv fwd")
+    for b, n in enumerate(nz):
+        check(lim[0][b, :n], ref[b, :n], dt, "subsampler conv fwd, limited, utterance %d" % b)
+        assert torch.equal(lim[0][b, :n], free[0][b, :n]), "rows in front of the limit of utterance %d changed bits" % b
+    for tag, out in (("", free), (", limited", lim)):
+        for got, want, what in ((out[1], xr.grad, "dX"), (out[2], wr.grad, "dW"), (out[3], br.grad, "db")):
+            check(got, want, dt, "subsampler conv %s%s" % (what, tag), scale=float(want.abs().max()) * (1 if dt == torch.float32 else 2))
+    assert torch.equal(lim[1], free[1]), "dx differs between the limited and the unlimited run"
+
+
 @pytest.mark.parametrize("ak,bk", [(1, 1), (1, 0), (0, 1), (0, 0)])
 @pytest.mark.parametrize("M,N,K_", [(3608, 3592, 328), (512, 1024, 16648), (4096, 4096, 64)])
 def test_gemm_8phase_large(K, ak, bk, M, N, K_):

@@ -1,11 +1,11 @@
-"""cst_posconv_fwd / _dx / _dw (csrc/posconv.hip) and the implicit-GEMM route of functional._PosConvFn on a real MI355X against the fp64
+"""cst_posconv_fwd / _dx / _dw (csrc/posconv.hip) and the implicit-GEMM route (functional._PosConvGemmFn) on a real MI355X against the fp64
 restatements of posconv_ref.py, under ITS per-element bounds (counted from the kernels' operation sequences; test_posconv_ref_cpu.py
 shows that a faithful fp32 evaluation stays inside them in two summation shapes and that every listed defect leaves them).  The cases
 are the smallest shapes that reach each path of the three kernels (posconv_ref.CASES names the path next to every case).
 
 Through the function every reference is a function of the device's own intermediates: z and y from x, w and bias; dz = act_bwd(dy, z)
 recomputed here (the same deterministic kernel: nothing is asserted about it, test_helper_gpu.py covers it); dx from that dz, the
-parameter-layout (unflipped) weight and dy; dw and db from that dz and x.  The weight re-layouts and the flip of _PosConvFn are so held
+parameter-layout (unflipped) weight and dy; dw and db from that dz and x.  The weight re-layouts and the flip of functional.py are so held
 against fp64 and not against themselves.  No element is excluded anywhere.  The GEMM route (CST_POSCONV_GEMM=1) must return the window
 route's bits at every case, and is therefore inside the same bounds.
 

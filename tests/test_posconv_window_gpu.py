@@ -1,5 +1,5 @@
 """Sliding-window kernels of the positional convolution (csrc/posconv.hip) against the implicit-GEMM route of
-functional._PosConvFn (CST_POSCONV_GEMM=1) and against torch's grouped conv1d in fp64.
+functional._PosConvGemmFn (CST_POSCONV_GEMM=1) and against torch's grouped conv1d in fp64.
 
 The window kernels keep the GEMM route's order of summation (one MFMA accumulator chain per output element over the same K
 order, the same epilogue code), so every result is compared with torch.equal: y, z, dx, and also dw / db (the weight-gradient chain —
