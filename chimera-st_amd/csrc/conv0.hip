@@ -623,6 +623,33 @@ __global__ __launch_bounds__(FB * FC) void conv0_bwd_finish_kernel(const float* 
 
 }  // namespace
 
+// Dynamic LDS of every launch below, in bytes, as a function of (k, stride, C):
+//   forward   generic  4 (k C + C + 64 stride + k)             register  4 (128 stride + 10)
+//   backward  generic  4 (k C + 4 C + 2048 stride + k)         register  max(4 (2048 stride + 10), 4096)
+//             MFMA     4 (((2047 stride + 10 + 96 + 3) & ~3) + 6144)   (up to stride 16; behind that the register kernel runs)
+// (none of these kernels has static LDS).  A CU of gfx950 has 160 KiB; a request above 64 KiB is announced with
+// hipFuncAttributeMaxDynamicSharedMemorySize (as posconv.hip and gemm.hip do), one above 160 KiB can never be launched: the entry points
+// refuse it before their first launch, so a refused call has written nothing.
+constexpr size_t C0_LDS_OPT_IN = 64 * 1024, C0_LDS_MAX = 160 * 1024;
+static size_t conv0_fwd_lds(int k, int stride, int64_t C, bool reg_path) {
+  return reg_path ? sizeof(float) * ((size_t)C0R_TB * stride + k) : sizeof(float) * ((size_t)k * C + C + (size_t)C0_TB * stride + k);
+}
+static size_t conv0_bwd_lds(int k, int stride, int64_t C, bool reg_path, bool mfma) {
+  if (mfma) return sizeof(float) * (size_t)((((size_t)(C0R_BWD_TB - 1) * stride + 10 + C0M_PAD + 3) & ~(size_t)3) + 512 * 8 + 512 * 4);
+  if (!reg_path) return sizeof(float) * ((size_t)k * C + 4 * C + (size_t)C0_BWD_TB * stride + k);
+  const size_t lds_r = sizeof(float) * ((size_t)C0R_BWD_TB * stride + k);
+  return lds_r < sizeof(float) * 256 * 4 ? sizeof(float) * 256 * 4 : lds_r;
+}
+// (every kernel's attribute is raised at most once per process; the call is host-side only)
+#define CONV0_LDS_ATTR(kernel, bytes)                                                                                                  \
+  do {                                                                                                                                 \
+    static bool attr_set = false;                                                                                                      \
+    if ((bytes) > C0_LDS_OPT_IN && !attr_set) {                                                                                        \
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)C0_LDS_MAX);  \
+      attr_set = true;                                                                                                                 \
+    }                                                                                                                                  \
+  } while (0)
+
 static int conv0_gram_blocks(int64_t L) { return (int)(cst_ceil_div(L, 256 * 8) < 64 ? cst_ceil_div(L, 256 * 8) : 64); }
 
 extern "C" int64_t cst_conv0_fwd_workspace(int64_t B, int64_t S, int k, int stride) {
@@ -637,6 +664,9 @@ extern "C" int cst_conv0_gn_gelu_fwd(const float* wav, const void* w, const void
   CST_REQUIRE(k >= 1 && k <= KMAX && stride >= 1 && S >= k, "cst_conv0_gn_gelu_fwd: unsupported k=%d stride=%d S=%lld", k, stride, (long long)S);
   CST_REQUIRE(C % 8 == 0 && C >= 8 && C / 8 <= 256, "cst_conv0_gn_gelu_fwd: C=%lld must be a multiple of 8 and <= 2048", (long long)C);
   CST_REQUIRE(dtype == CST_F32 || dtype == CST_BF16, "cst_conv0_gn_gelu_fwd: bad dtype %d", dtype);
+  const bool reg_path = k == 10 && C % 4 == 0 && C / 4 <= 256 && 256 % (C / 4) == 0;
+  const size_t lds = conv0_fwd_lds(k, stride, C, reg_path);
+  CST_REQUIRE(lds <= C0_LDS_MAX, "cst_conv0_gn_gelu_fwd: k=%d stride=%d C=%lld needs %zu bytes of LDS, a CU has %zu", k, stride, (long long)C, lds, C0_LDS_MAX);
   const int64_t L = (S - k) / stride + 1;
   hipStream_t s = (hipStream_t)stream;
   const double bytes = (double)B * S * 4.0 * 2.0 + (double)B * L * C * cst_dtype_size(dtype);
@@ -644,19 +674,26 @@ extern "C" int cst_conv0_gn_gelu_fwd(const float* wav, const void* w, const void
   const int gb = conv0_gram_blocks(L);
   if (k == 10) hipLaunchKernelGGL(conv0_gram_kernel<10>, dim3(gb, (unsigned)B), dim3(256), 0, s, wav, workspace, S, L, k, stride);
   else hipLaunchKernelGGL(conv0_gram_kernel<KMAX>, dim3(gb, (unsigned)B), dim3(256), 0, s, wav, workspace, S, L, k, stride);
-  const size_t lds = sizeof(float) * ((size_t)k * C + C + (size_t)C0_TB * stride + k);
   dim3 sg((unsigned)cst_ceil_div(C, 128), (unsigned)B), fg((unsigned)cst_ceil_div(L, C0_TB), (unsigned)B);
-  const bool reg_path = k == 10 && C % 4 == 0 && C / 4 <= 256 && 256 % (C / 4) == 0;
-  const size_t lds_r = sizeof(float) * ((size_t)C0R_TB * stride + k);
   dim3 fgr((unsigned)cst_ceil_div(L, C0R_TB), (unsigned)B);
   if (dtype == CST_BF16) {
     hipLaunchKernelGGL(conv0_stats_kernel<bf16_t>, sg, dim3(128), 0, s, (const bf16_t*)w, workspace, gb, gram, mean, rstd, C, L, k, eps);
-    if (reg_path) hipLaunchKernelGGL((conv0_fwd_reg_kernel<bf16_t, 10>), fgr, dim3(256), lds_r, s, wav, (const bf16_t*)w, (const bf16_t*)gamma, (const bf16_t*)beta, mean, rstd, (bf16_t*)y, S, L, (int)C, stride, frame_limit);
-    else hipLaunchKernelGGL(conv0_fwd_kernel<bf16_t>, fg, dim3(256), lds, s, wav, (const bf16_t*)w, (const bf16_t*)gamma, (const bf16_t*)beta, mean, rstd, (bf16_t*)y, S, L, (int)C, k, stride);
+    if (reg_path) {
+      CONV0_LDS_ATTR((conv0_fwd_reg_kernel<bf16_t, 10>), lds);
+      hipLaunchKernelGGL((conv0_fwd_reg_kernel<bf16_t, 10>), fgr, dim3(256), lds, s, wav, (const bf16_t*)w, (const bf16_t*)gamma, (const bf16_t*)beta, mean, rstd, (bf16_t*)y, S, L, (int)C, stride, frame_limit);
+    } else {
+      CONV0_LDS_ATTR(conv0_fwd_kernel<bf16_t>, lds);
+      hipLaunchKernelGGL(conv0_fwd_kernel<bf16_t>, fg, dim3(256), lds, s, wav, (const bf16_t*)w, (const bf16_t*)gamma, (const bf16_t*)beta, mean, rstd, (bf16_t*)y, S, L, (int)C, k, stride);
+    }
   } else {
     hipLaunchKernelGGL(conv0_stats_kernel<float>, sg, dim3(128), 0, s, (const float*)w, workspace, gb, gram, mean, rstd, C, L, k, eps);
-    if (reg_path) hipLaunchKernelGGL((conv0_fwd_reg_kernel<float, 10>), fgr, dim3(256), lds_r, s, wav, (const float*)w, (const float*)gamma, (const float*)beta, mean, rstd, (float*)y, S, L, (int)C, stride, frame_limit);
-    else hipLaunchKernelGGL(conv0_fwd_kernel<float>, fg, dim3(256), lds, s, wav, (const float*)w, (const float*)gamma, (const float*)beta, mean, rstd, (float*)y, S, L, (int)C, k, stride);
+    if (reg_path) {
+      CONV0_LDS_ATTR((conv0_fwd_reg_kernel<float, 10>), lds);
+      hipLaunchKernelGGL((conv0_fwd_reg_kernel<float, 10>), fgr, dim3(256), lds, s, wav, (const float*)w, (const float*)gamma, (const float*)beta, mean, rstd, (float*)y, S, L, (int)C, stride, frame_limit);
+    } else {
+      CONV0_LDS_ATTR(conv0_fwd_kernel<float>, lds);
+      hipLaunchKernelGGL(conv0_fwd_kernel<float>, fg, dim3(256), lds, s, wav, (const float*)w, (const float*)gamma, (const float*)beta, mean, rstd, (float*)y, S, L, (int)C, k, stride);
+    }
   }
   return cst_check_launch("cst_conv0_gn_gelu_fwd");
 }
@@ -680,6 +717,12 @@ extern "C" int cst_conv0_gn_gelu_bwd(const void* dy, const float* wav, const voi
   CST_REQUIRE(k >= 1 && k <= KMAX && stride >= 1 && S >= k, "cst_conv0_gn_gelu_bwd: unsupported k=%d stride=%d", k, stride);
   CST_REQUIRE(C % 8 == 0 && C >= 8 && C / 8 <= 256, "cst_conv0_gn_gelu_bwd: C=%lld must be a multiple of 8 and <= 2048", (long long)C);
   CST_REQUIRE(dtype == CST_F32 || dtype == CST_BF16, "cst_conv0_gn_gelu_bwd: bad dtype %d", dtype);
+  const bool reg_path = k == 10 && C % 4 == 0 && C / 4 <= 256 && 256 % (C / 4) == 0;
+  static const bool no_mfma = getenv("CST_CONV0_NO_MFMA") != nullptr;  // (A/B switch: the register kernel)
+  // (the MFMA kernel stages 24 KiB of weights and constants next to the span: from stride 17 on only the register kernel fits)
+  const bool mfma = reg_path && dtype == CST_BF16 && C == 512 && !no_mfma && conv0_bwd_lds(k, stride, C, true, true) <= C0_LDS_MAX;
+  const size_t lds = conv0_bwd_lds(k, stride, C, reg_path, mfma);
+  CST_REQUIRE(lds <= C0_LDS_MAX, "cst_conv0_gn_gelu_bwd: k=%d stride=%d C=%lld needs %zu bytes of LDS, a CU has %zu", k, stride, (long long)C, lds, C0_LDS_MAX);
   const int64_t L = (S - k) / stride + 1;
   hipStream_t s = (hipStream_t)stream;
   const double bytes = (double)B * S * 4.0 + (double)B * L * C * cst_dtype_size(dtype);
@@ -687,36 +730,34 @@ extern "C" int cst_conv0_gn_gelu_bwd(const void* dy, const float* wav, const voi
   const int nblk = conv0_bwd_blocks(L, k, C);
   float* acc = workspace + (size_t)B * nblk * (k + 2) * C;  // the reduced [B][k+2][C] behind the partials
   const dim3 rg((unsigned)B, (unsigned)(k + 2));
-  size_t lds = sizeof(float) * ((size_t)k * C + 4 * C + (size_t)C0_BWD_TB * stride + k);
   dim3 grid((unsigned)cst_ceil_div(L, C0_BWD_TB), (unsigned)B), fg((unsigned)cst_ceil_div(C, FC));
-  const bool reg_path = k == 10 && C % 4 == 0 && C / 4 <= 256 && 256 % (C / 4) == 0;
   if (reg_path) {
-    size_t lds_r = sizeof(float) * ((size_t)C0R_BWD_TB * stride + k);
-    if (lds_r < sizeof(float) * 256 * 4) lds_r = sizeof(float) * 256 * 4;
     dim3 gr((unsigned)cst_ceil_div(L, C0R_BWD_TB), (unsigned)B);
-    static const bool no_mfma = getenv("CST_CONV0_NO_MFMA") != nullptr;  // (A/B switch: the register kernel)
-    if (dtype == CST_BF16 && C == 512 && !no_mfma) {
-      const int span_max = (C0R_BWD_TB - 1) * stride + 10;
-      const size_t lds_m = sizeof(float) * (size_t)(((span_max + C0M_PAD + 3) & ~3) + 512 * 8 + 512 * 4);
-      hipLaunchKernelGGL(conv0_bwd_mfma_kernel, gr, dim3(512), lds_m, s, (const bf16_t*)dy, wav, (const bf16_t*)w, (const bf16_t*)gamma, (const bf16_t*)beta, mean, rstd, workspace, S, L, stride, frame_limit);
+    if (mfma) {
+      CONV0_LDS_ATTR(conv0_bwd_mfma_kernel, lds);
+      hipLaunchKernelGGL(conv0_bwd_mfma_kernel, gr, dim3(512), lds, s, (const bf16_t*)dy, wav, (const bf16_t*)w, (const bf16_t*)gamma, (const bf16_t*)beta, mean, rstd, workspace, S, L, stride, frame_limit);
       hipLaunchKernelGGL(conv0_bwd_reduce_kernel, rg, dim3(256), 0, s, workspace, acc, nblk, k + 2, (int)C);
       hipLaunchKernelGGL(conv0_bwd_finish_kernel<bf16_t>, fg, dim3(FB * FC), 0, s, acc, gram, (const bf16_t*)w, (const bf16_t*)gamma, mean, rstd, dw, dgamma, dbeta, B, C, L, k);
     } else if (dtype == CST_BF16) {
-      hipLaunchKernelGGL((conv0_bwd_reg_kernel<bf16_t, 10>), gr, dim3(256), lds_r, s, (const bf16_t*)dy, wav, (const bf16_t*)w, (const bf16_t*)gamma, (const bf16_t*)beta, mean, rstd, workspace, S, L, (int)C, stride, frame_limit);
+      CONV0_LDS_ATTR((conv0_bwd_reg_kernel<bf16_t, 10>), lds);
+      hipLaunchKernelGGL((conv0_bwd_reg_kernel<bf16_t, 10>), gr, dim3(256), lds, s, (const bf16_t*)dy, wav, (const bf16_t*)w, (const bf16_t*)gamma, (const bf16_t*)beta, mean, rstd, workspace, S, L, (int)C, stride, frame_limit);
       hipLaunchKernelGGL(conv0_bwd_reduce_kernel, rg, dim3(256), 0, s, workspace, acc, nblk, k + 2, (int)C);
       hipLaunchKernelGGL(conv0_bwd_finish_kernel<bf16_t>, fg, dim3(FB * FC), 0, s, acc, gram, (const bf16_t*)w, (const bf16_t*)gamma, mean, rstd, dw, dgamma, dbeta, B, C, L, k);
     } else {
-      hipLaunchKernelGGL((conv0_bwd_reg_kernel<float, 10>), gr, dim3(256), lds_r, s, (const float*)dy, wav, (const float*)w, (const float*)gamma, (const float*)beta, mean, rstd, workspace, S, L, (int)C, stride, frame_limit);
+      CONV0_LDS_ATTR((conv0_bwd_reg_kernel<float, 10>), lds);
+      hipLaunchKernelGGL((conv0_bwd_reg_kernel<float, 10>), gr, dim3(256), lds, s, (const float*)dy, wav, (const float*)w, (const float*)gamma, (const float*)beta, mean, rstd, workspace, S, L, (int)C, stride, frame_limit);
       hipLaunchKernelGGL(conv0_bwd_reduce_kernel, rg, dim3(256), 0, s, workspace, acc, nblk, k + 2, (int)C);
       hipLaunchKernelGGL(conv0_bwd_finish_kernel<float>, fg, dim3(FB * FC), 0, s, acc, gram, (const float*)w, (const float*)gamma, mean, rstd, dw, dgamma, dbeta, B, C, L, k);
     }
     return cst_check_launch("cst_conv0_gn_gelu_bwd");
   }
   if (dtype == CST_BF16) {
+    CONV0_LDS_ATTR(conv0_bwd_kernel<bf16_t>, lds);
     hipLaunchKernelGGL(conv0_bwd_kernel<bf16_t>, grid, dim3(256), lds, s, (const bf16_t*)dy, wav, (const bf16_t*)w, (const bf16_t*)gamma, (const bf16_t*)beta, mean, rstd, workspace, S, L, (int)C, k, stride);
     hipLaunchKernelGGL(conv0_bwd_reduce_kernel, rg, dim3(256), 0, s, workspace, acc, nblk, k + 2, (int)C);
     hipLaunchKernelGGL(conv0_bwd_finish_kernel<bf16_t>, fg, dim3(FB * FC), 0, s, acc, gram, (const bf16_t*)w, (const bf16_t*)gamma, mean, rstd, dw, dgamma, dbeta, B, C, L, k);
   } else {
+    CONV0_LDS_ATTR(conv0_bwd_kernel<float>, lds);
     hipLaunchKernelGGL(conv0_bwd_kernel<float>, grid, dim3(256), lds, s, (const float*)dy, wav, (const float*)w, (const float*)gamma, (const float*)beta, mean, rstd, workspace, S, L, (int)C, k, stride);
     hipLaunchKernelGGL(conv0_bwd_reduce_kernel, rg, dim3(256), 0, s, workspace, acc, nblk, k + 2, (int)C);
     hipLaunchKernelGGL(conv0_bwd_finish_kernel<float>, fg, dim3(FB * FC), 0, s, acc, gram, (const float*)w, (const float*)gamma, mean, rstd, dw, dgamma, dbeta, B, C, L, k);

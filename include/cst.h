@@ -295,7 +295,10 @@ int cst_attn_bwd(const cst_attn_desc* d, cst_stream stream);
  *   wav [B,S] fp32 (the raw samples as the collater hands them over; never down-cast);
  *   w [C,k], gamma, beta [C] in `dtype`;  y [B,L,C] channels-last in `dtype`;
  *   mean,rstd fp32 [B,C];  gram fp32 [B, k*k + k] (per-utterance lag moments, saved for backward);
- *   L = (S-k)/stride + 1;  k <= 16;  C % 8 == 0.
+ *   L = (S-k)/stride + 1;  k <= 16;  C % 8 == 0, C <= 2048.
+ *   A (k, stride, C) whose kernels would need more dynamic LDS than the 160 KiB of a CU is refused (CST_ERR_BAD_ARG) before anything
+ *   is launched or written: forward 4 (k C + C + 64 stride + k) bytes, backward 4 (k C + 4 C + 2048 stride + k); at k = 10 with C / 4
+ *   a divisor of 256 the register kernels need 4 (128 stride + 10) and 4 (2048 stride + 10) instead.
  * ------------------------------------------------------------------------------------------ */
 /* Live-frame limits of the conv feature extractor (wav2vec2.py:685-763) for one batch, all layers in ONE launch: which frames of every
  * layer's output anything reads, from the count of real frames behind the LAST layer (frames past an utterance's end are zeroed
