@@ -882,3 +882,211 @@ def interactive_main(argv=None):
                "translate_seconds": total_translate_time, "beam": args.beam, "models": len(models), "ignored_flags": ignored}
     print(json.dumps(summary), file=sys.stderr, flush=True)
     return summary
+
+
+# --------------------------------------------------------------------------------------------------------------------
+def infer_parser():
+    """The options of fairseq_infer.py: examples/speech_recognition/infer.py:31-86 and the generation group, same names and defaults."""
+    p = argparse.ArgumentParser(allow_abbrev=False)
+    p.add_argument("data")
+    p.add_argument("--task", default="audio_pretraining")
+    p.add_argument("--labels", default=None, help="extension of the label file (e.g. ltr)")
+    p.add_argument("--path", default=None, help="the wav2vec_ctc checkpoint (not needed with --load-emissions)")
+    p.add_argument("--gen-subset", default="test")
+    p.add_argument("--criterion", default="ctc")
+    p.add_argument("--w2l-decoder", default="viterbi", choices=["viterbi", "beam", "kenlm", "fairseqlm"],
+                   help="viterbi: best path; beam: CTC prefix beam search (kenlm / fairseqlm need bindings this build does not have)")
+    p.add_argument("--beam", type=int, default=5)
+    p.add_argument("--nbest", type=int, default=1)
+    p.add_argument("--beam-threshold", type=float, default=25.0)
+    p.add_argument("--beam-size-token", type=int, default=100)
+    p.add_argument("--lm-model", "--kenlm-model", default=None, dest="lm_model", help="a transformer_lm checkpoint over the target dictionary")
+    p.add_argument("--lm-weight", type=float, default=0.2)
+    p.add_argument("--word-score", type=float, default=1.0)
+    p.add_argument("--unk-weight", type=float, default=-math.inf)
+    p.add_argument("--sil-weight", type=float, default=0.0)
+    p.add_argument("--lexicon", default=None)
+    p.add_argument("--dump-features", default=None)
+    p.add_argument("--post-process", "--remove-bpe", default="letter", dest="post_process")
+    p.add_argument("--results-path", default=None)
+    p.add_argument("--max-tokens", type=int, default=None)
+    p.add_argument("--max-sentences", "--batch-size", type=int, default=None, dest="batch_size")
+    p.add_argument("--sample-rate", type=int, default=16000)
+    p.add_argument("--normalize", action="store_true")
+    p.add_argument("--dump-emissions", default=None, help="write the fp32 log-probabilities of every utterance to this file and stop")
+    p.add_argument("--load-emissions", default=None, help="decode these emissions instead of running a model")
+    p.add_argument("--fp16", action="store_true")
+    p.add_argument("--bf16", action="store_true")
+    p.add_argument("--quiet", action="store_true")
+    p.add_argument("--seed", type=int, default=1)
+    return p
+
+
+def check_infer_args(args):
+    """Everything infer.py offers that this build does not is refused by name, before any file is opened."""
+    if args.task != "audio_pretraining":
+        raise NotImplementedError("--task %s: fairseq_infer.py transcribes with the audio_pretraining task" % args.task)
+    if not args.labels:
+        raise ValueError("--labels is required: the references and the dictionary dict.<labels>.txt are found by it")
+    if args.criterion == "asg_loss":
+        raise NotImplementedError("--criterion asg_loss is not built (its transitions come from the wav2letter bindings): use --criterion ctc")
+    if args.criterion != "ctc":
+        raise NotImplementedError("--criterion %s: fairseq_infer.py decodes models trained with --criterion ctc" % args.criterion)
+    if args.w2l_decoder in ("kenlm", "fairseqlm"):
+        raise NotImplementedError("--w2l-decoder %s needs the flashlight / KenLM bindings, which are not in this build: use --w2l-decoder beam "
+                                  "(CTC prefix beam search; --lm-model rescores its n best with a transformer_lm)" % args.w2l_decoder)
+    if args.lexicon is not None:
+        raise NotImplementedError("--lexicon (lexicon-constrained decoding) needs the flashlight bindings, which are not in this build: use "
+                                  "--w2l-decoder beam, which is lexicon-free")
+    if args.sil_weight != 0:
+        raise NotImplementedError("--sil-weight %g is not built: the beam decoder has no silence score" % args.sil_weight)
+    if args.unk_weight != -math.inf:
+        raise NotImplementedError("--unk-weight %g is not built: the beam decoder has no lexicon and so no unknown word" % args.unk_weight)
+    if args.dump_features is not None:
+        raise NotImplementedError("--dump-features is not built: --dump-emissions writes the log-probabilities")
+    if args.path is not None and len(args.path.split(":")) > 1:
+        raise NotImplementedError("--path with several checkpoints is not built: infer.py decodes with models[0] only; pass one file")
+    if args.path is None and args.load_emissions is None:
+        raise ValueError("--path is required (or --load-emissions, which needs no checkpoint)")
+    if args.lm_model is not None and args.w2l_decoder != "beam":
+        raise ValueError("--lm-model rescores the n best of --w2l-decoder beam; %s has one hypothesis" % args.w2l_decoder)
+    if args.max_tokens is None and args.batch_size is None:
+        args.max_tokens = 4000000
+    return args
+
+
+def infer_result_files(args):
+    """infer.py:184-207: {kind: path} of the four result files, or None without --results-path."""
+    if not args.results_path:
+        return None
+    stem = os.path.basename(args.path if args.path is not None else args.load_emissions)
+    return {k: os.path.join(args.results_path, "%s-%s-%s.txt" % (k, stem, args.gen_subset)) for k in ("hypo.word", "hypo.units", "ref.word", "ref.units")}
+
+
+def word_errors(hyp_words, ref_words):
+    """(Levenshtein distance of the two word lists — cst_edit_distance over word ids —, the reference's length)."""
+    from . import kernels as K
+    ids = {}
+    enc = lambda ws: [ids.setdefault(w, len(ids)) for w in ws]
+    return K.edit_distance(enc(hyp_words), enc(ref_words)), len(ref_words)
+
+
+def process_predictions(args, hypos, tgt_dict, target_tokens, files, speaker, sid):
+    """infer.py:115-178: writes the nbest hypotheses and the reference of one utterance as "<text> (<speaker>-<id>)" lines; returns
+    (word errors, reference words, unit errors, reference units) of the TOP hypothesis."""
+    from . import kernels as K
+    from .dictionary import post_process
+    tgt_pieces = tgt_dict.string(target_tokens)
+    tgt_words = post_process(tgt_pieces, args.post_process)
+    first = None
+    for hypo in hypos[:min(len(hypos), args.nbest)]:
+        toks = [int(t) for t in hypo["tokens"].tolist()]
+        hyp_pieces = tgt_dict.string(toks)
+        hyp_words = post_process(hyp_pieces, args.post_process)
+        if first is None:
+            first = (toks, hyp_words)
+        if files is not None:
+            print("{} ({}-{})".format(hyp_pieces, speaker, sid), file=files["hypo.units"])
+            print("{} ({}-{})".format(hyp_words, speaker, sid), file=files["hypo.word"])
+            print("{} ({}-{})".format(tgt_pieces, speaker, sid), file=files["ref.units"])
+            print("{} ({}-{})".format(tgt_words, speaker, sid), file=files["ref.word"])
+        if not args.quiet:
+            print("HYPO:" + hyp_words)
+            print("TARGET:" + tgt_words)
+            print("___________________")
+    toks, hyp_words = first if first is not None else ([], "")
+    w_err, w_len = word_errors(hyp_words.split(), tgt_words.split())
+    return w_err, w_len, K.edit_distance(toks, list(target_tokens)), len(target_tokens)
+
+
+def infer_main(argv=None):
+    """examples/speech_recognition/infer.py:211-454 for a wav2vec_ctc checkpoint: transcribes a subset, writes hypothesis / reference
+    files, reports WER.  Returns (task, wer)."""
+    import numpy as np
+
+    from . import ctc_decoder as CD
+    argv = list(sys.argv[1:] if argv is None else argv)
+    args, ignored = infer_parser().parse_known_args(argv)
+    check_infer_args(args)
+    limit_host_threads()
+    host = CD.host_route()
+    targs = argparse.Namespace(data=args.data, labels=args.labels, criterion="ctc", sample_rate=args.sample_rate, normalize=args.normalize,
+                               max_sample_size=None, min_sample_size=None, enable_padding=False, task="audio_pretraining")
+    task = tasks.AudioPretrainingTask.setup_task(targs)
+    tgt_dict = task.target_dictionary
+    dtype = torch.bfloat16 if (args.fp16 or args.bf16) else torch.float32
+    models, emissions = None, None
+    if args.load_emissions is not None:
+        emissions = np.load(args.load_emissions, allow_pickle=True)
+    else:
+        models, _, _ = checkpoint_utils.load_model_ensemble_and_task([args.path], arg_overrides={"data": args.data}, task=task)
+        models = [m.to("cuda", dtype).eval() for m in models]
+    lm = lm_dict = None
+    if args.lm_model is not None:
+        from .dictionary import Dictionary
+        lm_data = getattr(checkpoint_utils.load_checkpoint_to_cpu(args.lm_model).get("args"), "data", None)
+        lm_dict_path = os.path.join(str(lm_data).split(":")[0], "dict.txt") if lm_data else None
+        lm_dict = Dictionary.load(lm_dict_path) if lm_dict_path and os.path.exists(lm_dict_path) else tgt_dict
+        CD.check_lm_dictionary(lm_dict, tgt_dict)
+        lm = checkpoint_utils.load_language_model(args.lm_model, tgt_dict).to("cuda", dtype).eval()
+    if args.w2l_decoder == "viterbi":
+        decoder = CD.CtcViterbiDecoder(args, tgt_dict)
+    else:
+        decoder = CD.CtcBeamDecoder(args, tgt_dict, lm_model=lm, lm_dict=lm_dict)
+    ds = task.load_dataset(args.gen_subset)
+    itr = task.get_batch_iterator(ds, max_tokens=args.max_tokens, max_sentences=args.batch_size, max_positions=(sys.maxsize, sys.maxsize),
+                                  ignore_invalid_inputs=True, seed=args.seed)
+    names = infer_result_files(args) if args.dump_emissions is None else None
+    files = None
+    if names is not None:
+        os.makedirs(args.results_path, exist_ok=True)
+        files = {k: open(v, "w") for k, v in names.items()}
+    errs_t = lengths_t = c_err_t = c_len_t = nsent = 0
+    dumped, t0 = {}, time.time()
+    for sample in itr.next_epoch_itr(shuffle=False):
+        if not sample or "net_input" not in sample:
+            continue
+        ids = sample["id"].tolist()
+        if emissions is not None:  # infer.py:283-294, 360-365: the stored log-probabilities stand in for the model
+            rows = [torch.from_numpy(np.asarray(emissions[i], dtype=np.float32)) for i in ids]
+            lens = torch.tensor([r.shape[0] for r in rows], dtype=torch.int64)
+            em = torch.zeros(int(lens.max()), len(rows), rows[0].shape[1], dtype=torch.float32)
+            for b, r in enumerate(rows):
+                em[:r.shape[0], b] = r
+            hypos = decoder.decode(em if host else em.cuda(), lens if host else lens.cuda())
+        else:
+            ni = {k: (v.to("cuda", dtype) if v.is_floating_point() else v.cuda()) for k, v in sample["net_input"].items()}
+            logits, lens = decoder.get_emissions(models, {"net_input": ni})
+            if args.dump_emissions is not None:
+                lp = torch.log_softmax(logits.float(), dim=-1).cpu()
+                for b, (i, n) in enumerate(zip(ids, lens.tolist())):
+                    dumped[i] = lp[:n, b].numpy().copy()
+                continue
+            hypos = decoder.decode(logits, lens)
+        for b, sid in enumerate(ids):
+            toks = sample["target"][b]
+            target_tokens = toks[(toks != tgt_dict.pad()) & (toks != tgt_dict.eos())].tolist()
+            w_err, w_len, c_err, c_len = process_predictions(args, hypos[b], tgt_dict, target_tokens, files, None, sid)
+            errs_t, lengths_t, c_err_t, c_len_t = errs_t + w_err, lengths_t + w_len, c_err_t + c_err, c_len_t + c_len
+        nsent += len(ids)
+    if files is not None:
+        for f in files.values():
+            f.close()
+    if args.dump_emissions is not None:  # infer.py:421-427: the list indexed by sample id
+        out = np.empty(len(dumped), dtype=object)
+        for i in range(len(dumped)):
+            out[i] = dumped[i]
+        with open(args.dump_emissions, "wb") as f:
+            np.save(f, out, allow_pickle=True)
+        print("saved %d emissions to %s" % (len(dumped), args.dump_emissions))
+        return task, None
+    dt = time.time() - t0
+    wer = errs_t * 100.0 / lengths_t if lengths_t > 0 else None
+    print("WER: {}".format(wer))
+    print("| Processed {} sentences ({} tokens) in {:.1f}s ({:.2f} sentences/s, {:.2f} tokens/s)".format(
+        nsent, c_len_t, dt, nsent / max(dt, 1e-9), c_len_t / max(dt, 1e-9)))
+    print("| Generate {} with beam={}".format(args.gen_subset, args.beam))
+    print(json.dumps({"event": "infer", "subset": args.gen_subset, "decoder": args.w2l_decoder, "route": "host" if host else getattr(decoder, "last_route", None) or "device",
+                      "wer": wer, "w_errors": errs_t, "w_total": lengths_t, "c_errors": c_err_t, "c_total": c_len_t, "sentences": nsent,
+                      "result_files": names, "ignored_flags": ignored}), flush=True)
+    return task, wer

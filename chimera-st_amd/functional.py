@@ -1434,6 +1434,28 @@ def ctc_greedy(logits, input_len, blank=0):
     return K.ctc_greedy(logits, input_len, int(blank))
 
 
+def ctc_prefix_beam_search(logits, input_len, blank, beam, beam_size_token, beam_threshold, nbest, trace=False):
+    """CTC prefix beam search on the device (cst_ctc_topn + cst_ctc_beam, include/cst.h) on raw logits [T, B, V]: per utterance the
+    list, best first, of (tokens — a list of ints —, score), at most min(nbest, beam) long.  Each frame offers its
+    min(beam_size_token, V - 1) most probable classes.  ONE transfer brings the packed result to the host.  trace=True returns
+    (hyps, trace) with trace = dict(node, pb, pnb [B, T, beam], nodes [B, 4, 1 + T beam]) as host numpy arrays.  A request beyond the
+    kernel's envelope raises (RuntimeError, CST_ERR_UNSUPPORTED); ctc_decoder.CtcBeamDecoder routes such requests to the host."""
+    T, B, V = logits.shape
+    N = max(1, min(int(beam_size_token), V - 1))
+    nb = max(1, min(int(nbest), int(beam)))
+    lists = K.ctc_topn(logits, input_len, int(blank), N)
+    r = K.ctc_beam(logits, input_len, int(blank), lists, int(beam), float(beam_threshold), nb, trace=trace)
+    host = r["packed"].cpu().numpy()
+    o1, o2, o3 = B * nb * T, B * nb * T + B * nb, B * nb * T + 2 * B * nb
+    tokens, lens = host[:o1].reshape(B, nb, T), host[o1:o2].reshape(B, nb)
+    score, n_hyp = host[o2:o3].view("float32").reshape(B, nb), host[o3:]
+    hyps = [[(tokens[b, h, :lens[b, h]].tolist(), float(score[b, h])) for h in range(int(n_hyp[b]))] for b in range(B)]
+    if not trace:
+        return hyps
+    return hyps, dict(node=r["trace_node"].cpu().numpy(), pb=r["trace_pb"].cpu().numpy(), pnb=r["trace_pnb"].cpu().numpy(),
+                      nodes=r["nodes"].cpu().numpy())
+
+
 class _InfoNceFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, y, idx, inv_temp):

@@ -890,6 +890,67 @@ def ctc_greedy(logits, input_len, blank):
     return ids, counts, packed
 
 
+CTC_BEAM_K_MAX, CTC_BEAM_N_MAX, CTC_BEAM_KN_MAX = 128, 128, 8192  # include/cst.h: the envelope of cst_ctc_beam
+
+
+def ctc_beam_supported(K, N):
+    """Whether cst_ctc_beam takes a beam of K prefixes with N classes per frame (beyond: CST_ERR_UNSUPPORTED)."""
+    return 1 <= K <= CTC_BEAM_K_MAX and 1 <= N <= CTC_BEAM_N_MAX and K * N <= CTC_BEAM_KN_MAX
+
+
+def ctc_topn(logits, input_len, blank, N, check=False):
+    """cst_ctc_topn: logits [T, B, V] (layouts as ctc_fwd), input_len int64 [B] on the device -> (lse fp32 [B, T], blank_lp fp32 [B, T],
+    tok_id int32 [B, T, N], tok_lp fp32 [B, T, N]).  check=True validates blank and N here and raises ValueError."""
+    logits, st, sb = _ctc_layout(logits)
+    T, B, V = logits.shape
+    input_len = _ctc_lens(input_len, B, "input_len")
+    if check and not (0 <= blank < V and 1 <= N <= CTC_BEAM_N_MAX):
+        raise ValueError("ctc_topn: blank %d must lie in [0, %d) and N %d in [1, %d]" % (blank, V, N, CTC_BEAM_N_MAX))
+    dev = logits.device
+    n = max(int(N), 1)
+    lse, blank_lp = torch.empty(B, T, dtype=torch.float32, device=dev), torch.empty(B, T, dtype=torch.float32, device=dev)
+    tok_id, tok_lp = torch.empty(B, T, n, dtype=torch.int32, device=dev), torch.empty(B, T, n, dtype=torch.float32, device=dev)
+    L.check(L.load().cst_ctc_topn(L.ptr(logits), st, sb, L.ptr(input_len), int(blank), int(N), L.ptr(lse), L.ptr(blank_lp), L.ptr(tok_id),
+                                  L.ptr(tok_lp), T, B, V, L.dtype_code(logits.dtype), L.stream_ptr()), "cst_ctc_topn")
+    return lse, blank_lp, tok_id, tok_lp
+
+
+def ctc_beam(logits, input_len, blank, lists, K, beam_threshold, nbest, trace=False, check=False):
+    """cst_ctc_beam over `lists` = ctc_topn(logits, input_len, blank, N): -> dict(tokens int32 [B, nbest, T] (-1 padded), len int32
+    [B, nbest], score fp32 [B, nbest], n_hyp int32 [B], packed — ONE int32 buffer all four are views of (score through a float32 view):
+    one transfer brings the result to the host) and, with trace, trace_node int32 / trace_pb / trace_pnb fp32 [B, T, K] and nodes int32
+    [B, 4, 1 + T K] (parents, tokens, child links).  check=True validates the envelope here and raises ValueError."""
+    logits, st, sb = _ctc_layout(logits)
+    T, B, V = logits.shape
+    input_len = _ctc_lens(input_len, B, "input_len")
+    lse, blank_lp, tok_id, tok_lp = lists
+    N = tok_id.shape[2]
+    K, nbest = int(K), int(nbest)
+    if check and not (ctc_beam_supported(K, N) and 1 <= nbest <= K):
+        raise ValueError("ctc_beam: beam %d, %d classes per frame, nbest %d outside K <= %d, N <= %d, K N <= %d, 1 <= nbest <= K"
+                         % (K, N, nbest, CTC_BEAM_K_MAX, CTC_BEAM_N_MAX, CTC_BEAM_KN_MAX))
+    dev = logits.device
+    nb, kk = max(nbest, 1), max(K, 1)
+    packed = torch.empty(B * nb * T + 2 * B * nb + B, dtype=torch.int32, device=dev)
+    o1, o2, o3 = B * nb * T, B * nb * T + B * nb, B * nb * T + 2 * B * nb
+    tokens, lens, score, n_hyp = packed[:o1].view(B, nb, T), packed[o1:o2].view(B, nb), packed[o2:o3].view(torch.float32).view(B, nb), packed[o3:]
+    nodes = torch.empty(B, 4, 1 + T * kk, dtype=torch.int32, device=dev) if trace else None
+    ws = nodes if trace else workspace(int(L.load().cst_ctc_beam_workspace_bytes(T, B, kk, N)), dev)
+    tn = tb = tnb = None
+    if trace:
+        tn = torch.full((B, T, kk), -1, dtype=torch.int32, device=dev)
+        tb = torch.full((B, T, kk), float("-inf"), dtype=torch.float32, device=dev)
+        tnb = torch.full((B, T, kk), float("-inf"), dtype=torch.float32, device=dev)
+    L.check(L.load().cst_ctc_beam(L.ptr(logits), st, sb, L.ptr(input_len), int(blank), L.ptr(lse), L.ptr(blank_lp), L.ptr(tok_id),
+                                  L.ptr(tok_lp), N, K, float(beam_threshold), nbest, L.ptr(ws), L.ptr(tokens), L.ptr(lens), L.ptr(score),
+                                  L.ptr(n_hyp), L.ptr(tn), L.ptr(tb), L.ptr(tnb), T, B, V, L.dtype_code(logits.dtype), L.stream_ptr()),
+            "cst_ctc_beam")
+    out = dict(tokens=tokens, len=lens, score=score, n_hyp=n_hyp, packed=packed)
+    if trace:
+        out.update(trace_node=tn, trace_pb=tb, trace_pnb=tnb, nodes=nodes)
+    return out
+
+
 def edit_distance(a, b):
     """cst_edit_distance: Levenshtein distance of two sequences of ints (host)."""
     import ctypes

@@ -200,6 +200,10 @@ SYMBOLS = [
     ("cst_ctc_bwd", c_int, [c_p, c_i64, c_i64, c_p, c_i64, c_p, c_p, c_i64, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64,
                             c_int, c_p]),
     ("cst_ctc_greedy", c_int, [c_p, c_i64, c_i64, c_p, c_i64, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_int, c_p]),
+    ("cst_ctc_topn", c_int, [c_p, c_i64, c_i64, c_p, c_i64, c_i64, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_int, c_p]),
+    ("cst_ctc_beam_workspace_bytes", c_i64, [c_i64, c_i64, c_i64, c_i64]),
+    ("cst_ctc_beam", c_int, [c_p, c_i64, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_i64, c_f, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
+                             c_i64, c_i64, c_i64, c_int, c_p]),
     ("cst_w2v_negatives", c_int, [ctypes.c_uint32, c_i64, c_i64, c_i64, c_i64, c_p, c_p]),
     ("cst_infonce_fwd", c_int, [c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_int, c_p]),
     ("cst_infonce_bwd_x", c_int, [c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_int, c_p]),

@@ -38,7 +38,8 @@ extern "C" {
  * 13: cst_score_tokens — scores of given target tokens, --score-reference).  cst_beam_step_lm and cst_lm_fusion_desc were ADDED at 13
  * without a bump: no existing signature or layout changed, and a library without the symbol fails at symbol lookup.  The same holds for
  * cst_lex_desc, cst_lex_workspace, cst_lex_init and cst_beam_step_lex (lexical constraints), added later at 13, and for cst_ctc_fwd,
- * cst_ctc_bwd, cst_ctc_greedy and cst_edit_distance (CTC fine-tuning), and for cst_w2v_negatives, cst_infonce_fwd, cst_infonce_bwd_x and
+ * cst_ctc_bwd, cst_ctc_greedy and cst_edit_distance (CTC fine-tuning), for cst_ctc_topn, cst_ctc_beam_workspace_bytes and cst_ctc_beam
+ * (CTC prefix beam search), and for cst_w2v_negatives, cst_infonce_fwd, cst_infonce_bwd_x and
  * cst_infonce_bwd_y, cst_gumbel_vq_workspace, cst_gumbel_vq_fwd and cst_gumbel_vq_bwd (the head of wav2vec2 pre-training), and for the
  * host-only query cst_gemm_route.
  * cst_version() returns the value the library was built with; chimera-st_amd/lib.py refuses a mismatch. */
@@ -580,6 +581,52 @@ int cst_ctc_bwd(const void* logits, int64_t stride_t, int64_t stride_b, const in
                 int64_t V, int dtype, cst_stream stream);
 int cst_ctc_greedy(const void* logits, int64_t stride_t, int64_t stride_b, const int64_t* input_len, int64_t blank, int32_t* argmax_ws,
                    int32_t* ids, int32_t* counts, int64_t T, int64_t B, int64_t V, int dtype, cst_stream stream);
+
+/* ------------------------------------------------------------------------------------------
+ * CTC prefix beam search on RAW logits (fairseq_infer.py --w2l-decoder beam; added at ABI 13 without a bump, as the CTC entries above
+ * were: no existing signature changed).  It stands where examples/speech_recognition/w2l_decoder.py puts the flashlight decoders
+ * (W2lKenLMDecoder, W2lFairseqLMDecoder) behind examples/speech_recognition/infer.py; it is NOT a port of them: flashlight's
+ * lexicon-free decoder keeps the best alignment per state, this one sums all alignments of a prefix (Graves 2006 §7.5.3; Hannun et
+ * al. 2014, Alg. 1).  W2lViterbiDecoder with the ctc criterion is cst_ctc_greedy.  Operands, strides, dtypes, the clamping of input_len
+ * and the CST_ERR_BAD_ARG refusals (nothing launched, no output touched) are those of the CTC block above.
+ *
+ * cst_ctc_topn, one workgroup per live frame (64 threads for V <= 512, else 256), writes (all [B, T] or [B, T, N], overwritten):
+ *   lse fp32: the frame's log-sum-exp, summed in the order of cst_ctc_fwd (equal bits, independent of the layout);
+ *   blank_lp fp32 = x[blank] - lse;  tok_id int32 / tok_lp fp32: the N most probable classes other than `blank` and their
+ *   log-probabilities x - lse, ordered by (log-probability descending, class id ascending); -1 / -inf past the V - 1 classes there are.
+ *   Frames at or past input_len[b] are not read: lse 0, blank_lp -inf, tok_id -1, tok_lp -inf.  1 <= N <= 128, beyond:
+ *   CST_ERR_UNSUPPORTED.
+ * cst_ctc_beam, one workgroup per utterance, loops over that utterance's frames.  The beam holds at most K prefixes with (p_b, p_nb),
+ *   the fp32 log-probabilities of the prefix's alignments so far that end in blank / in non-blank; it starts as the empty prefix with
+ *   (0, -inf).  (+) is logaddexp(a, b) = max + logf(1 + expf(min - max)).  Per frame and beam prefix l, tot = p_b (+) p_nb:
+ *     stay    p_b'(l) = tot + blank_lp;  p_nb'(l) = p_nb(l) + (x[last(l)] - lse) for a non-empty l — the last token's EXACT
+ *             log-probability, read from the logits, whether or not the frame's list holds it;
+ *     extend  by each listed token c:  p_nb'(l + c) = (c == last(l) ? p_b(l) : tot) + tok_lp(c).
+ *   Identity is exact: a prefix is a node (parent node, token) of an append-only per-utterance trie, and l + c IS beam entry l' exactly
+ *   when parent(l') == node(l) and token(l') == c; that term is added to p_nb'(l') (after the stay term; a prefix has one parent, so
+ *   one term at most) and is no candidate of its own.  Candidates score p_b' (+) p_nb'; those of score -inf or below (the best
+ *   score - beam_threshold) are dropped, the best K survive, ties broken by source beam rank, then stay before extension, then token
+ *   id.  A selected extension first looks (parent node, token) up among its parent's children — a prefix that left the beam and comes
+ *   back gets the node it had, so a prefix has ONE node and the identity above is exact — and creates a node only where there is none:
+ *   a frame adds at most K, and the 1 + T K nodes of the table suffice (the kernel checks all the same).  Nothing depends on the rest of the batch or on the order of execution: bit-reproducible.
+ *   Outputs: hyp_tokens int32 [B, nbest, T] (-1 padded), hyp_len int32 [B, nbest], hyp_score fp32 [B, nbest] (-inf past n_hyp[b]),
+ *   n_hyp int32 [B] = min(nbest, the final beam), best first.  input_len[b] = 0: one empty hypothesis of score 0.  1 <= nbest <= K.
+ *   workspace: cst_ctc_beam_workspace_bytes(T, B, K, N) bytes, the node table — per utterance four int32 arrays of 1 + T K entries:
+ *   parent, token, youngest child, next older sibling (0: none); node 0 is the empty prefix (-1, -1).  Readable after the call.
+ *   trace_node int32 / trace_pb / trace_pnb fp32 [B, T, K]: the beam after each live frame, in rank order, -1 / -inf past its size;
+ *   all three NULL: off.  Frames at or past input_len[b] are not written.
+ *   Envelope: K <= 128, N <= 128 and K N <= 8192 (so K = 64 with N = 128, K = 128 with N <= 64).  The extension scores of one frame
+ *   stay in LDS, 4 K N <= 32 KiB, beside 2 x 5 x 128 words of beam, 4 x 128 of stay terms, 2 x 128 of the frame's list and 2 x 128 of
+ *   child-list heads and sources (9 KiB): 41 KiB of the 64 KiB a workgroup may hold statically, three workgroups in a CU's 160 KiB.  Beyond: CST_ERR_UNSUPPORTED, nothing
+ *   launched (ctc_decoder.CtcBeamDecoder then takes its host route).
+ * ------------------------------------------------------------------------------------------ */
+int cst_ctc_topn(const void* logits, int64_t stride_t, int64_t stride_b, const int64_t* input_len, int64_t blank, int64_t N, float* lse,
+                 float* blank_lp, int32_t* tok_id, float* tok_lp, int64_t T, int64_t B, int64_t V, int dtype, cst_stream stream);
+int64_t cst_ctc_beam_workspace_bytes(int64_t T, int64_t B, int64_t K, int64_t N);
+int cst_ctc_beam(const void* logits, int64_t stride_t, int64_t stride_b, const int64_t* input_len, int64_t blank, const float* lse,
+                 const float* blank_lp, const int32_t* tok_id, const float* tok_lp, int64_t N, int64_t K, float beam_threshold,
+                 int64_t nbest, void* workspace, int32_t* hyp_tokens, int32_t* hyp_len, float* hyp_score, int32_t* n_hyp,
+                 int32_t* trace_node, float* trace_pb, float* trace_pnb, int64_t T, int64_t B, int64_t V, int dtype, cst_stream stream);
 
 /* ------------------------------------------------------------------------------------------
  * Contrastive head of wav2vec2 pre-training (added at ABI 13 without a bump: no existing signature changed).  Replaces sample_negatives
